@@ -9,8 +9,11 @@ Inputs (z batches) and weights are resident in HBM before the timed region.  Two
 (--streams), and for the small configurations several logical batches share one launch, each with its own
 batch-norm statistics (--fuse; dcgan32 8 x 256, mnist 32 x 64: ~2048 samples per launch): the work and the results of a step are unchanged.
 The K-step program of a step is replayed as a hipGraph (the launch-bound inner loop: ~1300 dependent launches per step;
---no-graph launches them one by one); the per-kernel HIP-event timing behind `roofline` then comes from one extra step
+--no-graph launches them one by one); with --full the per-kernel HIP-event timing behind `roofline` then comes from one extra step
 launched eagerly on one stream right after the timed region (the same kernels with the same arguments).
+
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the
+line (`value`, `ms_per_step`, ...).  Everything else it can measure (below) runs only with --full.
 
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL), independent z-batches per rank
 (seed 2019+rank, weak scaling), and ONE RCCL all-gather per step of the refined images into the
@@ -20,11 +23,13 @@ distinct ranks an all-gather of rank ids returned, pool bytes, per-rank throughp
 `--backend gloo --share-gpu` is the debug transport: all ranks on device 0, the pool staged through the host -- the whole
 N-rank control flow (self-launch, rank-offset seeds, gather, MAX-reduce, one JSON line) on a 1-GPU box.
 
-Besides the driver's keys the line carries: `roofline` (dominant kernel, flops issued / HIP-event launch time / the peak of the instructions it runs on), `kernels`,
+With --full, besides the driver's keys the line carries: `roofline` (dominant kernel, flops issued / HIP-event launch time / the peak of the instructions it runs on), `kernels`,
 `hbm`, `cpu_baseline`, `other_configs` (mnist, dcgan32, cyclegan256, synthetic2d: samples/s, roofline, cpu_baseline and the bx6 samples/s of each), `class_surface`
 (the reference's verbatim Refiner wiring, engine and generic path) and `bx6` (the opt-in split-bf16 contraction on the headline's workload: never the headline).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs out/      (+ out/<name>.npy: the last timed step's outputs)
+    python bench.py --gpus 1 --full                                       (+ roofline, cpu_baseline, bx6, other configurations, ...)
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8 --steps 3 --warmup 1
     python bench.py --gpus 2 --backend gloo --share-gpu --arch mnist --steps 2 --warmup 1      (1-GPU box)
 """
@@ -243,7 +248,7 @@ def run_synthetic2d(dev, rank, B, Ksteps, rate, steps, warmup, n_streams):
     def step(i):
         with torch.cuda.stream(streams[i % n_streams]):
             base = D.sigmoid_and_saliency(real, want_saliency=False)[0].mean()        # np.mean(real_sigmoid), refiner_cpu.py:23,28 (stays on the device)
-            return D.refine(x[i], base, Ksteps, rate, "ladam")[0]
+            return D.refine(x[i], base, Ksteps, rate, "ladam")
     def trial_ms(cand, m=min(n, 64)):
         nonlocal streams
         streams = cand
@@ -261,10 +266,11 @@ def run_synthetic2d(dev, rank, B, Ksteps, rate, steps, warmup, n_streams):
         step(i)
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
+    last = None
     for i in range(warmup, n):
-        step(i)
+        last = step(i)
     torch.cuda.synchronize(dev)
-    return time.perf_counter() - t0, (S, Ws, bs, x, real)
+    return time.perf_counter() - t0, (S, Ws, bs, x, real), last
 
 
 def cpu_baseline_synthetic2d(S, Ws, bs, x, real, B, Ksteps, rate, reps=20):
@@ -291,7 +297,9 @@ def bench_synthetic2d(args, dev, rank, world):
     (synthetic/main.py:32-62) -- the whole refiner_cpu loop as one launch per batch (cgs_amd.synthetic)."""
     B, Ksteps = args.batch or 512, args.refine_steps or 10
     n_streams = args.streams if args.streams > 0 else 8
-    dt, (S, Ws, bs, x, real) = run_synthetic2d(dev, rank, B, Ksteps, args.rate, args.steps, args.warmup, n_streams)
+    dt, (S, Ws, bs, x, real), last = run_synthetic2d(dev, rank, B, Ksteps, args.rate, args.steps, args.warmup, n_streams)
+    if rank == 0 and args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, {"best_x": last[0], "best_step": last[1]})
     if rank == 0:
         out = {"metric": f"refined samples/sec @ {Ksteps} refinement steps", "value": round(world * B * args.steps / dt, 1), "unit": "samples/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4),
@@ -299,7 +307,7 @@ def bench_synthetic2d(args, dev, rank, world):
                "config": {"workload": f"synthetic2d Imbal-8Gaussians MLP-GAN D 2-64x5-1, batch {B}, K={Ksteps}, ladam rate {args.rate}: "
                                       f"real-batch baseline + fused K-step refine (3 launches per batch, no host synchronisation), {n_streams} batches in flight"},
                "roofline": None, "lib": lib_stamp()}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_synthetic2d(S, Ws, bs, x, real, B, Ksteps, args.rate)
         emit(out, args.detail)
 
@@ -393,7 +401,7 @@ def other_configs(dev, skip, want_cpu):
         del z, P
         torch.cuda.empty_cache()
     if skip != "synthetic2d":
-        dt, (S, Ws, bs, x, real) = run_synthetic2d(dev, 0, 512, 10, 0.1, 256, 16, 8)
+        dt, (S, Ws, bs, x, real), _ = run_synthetic2d(dev, 0, 512, 10, 0.1, 256, 16, 8)
         out["synthetic2d"] = {"samples_per_s": round(512 * 256 / dt, 1), "batch": 512, "refine_steps": 10, "method": "ladam",
                               "batches_in_flight": 8, "steps": 256, "roofline": None}
         if want_cpu:
@@ -718,6 +726,29 @@ def emit(full, detail_path):
     print(text, flush=True)
 
 
+DUMP_BUDGET = 64 * 10**6     # bytes over all arrays of --dump-outputs
+DUMP_SEED = 2019             # the row sample of an output above the budget: the same rows in every run and every build
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: ``arrays`` (name -> tensor, what the timed path returned in its last step) as ``path/<name>.npy``, float32
+    (float64 for double and integer arrays: exact).  Above ``budget`` bytes in all, every array of more than one row keeps the same
+    fraction of its rows: a sorted RandomState(DUMP_SEED) sample, identical for arrays of one length."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu() if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t))
+        host[name] = (t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()).numpy()
+    room = budget - 4096 * len(host)                     # (the .npy headers)
+    fixed = sum(a.nbytes for a in host.values() if a.ndim == 0 or len(a) <= 1)
+    total = sum(a.nbytes for a in host.values())
+    frac = 1.0 if total <= room else max(0.0, (room - fixed) / (total - fixed))
+    for name, a in host.items():
+        if frac < 1.0 and a.ndim > 0 and len(a) > 1:
+            a = a[np.sort(np.random.RandomState(DUMP_SEED).choice(len(a), max(1, int(len(a) * frac)), replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def self_launch(n_gpus):
     """`python bench.py --gpus N` (N > 1) outside torch.distributed.run: start the N ranks as CHILD processes
     (`python -m torch.distributed.run --nproc-per-node N bench.py <same arguments>`) before this process has touched the
@@ -767,15 +798,21 @@ def main():
     ap.add_argument("--contraction", default="f32", choices=["f32", "bx6"],
                     help="f32 (default, the headline): every contraction on the exact-fp32 matrix instructions.  bx6: opt-in -- the layers with "
                          "a multiple of 64 output channels, Cred %% 32 == 0 and GPU-filling grids run on the bf16 matrix cores with every fp32 operand split exactly into three bf16 pieces "
-                         "(six products, fp32 accumulate: an fp32 chain's accuracy, DESIGN.md); the line's dtype says so.  The default run "
+                         "(six products, fp32 accumulate: an fp32 chain's accuracy, DESIGN.md); the line's dtype says so.  A --full run "
                          "reports this mode as a second object `bx6` next to the f32 headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the profiled step behind `roofline` / `kernels` / `hbm`, `cpu_baseline`, `bx6`, "
+                         "`other_configs`, `class_surface`, `f1`, `shaping` (without it a run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         f"<= {DUMP_BUDGET // 10**6} MB in all: a fixed sample of rows beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the mnist / dcgan32 / synthetic2d samples/s that are measured after the headline's timed region")
+                    help="(--full) skip the mnist / dcgan32 / synthetic2d samples/s that are measured after the headline's timed region")
     ap.add_argument("--detail", default=DETAIL_PATH,
                     help="sidecar file for the full record (kernel / hbm tables, per-configuration rooflines, class surface, f1, shaping: everything the "
                          "compact stdout line summarises in one number each); '' = do not write it")
-    ap.add_argument("--by-layer", action="store_true", help="key the per-kernel timing records by layer shape too (diagnostic)")
+    ap.add_argument("--by-layer", action="store_true", help="(--full) key the per-kernel timing records by layer shape too (diagnostic)")
     args = ap.parse_args()
     if args.steps <= 0:
         args.steps = 256 if args.arch == "synthetic2d" else 12
@@ -884,7 +921,8 @@ def main():
         e, st = engines[j], streams[j]
         timed = i >= args.warmup
         with torch.cuda.stream(st):
-            img = e.refine_from_z(z[i], Ksteps, args.rate)[0]
+            res = e.refine_from_z(z[i], Ksteps, args.rate)
+            img = res[0]
             if use_dist:
                 if timed:
                     g0 = torch.cuda.Event(enable_timing=True); g0.record(st)
@@ -896,7 +934,7 @@ def main():
                 ev = torch.cuda.Event(enable_timing=True)
                 ev.record(st)
                 done_ev.append(ev)
-        return img
+        return res
 
     for i in range(args.warmup):
         step(i)
@@ -904,14 +942,14 @@ def main():
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize(dev)
-    live_profile = rank == 0 and not args.graph and n_flight == 1
+    live_profile = args.full and rank == 0 and not args.graph and n_flight == 1
     if live_profile:                      # one batch in flight: per-launch HIP events inside the timed region
         K.PROFILE = {}
         K.PROFILE_BY_LAYER = args.by_layer
     t0 = time.perf_counter()
-    last_img = None
+    last = None
     for i in range(args.warmup, n_batches):
-        last_img = step(i)
+        last = step(i)
     torch.cuda.synchronize(dev)
     dt_own = time.perf_counter() - t0                                   # this rank's own work, before it waits for the others
     if use_dist:
@@ -919,10 +957,13 @@ def main():
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
     prof, K.PROFILE = K.PROFILE, None
-    # (this rank's last images, summed BEFORE the profiling step below re-uses engine 0 and its output buffer)
-    own_sum = float(last_img.double().sum().item()) if (use_dist and last_img is not None) else 0.0
+    # (this rank's last outputs, summed and dumped BEFORE the profiling step below re-uses engine 0 and its output buffers)
+    own_sum = float(last[0].double().sum().item()) if (use_dist and last is not None) else 0.0
+    if rank == 0 and args.dump_outputs and last is not None:
+        names = ("images", "default_logit", "optimal_logit", "optimal_step", "optimal_feature")    # RefineEngine.refine's return
+        dump_outputs(args.dump_outputs, dict(zip(names, last), **({"pool": pools[(n_batches - 1) % n_flight]} if use_dist else {})))
     prof_ms, prof_note, prof_wall_s = dt * 1e3, "HIP events around every launch inside the timed region", None
-    if rank == 0 and not live_profile and not (args.sync_bn and world > 1):      # (synchronised batch norm: a step is a collective of ALL ranks)
+    if args.full and rank == 0 and not live_profile and not (args.sync_bn and world > 1):      # (synchronised batch norm: a step is a collective of ALL ranks)
         # several batches in flight: kernels of different streams overlap, so a per-launch duration taken inside the
         # timed region would include the other stream's work; and a replayed hipGraph has no per-launch host hook.
         # Time ONE more step alone on one stream instead, launched eagerly (the same kernels with the same arguments).
@@ -986,8 +1027,8 @@ def main():
                 prof, prof_ms, 1e3 * dt / args.steps, prof_note, args.arch == "dcgan64" and B == 1024 and G == 1,
                 prof_steps=args.steps if live_profile else 1)
             out["executed_tflops"] = round(world * ex_step / (1e3 * dt / args.steps) / 1e9, 2)      # whole job, padding taps not counted
-        cpu = cpu_baseline(args.arch, Ksteps, args.rate) if world == 1 and not args.no_cpu_baseline else None   # (calibrates the host thread count)
-        if world == 1 and not args.no_other_configs:
+        cpu = cpu_baseline(args.arch, Ksteps, args.rate) if args.full and world == 1 and not args.no_cpu_baseline else None   # (calibrates the host thread count)
+        if args.full and world == 1 and not args.no_other_configs:
             if args.contraction == "f32":
                 # the opt-in split-bf16 mode on the SAME workload, engines, batches in flight and z batches, timed right after
                 # (and outside) the headline's region: its own samples/s, dtype and roofline (never the headline)

@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,7 +44,7 @@ def run_bench(*extra, detail=None):
 def test_bench_line_small_config(tmp_path):
     """The compact line (contract keys + roofline + cpu_baseline + lib + one-number summary, < 6 kB: VERDICT r5 #1) and the full record
     in the sidecar it names."""
-    line, d = run_bench("--arch", "mnist", "--steps", "2", "--warmup", "1", "--refine-steps", "5", detail=tmp_path / "bench_detail.json")
+    line, d = run_bench("--full", "--arch", "mnist", "--steps", "2", "--warmup", "1", "--refine-steps", "5", detail=tmp_path / "bench_detail.json")
     for k in REQUIRED + ["lib", "summary", "detail"]:
         assert k in line, k
     for k in REQUIRED:
@@ -93,6 +94,27 @@ def test_bench_line_small_config(tmp_path):
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0 and c["sample"]
 
 
+@pytest.mark.parametrize("arch,outputs", [("mnist", {"images": (2048, 28, 28, 1), "default_logit": (2048,), "optimal_step": (2048,)}),
+                                          ("synthetic2d", {"best_x": (512, 2), "best_step": (512,)})], ids=["mnist", "synthetic2d"])
+def test_a_plain_run_times_its_steps_and_dumps_its_last_outputs(tmp_path, arch, outputs):
+    """Without --full the line is the headline alone (no profiled step, no baselines, no other configurations), --steps sets the timed
+    steps, and --dump-outputs writes the last timed step's outputs: float arrays, <= 64 MB, the same for the same arguments."""
+    dumps = []
+    for run in range(2):
+        dumps.append(tmp_path / f"out{run}")
+        d = run_bench("--arch", arch, "--steps", "3", "--warmup", "1", "--refine-steps", "3", "--dump-outputs", str(dumps[-1]))
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["roofline"] is None and "cpu_baseline" not in d and "summary" not in d and "executed_tflops" not in d
+    files = {p.name: p for p in dumps[0].iterdir()}
+    assert sum(p.stat().st_size for p in files.values()) <= 64 * 10**6 and {f"{n}.npy" for n in outputs} <= set(files)
+    for name, shape in outputs.items():
+        a, b = (np.load(dd / f"{name}.npy") for dd in dumps)
+        assert a.shape == shape and a.dtype in (np.float32, np.float64) and np.isfinite(a).all()
+        np.testing.assert_allclose(a, b, rtol=1e-4, atol=1e-4)
+
+
 def test_a_failed_graph_capture_falls_back_to_eager_launches_in_the_same_process():
     """The default is hipGraph replay at every world size; if the capture raises (here: a test hook refuses it) the run must go on
     with eager launches in the SAME process and say so in the line -- and with an explicit --graph the failure is an error."""
@@ -109,7 +131,7 @@ def test_a_failed_graph_capture_falls_back_to_eager_launches_in_the_same_process
 
 
 def test_bench_synthetic2d_line():
-    d = run_bench("--arch", "synthetic2d", "--steps", "3", "--warmup", "1")
+    d = run_bench("--full", "--arch", "synthetic2d", "--steps", "3", "--warmup", "1")
     for k in REQUIRED:
         assert k in d, k
     assert d["value"] > 0
@@ -148,7 +170,7 @@ def test_two_ranks_on_the_one_gpu_through_the_whole_multi_rank_path():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("MASTER_ADDR", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--arch", "mnist",
-                          "--steps", "4", "--warmup", "1", "--refine-steps", "3", "--no-cpu-baseline"], cwd=ROOT, capture_output=True,
+                          "--steps", "4", "--warmup", "1", "--refine-steps", "3", "--no-cpu-baseline", "--full"], cwd=ROOT, capture_output=True,
                          text=True, timeout=900, env=env)        # (5 batches over 4 engines: the LAST one runs on engine 0, the one the roofline's extra step re-uses)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -181,7 +203,7 @@ def test_two_ranks_on_the_one_gpu_with_the_drivers_own_workload(arch, contractio
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("MASTER_ADDR", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--arch", arch,
-                          "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--contraction", contraction], cwd=ROOT, capture_output=True, text=True,
+                          "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full", "--contraction", contraction], cwd=ROOT, capture_output=True, text=True,
                          timeout=1200, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -209,7 +231,7 @@ def test_eight_ranks_on_the_one_gpu(arch, extra, B, G, img):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("MASTER_ADDR", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--share-gpu", "--arch", arch,
-                          "--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + extra, cwd=ROOT, capture_output=True, text=True,
+                          "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"] + extra, cwd=ROOT, capture_output=True, text=True,
                          timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

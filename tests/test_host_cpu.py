@@ -544,6 +544,33 @@ def test_bench_final_line_stays_small_and_carries_the_contract(tmp_path, capsys)
     assert "detail" not in json.loads(cap.out.strip()) and "could not write" in cap.err
 
 
+def test_bench_dump_outputs_keeps_float_arrays_under_the_budget(tmp_path):
+    """``bench.py --dump-outputs``: one float32 / float64 .npy per output (integers exact in float64), at most ``DUMP_BUDGET`` bytes on
+    disk; a larger output keeps the same seeded rows of every array of its length, so that two builds' files compare row for row."""
+    import importlib
+    import sys
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    rs = np.random.RandomState(0)
+    small = {"images": torch.from_numpy(rs.randn(16, 4, 4, 3).astype(np.float32)), "optimal_step": torch.arange(16, dtype=torch.int32),
+             "logit": torch.from_numpy(rs.randn(16)).half()}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    for name, t in small.items():
+        a = np.load(tmp_path / "small" / f"{name}.npy")
+        assert a.dtype == (np.float64 if name == "optimal_step" else np.float32)
+        np.testing.assert_array_equal(a, t.double().numpy())
+    big = {"images": torch.from_numpy(rs.randn(1000, 64).astype(np.float32)), "best_step": torch.arange(1000, dtype=torch.float32),
+           "scale": torch.tensor(2.0, dtype=torch.float64)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big, budget=100_000)
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= 100_000
+    rows = np.load(tmp_path / "a" / "best_step.npy").astype(int)
+    assert 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "images.npy"), big["images"].numpy()[rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "best_step.npy"), rows)
+    assert np.load(tmp_path / "a" / "scale.npy") == 2.0
+
+
 def test_tf_checkpoint_converter_runs_against_the_checkpoint_reader_interface(tmp_path, monkeypatch):
     """tools/tf_ckpt_to_safetensors.py (reference saver: nsgan/GAN.py:465-491) has no TensorFlow to run against in
     this image.  Its own logic -- argument handling, reading every variable through the ``tf.train.load_checkpoint`` /

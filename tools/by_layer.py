@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the per-(kernel, layer) table of a `python bench.py --by-layer ...` JSON line: launches, avg us, issued TFLOP/s, share of the step.
+"""Print the per-(kernel, layer) table of a `python bench.py --full --by-layer ...` JSON line: launches, avg us, issued TFLOP/s, share of the step.
     python tools/by_layer.py gpurun_out/<log> [...]"""
 import json
 import sys
