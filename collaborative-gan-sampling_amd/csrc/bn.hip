@@ -6,8 +6,6 @@
 // Per-channel reductions are two-stage and deterministic (no float atomics): stage 1 writes one
 // (sum_a, sum_b) partial per block and channel, stage 2 adds the partials in a fixed order in
 // double and finishes the statistics.  Run-to-run results are bit-identical.
-#include <stdlib.h>
-
 #include "cgs_internal.h"
 
 #define BN_MAX_BLOCKS CGS_BN_MAX_BLOCKS
@@ -400,9 +398,6 @@ __global__ __launch_bounds__(256) void norm_small_kernel(const float* __restrict
 }
 #define NORM_SMALL_MAX_ROWS (16 * NS_ROWS)
 static bool norm_small_ok(int rows) {
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_NORM_SMALL") && atoi(getenv("CGS_NORM_SMALL")) == 0) return false;      // (A/B switch of experiment builds)
-#endif
     return rows <= NORM_SMALL_MAX_ROWS;
 }
 
@@ -506,18 +501,11 @@ __global__ __launch_bounds__(256) void norm_fa_kernel(const float* __restrict__ 
 // rows per block of norm_fa_kernel for a call, 0 = the two-launch form serves it (too many partial rows, or a tensor large enough that the
 // statistics' re-derivation per block and the plain row loop would cost more than the launch they save)
 static int norm_fa_rows_per_block(int groups, int rows_per_seg, int nseg, int M_group, int C) {
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_NORM_FA") && atoi(getenv("CGS_NORM_FA")) == 0) return 0;
-#endif
     // (limits from a same-process A/B over (rows, MB), profiles/r06_za_norm_fa_limits_ab.txt: every block re-derives the statistics, so the launch it saves
     // is only a gain while that is a handful of loads -- <= 16 rows, <= 2 MB: dcgan32 at batch 64 -2.2 % per call, neutral elsewhere; with <= 64 rows / 4 MB
     // -0.8 % there and +0.2 ... +0.4 % on dcgan64 at batch 64 and dcgan32 at batch 256)
-    long max_rows = 16;
-    size_t max_bytes = (size_t)2 << 20;
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_NORM_FA_ROWS")) max_rows = atol(getenv("CGS_NORM_FA_ROWS"));
-    if (getenv("CGS_NORM_FA_MB")) max_bytes = (size_t)atol(getenv("CGS_NORM_FA_MB")) << 20;
-#endif
+    const long max_rows = 16;
+    const size_t max_bytes = (size_t)2 << 20;
     if ((long)rows_per_seg * nseg > max_rows || (long)rows_per_seg * nseg > NFA_MAX_ROWS || groups > 65535) return 0;
     if ((size_t)groups * M_group * C * sizeof(float) > max_bytes) return 0;
     const long cg = cgs_ceil_div(C, 64);

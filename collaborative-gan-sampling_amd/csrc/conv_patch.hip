@@ -8,8 +8,6 @@
 // staged once in LDS, and every A fragment of v_mfma_f32_32x32x2_f32 is one ds_read_b32 at
 //   patch[(2*oy+ky)*pitch + (2*ox+kx)*Cin + ci] = rowbase(pixel) + koff(k),  koff(k) = (k / (kw*Cin))*pitch + k % (kw*Cin)
 // (for a fixed ky the (kx,ci) run is contiguous in NHWC).  Output through the same LDS-transposed 16-byte epilogue.
-#include <stdlib.h>
-
 #include "cgs_internal.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -458,13 +456,7 @@ __global__ __launch_bounds__(256, AUXM == 1 ? 2 : 4) void conv_patch2_kernel(Pat
         const unsigned obase_l = (unsigned)(nj + 4 * h * p.N) * 4u + (unsigned)(wm * 4) * rowstride;
         const int seg_n0 = n0;
         for (; t < t_end && n0 == seg_n0; ++t, ++it) {
-#ifdef CGS_PATCH_STAMPS
-            unsigned long long st0 = __builtin_amdgcn_s_memtime();
-#endif
             __syncthreads();                             // patch[it & 1] is in LDS; patch[(it+1) & 1] is free
-#ifdef CGS_PATCH_STAMPS
-            unsigned long long st1 = __builtin_amdgcn_s_memtime();
-#endif
             int nb_ = b, noy0 = oy0, nox0 = ox0, nn0 = n0;
             const bool more = t + 1 < t_end;
             if (more) {
@@ -502,9 +494,6 @@ __global__ __launch_bounds__(256, AUXM == 1 ? 2 : 4) void conv_patch2_kernel(Pat
                             aux_rsrc, ab + (unsigned)(2 * tm + lrow / TC) * rowstride + (unsigned)(lrow % TC) * (unsigned)p.N * 4u, 0, 0));
                     }
             }
-#ifdef CGS_PATCH_STAMPS
-            unsigned long long st2 = __builtin_amdgcn_s_memtime();
-#endif
             // the accumulators start at the bias: every plain VALU op of the epilogue costs matrix time on this SIMD (32 v_add per
             // tile were worth 16 % of the kernel), the MFMA adds onto whatever is there for free
             f32x16 acc[2];
@@ -530,15 +519,9 @@ __global__ __launch_bounds__(256, AUXM == 1 ? 2 : 4) void conv_patch2_kernel(Pat
                     acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bw[ky * HALF + sidx], acc[1], 0, 0, 0);
                 }
             }
-#ifdef CGS_PATCH_STAMPS
-            unsigned long long st3 = __builtin_amdgcn_s_memtime();
-#endif
             // the next patch goes to LDS BEFORE this tile's output stores are issued: its wait (vmcnt counts loads and stores in
             // issue order) then covers only the patch loads and the previous tile's stores, both a whole MFMA phase old
             if (more) STORE_PATCH((it + 1) & 1);
-#ifdef CGS_PATCH_STAMPS
-            unsigned long long st4 = __builtin_amdgcn_s_memtime();
-#endif
             // epilogue straight from the accumulator registers: lane (h, j) holds channel j of 16 rows per row tile, so one
             // buffer_store_dword writes two whole 128-byte channel runs (rows R and R + 4).  No LDS round trip, and every
             // address is one of two per-lane bases (tile row 0 / 1 of the row tile) plus an instruction immediate.
@@ -600,12 +583,6 @@ __global__ __launch_bounds__(256, AUXM == 1 ? 2 : 4) void conv_patch2_kernel(Pat
                     default: patch2_store<CGS_EPI_TANH_BWD>(p, out_rsrc, aux_rsrc, acc, obase_l + tile_off, rowstride, ea1, eb1); break;
                 }
             }
-#ifdef CGS_PATCH_STAMPS
-            if (p.ep_b && lane == 0 && blockIdx.x < 64 && it < 16) {
-                unsigned long long* dbg = (unsigned long long*)p.ep_b + (((size_t)blockIdx.x * 4 + wave) * 16 + it) * 8;
-                dbg[0] = st0; dbg[1] = st1; dbg[2] = st2; dbg[3] = st3; dbg[4] = st4; dbg[5] = __builtin_amdgcn_s_memtime();
-            }
-#endif
             b = nb_; oy0 = noy0; ox0 = nox0; n0 = nn0;
         }
     }
@@ -616,9 +593,6 @@ __global__ __launch_bounds__(256, AUXM == 1 ? 2 : 4) void conv_patch2_kernel(Pat
 
 // which (KH, RP) instantiation of conv_patch2_kernel serves a layer (0 = none: the general kernel above)
 static int patch2_rp(const CgsLayer& L, bool dirT) {
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_PATCH_V1")) return 0;
-#endif
     if (dirT || L.sh != 2 || L.sw != 2) return 0;
     if (((L.sw * L.Cb) & 1) != 0) return 0;                 // 8-byte aligned pixel starts
     // the instantiated shape: 5 tap rows of 5 x 3 floats, a 19 x 35 x 3 patch (8 floats per thread)

@@ -15,8 +15,6 @@
 // needed); the packed weights (37 KB for 9 x 64 x 16) sit in LDS for the whole block.
 #include <stdio.h>
 
-#include <stdlib.h>
-
 #include "cgs_internal.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -640,11 +638,7 @@ int cgs_convt_quad_launch(const CgsLayer& L, int B, const float* in, const float
     if ((long)B * L.Hs * L.Ws * L.Cs * 4 > 0x7fffffffL) return cgs_set_error(CGS_EINVAL, "convt_quad: input exceeds 2 GiB (split the batch)");
     // the taps kernel reads the raw weights and the input as float4: a view at an unaligned offset keeps the packed rows / quad forms below
     const bool taps_aligned = !(((uintptr_t)w | (uintptr_t)in) & 15);
-#ifdef CGS_EXPERIMENT
-    if (cgs_convt_taps_ok(L) && taps_aligned && !getenv("CGS_NO_TAPS")) return cgs_convt_taps_launch(L, B, in, w, bias, out, epilogue, ep_a, ep_aux, s);
-#else
     if (cgs_convt_taps_ok(L) && taps_aligned) return cgs_convt_taps_launch(L, B, in, w, bias, out, epilogue, ep_a, ep_aux, s);      // (reads the unpacked weights)
-#endif
     if (const int mt = rows_mt(L)) {
         RowsParams r;
         r.in = in; r.wp = ws; r.bias = bias; r.out = out; r.ep_a = ep_a; r.ep_aux = ep_aux;
@@ -660,10 +654,7 @@ int cgs_convt_quad_launch(const CgsLayer& L, int B, const float* in, const float
         // output row pairs per task: the forward 5x5 64 -> 3 layers run the tall form (with an aux epilogue its 64 accumulators + the
         // aux values do not fit 128 VGPRs: 35 spilled registers)
         const bool tall_ok = s5 && L.Cb == 3 && L.Hs >= 8 && epilogue < CGS_EPI_RELU_BWD_AFFINE;
-        int np = tall_ok ? 4 : 2;
-#ifdef CGS_EXPERIMENT
-        if (getenv("CGS_ROWS_NP")) np = atoi(getenv("CGS_ROWS_NP")) == 4 && tall_ok ? 4 : 2;
-#endif
+        const int np = tall_ok ? 4 : 2;
         const long tasks = (long)B * ((L.Hs + np - 1) / np);
         if (tasks == 0) return CGS_OK;
         // persistent blocks of 8 independent waves, two per CU; a block's waves walk neighbouring row pairs of a contiguous run

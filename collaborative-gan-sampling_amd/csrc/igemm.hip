@@ -24,7 +24,6 @@
 // conflict-free).
 #include <stdarg.h>
 #include <stdio.h>
-#include <stdlib.h>
 
 #include "cgs_internal.h"
 #include "igemm_epilogue.h"
@@ -227,11 +226,6 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p) {
     // resident block in its K loop).  Prologue and epilogue therefore run at priority 3 and the K loop below them: the short
     // phases finish at once and cost the matrix stream a few cycles per instruction.
     __builtin_amdgcn_s_setprio(3);
-#ifdef CGS_DIAG_STAMPS      // diagnostic build only (tools/clock_probe.py): per-block timeline stamps into the workspace tail
-    const bool stamp = p.slab != nullptr && p.splitk == 1 && tid == 0;
-    unsigned long long sr_in = 0;
-    if (stamp) sr_in = __builtin_amdgcn_s_memrealtime();
-#endif
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave - wm * WN;
     const int h = lane >> 5, j = lane & 31;
@@ -387,10 +381,6 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
 
-#ifdef CGS_DIAG_STAMPS
-    unsigned long long sr_loop0 = 0;
-    if (stamp) sr_loop0 = __builtin_amdgcn_s_memrealtime();
-#endif
     // ------------------------------------------------------------------------------------------------------------------
     // K loop.  Per-tile vector-ALU work is kept to a minimum: VALU instructions and MFMAs of a SIMD share its vector issue, and
     // every VALU op in the loop costs matrix time even from another wave (tools/probe/mfma_probe.hip: 32 MFMAs + 8 ds_read_b128
@@ -557,9 +547,6 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p) {
             }                                                                                                   \
     } while (0)
     constexpr int NG = BK / 8;                       // MFMA groups per tile
-#ifdef CGS_DIAG_STAMPS
-    int diag_tiles = 0;
-#endif
     // Fair progress among the blocks of a CU: the hardware arbitrates MFMA issue by priority, then AGE, so of the (equally old
     // or not) resident blocks the oldest runs ahead and finishes first, and the launch ends with one block per CU that
     // has most of its work left and nobody to hide its latencies.  Every block therefore starts at priority 3 and steps down as
@@ -626,7 +613,6 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p) {
             ADDR_(ld);                                                                                          \
         }                                                                                                       \
         for (int buf = 0; cur.kt < nk; buf ^= 1) {                                                              \
-            DIAG_TILES32;                                                                                       \
             ISSUE_(ld);                                                                                         \
             _Pragma("unroll") for (int jj = 0; jj + 1 < NG; jj += 2) {     /* NG is even: fragments ping-pong between two register sets */ \
                 FRAG_READ(buf, jj + 1, fa1, fb1);                                                               \
@@ -655,15 +641,9 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p) {
             __builtin_amdgcn_sched_barrier(0);                                                                  \
         }                                                                                                       \
     }
-#ifdef CGS_DIAG_STAMPS
-#define DIAG_TILES32 ++diag_tiles
-#else
-#define DIAG_TILES32
-#endif
         if (uni) K_LOOP32(ADDR_TILE_U, ISSUE_TILE_U)
         else K_LOOP32(ADDR_TILE_V, ISSUE_TILE_V)
 #undef K_LOOP32
-#undef DIAG_TILES32
     } else if constexpr (VEC) {
         // Two copies of the body, one per LDS buffer: the buffer offsets are then instruction immediates instead of a VALU add
         // per address and tile.  The pair loop has ONE exit (at its top, on a two-tile look-ahead), an odd last tile runs in a
@@ -684,11 +664,6 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p) {
         __syncthreads();                                                                                        \
         cur = NXT_;                                                                                             \
     }
-#ifdef CGS_DIAG_STAMPS
-#define DIAG_TILES(n_) diag_tiles += (n_)
-#else
-#define DIAG_TILES(n_)
-#endif
 #define K_LOOP16(ADDR_, ISSUE_)                                                                                 \
     {                                                                                                           \
         KIt n1 = cur;                                                                                           \
@@ -697,26 +672,20 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p) {
             const KIt n2 = kit_next(n1);                                                                        \
             KIt n3 = n2;                                                                                        \
             if (n2.kt < nk) n3 = kit_next(n2);                                                                  \
-            DIAG_TILES(2);                                                                                      \
             TILE_BODY(0, n1, ADDR_, ISSUE_);                                                                    \
             TILE_BODY(1, n2, ADDR_, ISSUE_);                                                                    \
             n1 = n3;                                                                                            \
         }                                                                                                       \
         if (cur.kt < nk) {                               /* an odd last tile */                                 \
-            DIAG_TILES(1);                                                                                      \
             TILE_BODY(0, n1, ADDR_, ISSUE_);                                                                    \
         }                                                                                                       \
     }
         if (uni) K_LOOP16(ADDR_TILE_U, ISSUE_TILE_U)
         else K_LOOP16(ADDR_TILE_V, ISSUE_TILE_V)
 #undef K_LOOP16
-#undef DIAG_TILES
 #undef TILE_BODY
     } else {
         for (int buf = 0; kt < nk; buf ^= 1) {
-#ifdef CGS_DIAG_STAMPS
-            ++diag_tiles;
-#endif
             const int kn = next_chunk(kt + 1);
             const int kl = kn < nk ? kn : kt;            // tile to prefetch (the current one again after the last)
             const float* a = As + buf * BM * LDA + (wm * (BM / WM) + j) * LDA;
@@ -741,10 +710,6 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p) {
 #undef PRIO_STEP
 #undef MFMA_GROUP
 
-#ifdef CGS_DIAG_STAMPS
-    unsigned long long sr_loop1 = 0;
-    if (stamp) sr_loop1 = __builtin_amdgcn_s_memrealtime();
-#endif
 #undef LOAD_TILE
 #undef STORE_TILE
 #undef DECODE_ROW
@@ -862,16 +827,6 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p) {
                 *(f32x4*)(dst + p.N) = st_b;
             }
         }
-#ifdef CGS_DIAG_STAMPS
-        if (stamp) {
-            unsigned long long* dbg = (unsigned long long*)p.slab + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8;
-            dbg[0] = sr_in; dbg[1] = sr_loop0; dbg[2] = sr_loop1; dbg[3] = __builtin_amdgcn_s_memrealtime();
-            dbg[4] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |                 // HW_ID: wave / simd / cu / sh / se
-                     ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);        // XCC_ID
-            dbg[5] = (unsigned long long)diag_tiles;
-            dbg[6] = (unsigned long long)mb | ((unsigned long long)nb << 32);
-        }
-#endif
         return;
     }
 #pragma unroll     // (must stay fully unrolled: a run-time tn would index the accumulator array and push it to scratch)
@@ -1074,22 +1029,10 @@ static int choose_splitk(const IgemmParams& p) {
         if (p.cls[i].R * p.cls[i].C > 0 && nk < nk_min) nk_min = nk;
     }
     // (splitting grids of 256-1023 blocks as well was measured on dcgan32, B = 256: -10 % with two batches in flight)
-    long target = 512, maxb = 256;
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_SPLITK_TARGET")) target = atol(getenv("CGS_SPLITK_TARGET"));
-    if (getenv("CGS_SPLITK_MAXBLOCKS")) maxb = atol(getenv("CGS_SPLITK_MAXBLOCKS"));
-#endif
-    if (blocks == 0 || blocks >= maxb || nk_min < 8) return 1;
+    if (blocks == 0 || blocks >= 256 || nk_min < 8) return 1;
     long cap = nk_min / 4;                       // at least four 32-deep K tiles per slice (in the class with the shortest K)
     if (cap > 64) cap = 64;
     if (cap < 2) return 1;
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_SPLITK_MODEL") && atoi(getenv("CGS_SPLITK_MODEL")) == 0) {          // (A/B: the rule before round 5: aim at ``target`` blocks)
-        long s = (target + blocks - 1) / blocks;
-        if (s > cap) s = cap;
-        return s < 2 ? 1 : (int)s;
-    }
-#endif
     // The factor with the least modelled time (round 5; calibrated on the batch-64 launches of dcgan32 / dcgan64 / mnist, tools/sessions/r05_q.sh:
     // these launches are matrix-bound per block, every block on its own SIMDs).  In units of one 128x128x32 tile on an otherwise idle CU:
     //   K loop  = (K tiles per slice) x (blocks on the fullest CU), x 1.41 if that is ONE block (nobody hides its load -> LDS -> MFMA latencies:
@@ -1118,7 +1061,6 @@ static int choose_splitk(const IgemmParams& p) {
         const double cost = (load == 1 ? 1.41 : (double)load) * (double)cps * tile + 0.3 * slice_mb * (double)s;
         if (cost < best_cost) { best_cost = cost; best = (int)s; }
     }
-    (void)target;
     return best;
 }
 
@@ -1163,9 +1105,6 @@ static IgemmTiles igemm_choose_tiles(const IgemmParams& p, bool tail_wide = true
             wide = true;
             wide_for_tail = true;
         }
-#ifdef CGS_EXPERIMENT
-        if (getenv("CGS_FORCE_WIDE")) wide = atoi(getenv("CGS_FORCE_WIDE")) != 0;      // (A/B: 0 = the narrow tiles, 1 = the wide ones, whatever the rules above said)
-#endif
     }
     // K tile: 32 when every tile lies inside one tap (VEC); 16 for the generic-K gather (small K: less padding waste)
     // (8-wave 128x128 blocks, 4 waves per SIMD: +1.3 % with one batch in flight, +-0 with two -- not kept)
@@ -1185,9 +1124,7 @@ static IgemmTiles igemm_choose_tiles(const IgemmParams& p, bool tail_wide = true
         // a launch that leaves a sign mask (one-pass epilogue only), or statistics when the workspace has no room for the split-K slabs
         // (with room it is split: splitk_reduce_stats_kernel): under 256 blocks of 128x128 it would leave most CUs idle (config 5's
         // PatchGAN 4x4 128->256 layer: 128 blocks, 54 TFLOP/s) -- as 128x64 blocks at least every CU gets one
-#ifndef CGS_NO_STAT_NARROW
         else if (wb < 256 && (p.stat_part || p.sign_out)) { wide = false; mid = true; }
-#endif
     }
     bool deep = true;
     if (vec && p.splitk == 1 && !mid) {
@@ -1202,10 +1139,6 @@ static IgemmTiles igemm_choose_tiles(const IgemmParams& p, bool tail_wide = true
         // the pixel-major 8x8 256<-512 layer of dcgan64 (1024 very uneven blocks) stays 32-deep: 0.61 vs 0.74 ms
         if (deep && !p.pix_major && p.nclasses > 1 && tot_blocks >= 1024) deep = false;
     }
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_FORCE_DEEP")) deep = atoi(getenv("CGS_FORCE_DEEP")) != 0;
-    if (getenv("CGS_FORCE_NARROW")) wide = false;
-#endif
     // Tall tiles, 256 x 64 (four 64 x 64 wave tiles stacked: the per-wave shape of the 128 x 128 block), for launches to 64 output channels
     // whose K loops are SHORT (<= 512 per class: 32 tiles of 16) and whose grid is many rounds of blocks: half the blocks, so half the
     // prologues / epilogues per output, and every A fragment meets two B fragments.  Measured per stage (round 5, A/B interleaved in one
@@ -1219,12 +1152,6 @@ static IgemmTiles igemm_choose_tiles(const IgemmParams& p, bool tail_wide = true
         // (pixel-major launches only: config 5's image-major 128x128 128->64 transposed layer, K = 512, measured 166.8 -> 168.8 us)
         tall = vec && !wide && !mid && !deep && p.splitk == 1 && p.Np == 64 && p.pix_major && (p.B % 256) == 0 && kmax <= 512 &&
                igemm_blocks(p, 64, 256) >= 1536;
-#ifdef CGS_EXPERIMENT
-        if (getenv("CGS_TALL")) {        // 0: never; 1: wherever the tile can run (from CGS_TALL_MIN blocks on: parity runs force it onto small launches)
-            tall = atoi(getenv("CGS_TALL")) != 0 && vec && !wide && !mid && !deep && p.splitk == 1 && p.Np == 64 && (!p.pix_major || (p.B % 256) == 0) &&
-                   igemm_blocks(p, 64, 256) >= (getenv("CGS_TALL_MIN") ? atol(getenv("CGS_TALL_MIN")) : 1536);
-        }
-#endif
     }
     return IgemmTiles{wide, mid, deep, tall, wide_for_tail && wide};
 }
@@ -1241,15 +1168,11 @@ static int igemm_blocks_per_cu(bool wide, bool deep) { return deep ? (wide ? 2 :
 // 253.4 -> 209.1 us (0.66 -> 0.80 of peak).
 // Launches of SEVERAL rounds (T = q * L + r on L = 256 * blocks-per-CU slots, the short last round cut the same way) were measured too and
 // are NOT split: +2 % / +-0 / +4.5 % on three of them, -3.4 % and -1.3 % on two (dcgan32 16x16 64<-128, dcgan64 32x32 64<-128: their
-// last round already overlaps the tail of the one before, and the slices pay a prologue, a raw 32 KB store and the reduce pass each);
-// experiment builds keep that plan behind CGS_TAIL_MULTI=1.
+// last round already overlaps the tail of the one before, and the slices pay a prologue, a raw 32 KB store and the reduce pass each).
 static IgemmTail igemm_choose_tail(const IgemmParams& p, const IgemmTiles& t) {
     IgemmTail none{0, 0, 0};
     if (!igemm_round_rules_apply()) return none;
     if (!p.vec || p.splitk > 1 || p.stat_part || p.sign_out || (p.N & 3) || t.tall) return none;
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_TAIL") && atoi(getenv("CGS_TAIL")) == 0) return none;
-#endif
     const int bn = t.wide ? 128 : 64, tbk = t.deep ? 32 : 16;
     const IgemmClass& cl = p.cls[p.nclasses - 1];
     const long Ml = (long)p.B * cl.R * cl.C;
@@ -1258,28 +1181,13 @@ static IgemmTail igemm_choose_tail(const IgemmParams& p, const IgemmTiles& t) {
     const long T = igemm_blocks(p, bn);
     const long L = 256L * igemm_blocks_per_cu(t.wide, t.deep);
     const int nk = cgs_ceil_div(cl.K, tbk);
-    long r; int S;
     if (T < 256) return none;                                            // (under-filled grids are split over K as a whole)
-    if (T <= L) {
-        r = T % 256;
-        if (r == 0 || r > 176) return none;                              // (a remainder above ~2/3 of the CUs: the last tile time is mostly used)
-        S = (int)((256 + r / 2) / r);
-        if (S > 16) S = 16;
-    } else {
-#ifdef CGS_EXPERIMENT
-        if (!getenv("CGS_TAIL_MULTI") || atoi(getenv("CGS_TAIL_MULTI")) == 0) return none;
-        r = T % L;
-        if (r == 0 || r * 5 > L * 4) return none;
-        S = (int)((L + r / 2) / r);
-        if (S > 8) S = 8;
-#else
-        return none;
-#endif
-    }
+    if (T > L) return none;                                              // (several rounds: not split, above)
+    long r = T % 256;
+    if (r == 0 || r > 176) return none;                                  // (a remainder above ~2/3 of the CUs: the last tile time is mostly used)
+    int S = (int)((256 + r / 2) / r);
+    if (S > 16) S = 16;
     if (S > nk / 4) S = nk / 4;                                          // at least 4 K tiles per slice
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_TAIL_S")) S = atoi(getenv("CGS_TAIL_S"));
-#endif
     if (S < 2) return none;
     if (r > Tl) r = Tl;
     for (int i = 0; i < p.nclasses; ++i)                                 // (one id space for all classes: equal sizes only)
@@ -1361,16 +1269,6 @@ static int launch_cfg(const IgemmParams& p, hipStream_t s) {
             else if (p.splitk == 1 && per_round < p.nclasses && (p.nclasses % per_round) == 0) q.cls_flip = (int)per_round;      // several rounds per slice
         }
     }
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_CLS_FLIP") && atoi(getenv("CGS_CLS_FLIP")) == 0) q.cls_flip = 0;
-    if (getenv("CGS_CLS_FLIP") && atoi(getenv("CGS_CLS_FLIP")) == 2 && p.splitk == 1) q.cls_flip = 0;      // (2 = split launches only, as first adopted)
-    if (getenv("CGS_CLS_INTER") && atoi(getenv("CGS_CLS_INTER")) && q.xcd_map == 1 && (mtiles % 8) == 0 && p.nclasses > 1 && p.tail_s <= 1 && p.splitk == 1 && !p.pix_major &&
-        gx >= atol(getenv("CGS_CLS_INTER"))) {
-        bool eq = true;
-        for (int i = 1; i < p.nclasses; ++i) eq = eq && p.cls[i].R * p.cls[i].C == p.cls[0].R * p.cls[0].C;
-        if (eq) { q.xcd_map = 2; gx *= p.nclasses; gy = 1; }
-    }
-#endif
     if (gx > 0x7fffffffL) return cgs_set_error(CGS_EINVAL, "igemm: grid too large");
     hipLaunchKernelGGL(kern, dim3((unsigned)gx, gy, p.splitk > 1 ? p.splitk : 1), dim3(64 * NW), smem, s, q);
     CGS_CHECK_LAUNCH("igemm");
@@ -1402,13 +1300,7 @@ static bool igemm_pix_major(const IgemmParams& p) {
     int maxRC = 0;
     for (int i = 0; i < p.nclasses; ++i) maxRC = p.cls[i].R * p.cls[i].C > maxRC ? p.cls[i].R * p.cls[i].C : maxRC;
     const size_t in_bytes = (size_t)p.B * p.Hin * p.Win * p.Cred * 4;
-    int pix_max = 256;
-    size_t pix_bytes = (size_t)384 << 20;
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_PIXMAX")) pix_max = atoi(getenv("CGS_PIXMAX"));
-    if (getenv("CGS_PIXBYTES")) pix_bytes = (size_t)atoi(getenv("CGS_PIXBYTES")) << 20;
-#endif
-    return p.vec && p.B >= 128 && maxRC <= pix_max && maxRC > 1 && in_bytes <= pix_bytes;
+    return p.vec && p.B >= 128 && maxRC <= 256 && maxRC > 1 && in_bytes <= ((size_t)384 << 20);
 }
 
 // GEMM row order of a launch and, for whole-tile pixel-major launches, the heaviest-first pixel order (BM = rows of a block tile)
@@ -1470,10 +1362,6 @@ int cgs_igemm_launch(const IgemmParams& p_in, void* slab, size_t slab_bytes, hip
     p.splitk = 1; p.slab = nullptr;
     p.tail_from = p.tail_n = p.tail_s = 0;
     p.prio_t[0] = p.prio_t[1] = p.prio_t[2] = 0;
-#ifdef CGS_DIAG_STAMPS
-    // (the stamps go to the LAST MiB of the caller's workspace: 16384 blocks x 64 bytes; tools/clock_probe.py sizes it so)
-    if (getenv("CGS_STAMP") && slab && slab_bytes >= (1u << 20)) p.slab = (float*)((char*)slab + slab_bytes - (1u << 20) - ((uintptr_t)((char*)slab + slab_bytes) & 15));
-#endif
     int maxRC = 0;
     for (int i = 0; i < p.nclasses; ++i) maxRC = p.cls[i].R * p.cls[i].C > maxRC ? p.cls[i].R * p.cls[i].C : maxRC;
     cgs_igemm_row_policy(p, 128);
@@ -1494,12 +1382,7 @@ int cgs_igemm_launch(const IgemmParams& p_in, void* slab, size_t slab_bytes, hip
         return cgs_set_error(CGS_EINVAL, "igemm: a sign mask needs N %% 32 == 0, the relu / lrelu forward epilogues and a grid that is not split over K");
     {   // split-K for under-filled grids, if the caller's workspace has room for the partial slabs
         const size_t need = p.sign_out ? 0 : cgs_igemm_splitk_bytes(p);      // (a sign mask comes out of the one-pass epilogue; statistics: splitk_reduce_stats_kernel)
-#ifdef CGS_EXPERIMENT
-        const bool stat_split = !(p.stat_part && getenv("CGS_STAT_SPLIT") && atoi(getenv("CGS_STAT_SPLIT")) == 0);      // (A/B: 0 = statistics launches unsplit, as before round 5)
-#else
-        const bool stat_split = true;
-#endif
-        if (need && stat_split && slab && slab_bytes >= need) {
+        if (need && slab && slab_bytes >= need) {
             p.splitk = choose_splitk(p); p.slab = (float*)slab;
             size_t off = 0;
             for (int i = 0; i < p.nclasses; ++i) {
@@ -1525,18 +1408,10 @@ int cgs_igemm_launch(const IgemmParams& p_in, void* slab, size_t slab_bytes, hip
         p.tail_from = tl.from; p.tail_n = tl.n; p.tail_s = tl.s; p.slab = (float*)slab;
         cgs_note_tail(tl.n, tl.s);
     }
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_PLAN_PRINT")) {
-        const long T_ = igemm_blocks(p, wide ? 128 : 64), L_ = 256L * igemm_blocks_per_cu(wide, deep);
-        fprintf(stderr, "[igemm plan] B=%d in %dx%dx%d -> out %dx%dx%d classes %d K0=%d: tile 128x%dx%d, T=%ld L=%ld (T%%256=%ld, T%%L=%ld) splitk=%d stats=%d signs=%d pix_major=%d lpt=%d tail=%dx%d\n",
-                p.B, p.Hin, p.Win, p.Cred, p.Hout, p.Wout, p.N, p.nclasses, p.cls[0].K, wide ? 128 : 64, deep ? 32 : 16, T_, L_, T_ % 256, T_ % L_, p.splitk,
-                p.stat_part != nullptr, p.sign_out != nullptr, p.pix_major, p.lpt, p.tail_n, p.tail_s);
-    }
-#endif
     {
         // Launches whose blocks are all resident at once (one "round": <= 4 blocks per CU with the 16-deep tiles, 2 with the
-        // 32-deep ones) end when their slowest CU ends.  Two things even that out (measured per layer with in-kernel stamps,
-        // tools/clock_probe.py: CU finish times 633-761 us before, span 761 -> 700 us for the 16x16 128->256 layer):
+        // 32-deep ones) end when their slowest CU ends.  Two things even that out (measured per layer with in-kernel stamps:
+        // CU finish times 633-761 us before, span 761 -> 700 us for the 16x16 128->256 layer):
         //  (a) fair progress of the blocks sharing a CU (priority steps, see the kernel);
         //  (b) the pixel-major tiles have 9..25 valid taps each and the dispatcher hands workgroups to the 32 CUs of an XCD
         //      round-robin, so the heaviest-first order alone gives the first CUs several 25-tap tiles; instead the tiles are
@@ -1577,20 +1452,10 @@ int cgs_igemm_launch(const IgemmParams& p_in, void* slab, size_t slab_bytes, hip
         }
     }
     p.uni = !(p.nclasses > 1 && wide && maxRC <= 64);
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_UNI")) p.uni = atoi(getenv("CGS_UNI")) == 2 ? p.uni : atoi(getenv("CGS_UNI"));
-#endif
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_PRIO")) sscanf(getenv("CGS_PRIO"), "%d,%d,%d", &p.prio_t[0], &p.prio_t[1], &p.prio_t[2]);
-    if (getenv("CGS_NOBALANCE")) { /* diagnostic: handled by CGS_PRIO=0,0,0 for (a); (b) has no switch */ }
-#endif
     // Launches of at most 64 GEMM rows that are split over K (the fully connected layers at the reference's batch size, nsgan/main.py:32: 64 x 6272 x 1024):
     // 64-row tiles -- a 128-row tile is half padding there and the blocks are matrix-bound (4-8 K tiles each on their own SIMDs).  Same-process
     // A/B (round 5, profiles/r05_t_bm64_ab.txt): mnist's 6272->1024 forward 34.6 -> 25.9 us, backward 32.5 -> 24.0 us, the batch-64 call 12.14 -> 11.38 ms.
     bool half = vec && wide && deep && p.splitk > 1 && !p.tap_parity && (long)p.B * maxRC <= 64;
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_BM64")) half = half && atoi(getenv("CGS_BM64")) != 0;
-#endif
     // (a launch that leaves the norm-backward sums runs the igemm_ns_kernel twin of its tile; every other launch the kernel of the rounds before)
     const bool ns = p.stat_part && p.ns_mean;
 #define LC(...) (ns ? launch_cfg<__VA_ARGS__, true>(p, s) : launch_cfg<__VA_ARGS__, false>(p, s))

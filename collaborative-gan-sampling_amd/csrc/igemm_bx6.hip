@@ -18,14 +18,12 @@
 // store (5.5 vector-ALU operations per element, once per block and K stage).  LDS rows are 32 bytes (one 16-deep K stage of
 // one plane), so a fragment read of the 32 x 32 x 16 MFMA is a linear 1 KB per wave.
 #include <stdio.h>
-#include <stdlib.h>
 
 #include "cgs_internal.h"
 #include "igemm_epilogue.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 // two floats -> their three bf16 pieces, packed pairwise (low half = x0's piece): hi, mid, lo
@@ -105,16 +103,12 @@ int cgs_pack_weights_bx6(const IgemmParams& p, const CgsLayer& L, bool dirT, con
 // ------------------------------------------------------------------------------------------------
 // main kernel
 // ------------------------------------------------------------------------------------------------
-#ifndef BX6_V
-#define BX6_V 1          // bit 0: the weight tile goes global -> LDS directly (buffer_load ... lds), no register staging
-#endif
-// waves per SIMD the register budget is sized for: the four-wave blocks run two per CU (256 registers per lane); the two-wave
-// 256 x 64 block's LDS lets two blocks = four waves share a CU, one per SIMD (512 registers: its eight staged float4 fit)
+// The register budget is sized for two waves per SIMD (256 registers per lane): the four-wave blocks run two per CU.
 // The one-wave 128 x 64 block ("solo", for layers with 64 output channels per tile): no other wave shares its tile, so it keeps ONE LDS
 // image (the fragments of a stage are all in registers before the image is overwritten), 18.5 KB: eight blocks = two waves per SIMD
 // per CU, no barriers, no lockstep between them.
 template <int BM, int BN, bool PAR>
-__global__ __launch_bounds__(BM* BN / 128, BM* BN == 128 * 256 || BM * BN == 128 * 64 ? 2 : 1) void igemm_bx6_kernel(IgemmParams p) {
+__global__ __launch_bounds__(BM* BN / 128, 2) void igemm_bx6_kernel(IgemmParams p) {
     constexpr int WNN = BN / 64;                       // waves along N; wave tile 128 x 64
     constexpr int NW = (BM / 128) * WNN, NT = 64 * NW;
     constexpr bool SOLO = NW == 1;
@@ -123,7 +117,6 @@ __global__ __launch_bounds__(BM* BN / 128, BM* BN == 128 * 256 || BM * BN == 128
     constexpr int PLA = BM * PITCH, PLB = BN * PITCH;  // bytes of an A / B plane
     constexpr int BUF = 3 * (PLA + PLB);               // one stage: A planes [3][BM][16], then B planes [3][BN][16]
     constexpr int AI = BM * 4 / NT, AR = NT / 4;       // float4 of A per thread and stage; rows per staging pass
-    [[maybe_unused]] constexpr int NB = BN * 6 / NT;   // 16-byte pieces of B per thread and stage when staged through registers (3 planes x BN columns x 2 halves)
     constexpr int ER = 32, LDE = 64 + 4;               // epilogue staging: 32 rows of the wave tile at a time
     constexpr int STAGE_B = NW * ER * LDE * 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -269,7 +262,6 @@ __global__ __launch_bounds__(BM* BN / 128, BM* BN == 128 * 256 || BM * BN == 128
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)((const unsigned short*)p.wp + (size_t)c.w_off * 3), 0, 0x7ffffff0, 0x00020000);
     const int b_tile_bytes = 3 * p.Np * PITCH;
-#if BX6_V & 1
     // LDS-DMA: a wave-instruction copies 1 KB = 32 columns of one plane (lane l -> bytes [16 l, 16 l + 16) of the piece, in global
     // memory and in LDS alike: the packed tile and its LDS image are the same linear array); piece = wave + NW * u
     constexpr int PPP = BN / 32;                       // pieces per plane
@@ -281,17 +273,6 @@ __global__ __launch_bounds__(BM* BN / 128, BM* BN == 128 * 256 || BM * BN == 128
         const int piece = wave + NW * u, plane = piece / PPP, sub = piece - plane * PPP;
         b_soff[u] = __builtin_amdgcn_readfirstlane(plane * p.Np * PITCH + n0 * PITCH + sub * 1024);
     }
-#else
-    unsigned b_voff[NB], b_lds[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        const int idx = tid + NT * u;
-        const int plane = idx / (BN * 2), rem = idx - plane * (BN * 2);
-        b_voff[u] = (unsigned)(plane * p.Np * PITCH + n0 * PITCH + rem * 16);
-        b_lds[u] = (unsigned)(3 * PLA + plane * PLB + rem * 16);
-    }
-    u32x4 rb[NB];
-#endif
     unsigned a_off[AI];
     f32x4 ra[AI];
 #define ADDR_TILE(s_)                                                                                           \
@@ -303,7 +284,6 @@ __global__ __launch_bounds__(BM* BN / 128, BM* BN == 128 * 256 || BM * BN == 128
         _Pragma("unroll") for (int i = 0; i < AI; ++i)                                                          \
             a_off[i] = (tapmask[i] & need_) == need_ ? rowoff[i] + soff_ : 0xFFFFFFF0u;                         \
     } while (0)
-#if BX6_V & 1
     // (the weight tile of stage s_ goes straight into LDS buffer DST_: free since the barrier that ended the stage before, complete
     // before the one that ends this stage -- the barrier's fence waits for the DMA)
 #define ISSUE_A(RA_)                                                                                            \
@@ -322,22 +302,6 @@ __global__ __launch_bounds__(BM* BN / 128, BM* BN == 128 * 256 || BM * BN == 128
             bx6_dma16(w_rsrc, lds + (DST_) * BUF + 3 * PLA + plane_ * PLB + sub_ * 1024, b_lane, b_soff_ + b_soff[u]); \
         }                                                                                                       \
     } while (0)
-#else
-#define ISSUE_A(RA_)                                                                                            \
-    _Pragma("unroll") for (int i = 0; i < AI; ++i)                                                              \
-        RA_[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, a_off[i], 0, 0));
-#define ISSUE_B(s_, DST_)                                                                                       \
-    do {                                                                                                        \
-        const int b_soff_ = (s_).kt * b_tile_bytes;                                                             \
-        _Pragma("unroll") for (int u = 0; u < NB; ++u)                                                          \
-            rb[u] = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_voff[u], b_soff_, 0);                       \
-    } while (0)
-#define ISSUE_TILE(s_, DST_)                                                                                    \
-    do {                                                                                                        \
-        ISSUE_A(ra);                                                                                            \
-        ISSUE_B(s_, DST_);                                                                                      \
-    } while (0)
-#endif
     const unsigned a_lds = (unsigned)(ar * PITCH + aq * 8);
 #define STORE_TILE(BUF_) STORE_TILE_R(BUF_, ra)
 #define STORE_TILE_R(BUF_, RA_)                                                                                 \
@@ -354,11 +318,7 @@ __global__ __launch_bounds__(BM* BN / 128, BM* BN == 128 * 256 || BM * BN == 128
         }                                                                                                       \
         STORE_B(base_);                                                                                         \
     } while (0)
-#if BX6_V & 1
 #define STORE_B(base_)
-#else
-#define STORE_B(base_) _Pragma("unroll") for (int u = 0; u < NB; ++u) *(u32x4*)((base_) + b_lds[u]) = rb[u];
-#endif
 
     f32x16 acc[4][2];
 #pragma unroll
@@ -396,12 +356,6 @@ __global__ __launch_bounds__(BM* BN / 128, BM* BN == 128 * 256 || BM * BN == 128
     } while (0)
     // one K stage: issue the next stage's loads, contract this one from LDS buffer BUF_, split + stage the next one into the
     // other buffer, one barrier.  After the last stage the "next" one is a harmless reload of it into the dead buffer.
-#ifdef BX6_STAMPS      // diagnostic build only (tools/bx6_probe.py): cycles per phase of a stage, summed over the block's K loop
-#define STAMP(i_) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_sum[i_] += t_ - st_last; st_last = t_; __builtin_amdgcn_sched_barrier(0); }
-    unsigned long long st_sum[4] = {0, 0, 0, 0}, st_last = 0, st_rt0 = 0;
-#else
-#define STAMP(i_)
-#endif
 #define TILE_BODY(BUF_, NXT_)                                                                                   \
     {                                                                                                           \
         KIt ld;                                                                                                 \
@@ -409,13 +363,9 @@ __global__ __launch_bounds__(BM* BN / 128, BM* BN == 128 * 256 || BM * BN == 128
         ADDR_TILE(ld);                                                                                          \
         ISSUE_TILE(ld, (BUF_) ^ 1);                                                                             \
         __builtin_amdgcn_sched_barrier(0);                                                                      \
-        STAMP(0);                                                                                               \
         COMPUTE(BUF_);                                                                                          \
-        STAMP(1);                                                                                               \
         STORE_TILE((BUF_) ^ 1);                                                                                 \
-        STAMP(2);                                                                                               \
         __syncthreads();                                                                                        \
-        STAMP(3);                                                                                               \
         cur = NXT_;                                                                                             \
     }
 
@@ -431,10 +381,6 @@ __global__ __launch_bounds__(BM* BN / 128, BM* BN == 128 * 256 || BM * BN == 128
     }
     __syncthreads();
     __builtin_amdgcn_s_setprio(0);
-#ifdef BX6_STAMPS
-    st_rt0 = __builtin_amdgcn_s_memrealtime();
-    st_last = __builtin_amdgcn_s_memtime();
-#endif
     if constexpr (SOLO) {
         // one wave, one LDS image: read ALL fragments of the stage, then -- the image is dead -- start the DMA of the next stage's weights
         // into it and the loads of its activations, contract, split + store the activations, wait for the DMA.  (__syncthreads of a
@@ -455,13 +401,9 @@ __global__ __launch_bounds__(BM* BN / 128, BM* BN == 128 * 256 || BM * BN == 128
             ISSUE_A(ra);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // every fragment has left LDS: the image may be overwritten
             ISSUE_B(ld, 0);
-            STAMP(0);
             MM(0, 0) MM(0, 1) MM(1, 0) MM(1, 1) MM(0, 2) MM(2, 0)
-            STAMP(1);
             STORE_TILE(0);
-            STAMP(2);
             __syncthreads();
-            STAMP(3);
             cur = nxt;
         }
     } else {
@@ -478,16 +420,6 @@ __global__ __launch_bounds__(BM* BN / 128, BM* BN == 128 * 256 || BM * BN == 128
         if (cur.kt < nk) TILE_BODY(0, n1);               // an odd last stage
     }
 
-#ifdef BX6_STAMPS
-    if (p.slab && tid == 0) {
-        unsigned long long* dbg = (unsigned long long*)p.slab + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8;
-        dbg[0] = st_rt0; dbg[1] = __builtin_amdgcn_s_memrealtime();
-        dbg[2] = st_sum[0]; dbg[3] = st_sum[1]; dbg[4] = st_sum[2]; dbg[5] = st_sum[3];
-        dbg[6] = (unsigned long long)nk;
-        dbg[7] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
-    }
-#endif
-#undef STAMP
 #undef TILE_BODY
 #undef KIT_SEL
 #undef COMPUTE
@@ -599,13 +531,6 @@ static int launch_bx6(const IgemmParams& p, hipStream_t s) {
     q.xcd_map = (mtiles % 8 == 0 || mtiles >= 64) ? 1 : 0;
     long gx = (q.xcd_map ? (mtiles + 7) / 8 * 8 : mtiles) * (p.Np / BN);
     unsigned gy = (unsigned)p.nclasses;
-#ifdef CGS_EXPERIMENT
-    if (getenv("CGS_CLS_INTER") && atoi(getenv("CGS_CLS_INTER")) && q.xcd_map == 1 && (mtiles % 8) == 0 && p.nclasses > 1 && !p.pix_major && gx >= atol(getenv("CGS_CLS_INTER"))) {
-        bool eq = true;
-        for (int i = 1; i < p.nclasses; ++i) eq = eq && p.cls[i].R * p.cls[i].C == p.cls[0].R * p.cls[0].C;
-        if (eq) { q.xcd_map = 2; gx *= p.nclasses; gy = 1; }
-    }
-#endif
     if (gx > 0x7fffffffL) return cgs_set_error(CGS_EINVAL, "igemm_bx6: grid too large");
     hipLaunchKernelGGL((igemm_bx6_kernel<BM, BN, PAR>), dim3((unsigned)gx, gy, 1), dim3(NT), smem, s, q);
     CGS_CHECK_LAUNCH("igemm_bx6");
@@ -615,22 +540,16 @@ static int launch_bx6(const IgemmParams& p, hipStream_t s) {
     return CGS_OK;
 }
 
-int cgs_igemm_bx6_launch(const IgemmParams& p_in, hipStream_t s, void* dbg, size_t dbg_bytes) {
+int cgs_igemm_bx6_launch(const IgemmParams& p_in, hipStream_t s) {
     IgemmParams p = p_in;
     p.splitk = 1; p.slab = nullptr;
-#ifdef BX6_STAMPS
-    if (getenv("CGS_STAMP") && dbg && dbg_bytes >= (1u << 20)) p.slab = (float*)((char*)dbg + dbg_bytes - (1u << 20) - ((uintptr_t)((char*)dbg + dbg_bytes) & 15));   // (the last MiB of the workspace)
-#endif
     p.prio_t[0] = p.prio_t[1] = p.prio_t[2] = 0;
     p.uni = 0;
     if (!p.vec || (p.N % 64) || p.Np != p.N) return cgs_set_error(CGS_EINVAL, "igemm_bx6: needs Cred %% 32 == 0 and N %% 64 == 0");
     if (p.sign_out && p.epilogue != CGS_EPI_AFFINE_RELU && p.epilogue != CGS_EPI_LRELU)
         return cgs_set_error(CGS_EINVAL, "igemm_bx6: a sign mask needs the relu / lrelu forward epilogues");
-#ifndef BX6_SOLO
-#define BX6_SOLO 1       // N % 128 != 0: one-wave 128 x 64 blocks (1) or the two-wave 256 x 64 block (0)
-#endif
     const bool n256 = (p.N % 256) == 0;
-    const int BM = (n256 || (BX6_SOLO && (p.N % 128) != 0)) ? 128 : 256;
+    const int BM = (n256 || (p.N % 128) != 0) ? 128 : 256;
     cgs_igemm_row_policy(p, BM);
     if ((long)p.B * p.Hout * p.Wout * p.N * 4 > 0x7fffffffL || (long)p.B * p.Hin * p.Win * p.Cred * 4 > 0x7fffffffL)
         return cgs_set_error(CGS_EINVAL, "igemm_bx6: a tensor of one launch exceeds 2 GiB (the caller splits the batch)");
@@ -645,9 +564,5 @@ int cgs_igemm_bx6_launch(const IgemmParams& p_in, hipStream_t s, void* dbg, size
     cgs_igemm_count_flops(p, BM);
     if (n256) return p.tap_parity ? launch_bx6<128, 256, true>(p, s) : launch_bx6<128, 256, false>(p, s);
     if ((p.N % 128) == 0) return p.tap_parity ? launch_bx6<256, 128, true>(p, s) : launch_bx6<256, 128, false>(p, s);
-#if BX6_SOLO
     return p.tap_parity ? launch_bx6<128, 64, true>(p, s) : launch_bx6<128, 64, false>(p, s);
-#else
-    return p.tap_parity ? launch_bx6<256, 64, true>(p, s) : launch_bx6<256, 64, false>(p, s);
-#endif
 }

@@ -67,8 +67,7 @@ class _Conv(_Stage):
         """Called by the norm stage right above: have this conv leave the statistics partials, if the library can.
         ``group_images``: the norm keeps one set of statistics per that many consecutive images (instance norm: 1; the batch
         norm of fused logical batches: one batch); None = the whole batch.  Returns the partials buffer or None."""
-        import os
-        if os.environ.get("CGS_NO_FUSED_BN_STATS") or self.epi != L.EPI_NONE:       # (the first: A/B switch for measurements)
+        if self.epi != L.EPI_NONE:
             return None
         H, W, Cin = self.dx.shape[1:]
         kh, kw, _, Cout = self.w.shape
@@ -113,8 +112,7 @@ class _Deconv(_Stage):
     part_layout = None
 
     def want_stats(self, B, group_images=None):
-        import os
-        if os.environ.get("CGS_NO_FUSED_BN_STATS") or self.epi != L.EPI_NONE:
+        if self.epi != L.EPI_NONE:
             return None
         lay = K.conv_stat_layout(L.DECONV_FWD, *self.call_dims(), self.s, self.s, group_images or B)
         if lay is not None:
@@ -463,7 +461,7 @@ def link_backward_fusion(stages):
 # (the reference's batch 64, single calls of <= 256 images, config 5's 8-image batches: -0.7 ... -2.8 % per call); on the
 # matrix-bound launches of the big batches (dcgan64 at batch 1024: 67 / 134 MB norm inputs) it is a wash -- the sums twin's dearer epilogue and the
 # saved pass cancel, -0.2 % +- the noise of a same-process A/B (profiles/r06_m_*, r06_o_*) -- and those launches would merely move from the
-# headline's dominant kernel to its twin's name in every kernel table.  (CGS_NSTAT_MAX_MB overrides it for A/B measurements: 0 = never.)
+# headline's dominant kernel to its twin's name in every kernel table.
 NSTAT_MAX_BYTES = 48 * 2 ** 20
 
 
@@ -474,9 +472,6 @@ def link_norm_backward_stats(stages, B):
     Only where the library offers it for the call (exact-fp32 implicit GEMM, groups that end on 64-row boundaries of the launch's row
     order); everything else keeps the three-kernel backward.  Call after the norms' groups are final (set_groups re-allocates the
     saved statistics)."""
-    import os
-    if os.environ.get("CGS_NO_FUSED_BN_BWD_STATS"):           # (A/B switch for measurements)
-        return
     for below, above in zip(stages[:-1], stages[1:]):
         if isinstance(below, _Residual):
             link_norm_backward_stats(below.inner, B)
@@ -489,8 +484,7 @@ def link_norm_backward_stats(stages, B):
         else:
             continue
         C = below.out.shape[-1]
-        limit = float(os.environ["CGS_NSTAT_MAX_MB"]) * 2 ** 20 if os.environ.get("CGS_NSTAT_MAX_MB") else NSTAT_MAX_BYTES
-        if limit is not None and below.out.numel() * 4 > limit:
+        if below.out.numel() * 4 > NSTAT_MAX_BYTES:
             continue
         if isinstance(above, _Conv):
             H, W, Cin = above.dx.shape[1:]

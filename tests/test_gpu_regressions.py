@@ -236,8 +236,8 @@ def test_packed_weight_cache_never_drops_live_entries():
 def test_tail_split_launches(case):
     """Round 5: a launch whose tiles fill ONE partial round of workgroup slots (T = a * 256 + r tiles) contracts its last r tiles in
     several K slices (csrc/igemm.hip, igemm_choose_tail; partial tiles added in a fixed order by tail_reduce_kernel) -- the product plan,
-    case "linear_bwd_mnist".  The other cases are launches of several rounds, whose short last round is cut the same way only in
-    experiment builds (CGS_TAIL_MULTI=1: measured, not adopted); they skip here.  The big launch must agree with the same op on 64-sample
+    case "linear_bwd_mnist".  The other cases are launches of several rounds, whose short last round is not cut (measured, not
+    adopted: the comment above igemm_choose_tail); they skip here.  The big launch must agree with the same op on 64-sample
     pieces (small grids: the oracle-pinned paths), carry its epilogue through the reduce kernel, and be bit-identical from run to run."""
     from cgs_amd import kernels as K, lib as L
     d = torch.device("cuda:0")
@@ -266,7 +266,7 @@ def test_tail_split_launches(case):
     tiles, split = int(lib.cgs_last_tail_tiles()), int(lib.cgs_last_tail_split())
     if tiles == 0:
         assert case != "linear_bwd_mnist", "the one-round tail split is the product plan for this launch"
-        pytest.skip("launches of several rounds are split in experiment builds only (CGS_TAIL_MULTI=1)")
+        pytest.skip("launches of several rounds are not split (measured, not adopted)")
     assert split >= 2, (case, tiles, split, L.last_kernel())
     pieces = torch.cat([run(*[t[i:i + 64].contiguous() for t in args]) for i in range(0, B, 64)])
     assert int(lib.cgs_last_tail_tiles()) == 0                             # (the small grids do not split a tail)

@@ -41,42 +41,26 @@ def flat(stages):
             yield st
 
 
-# LB_AB="CGS_TAIL=0;CGS_TAIL=1": time every stage under each environment setting of an experiment build (CGS_LIB=.../libcgs_exp.so reads its
-# switches at every launch), interleaved in ONE process (clocks and placement differ by up to 10 % between processes), best of LB_REPS rounds
-modes = [m for m in os.environ.get("LB_AB", "").split(";") if m] or [""]
+# best of LB_REPS rounds
 reps = int(os.environ.get("LB_REPS", "3"))
 
 
-def set_mode(m):
-    for kv in m.split(","):
-        if kv:
-            k, v = kv.split("=")
-            if v == "-":                      # "-" unsets the variable
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def timed(fn):
-    best, info = [1e30] * len(modes), [None] * len(modes)
+    best, info = 1e30, None
     for _ in range(reps):
-        for i, m in enumerate(modes):
-            set_mode(m)
-            t = timeit(fn)
-            if t < best[i]:
-                best[i], info[i] = t, (L.last_kernel(), float(L.load().cgs_last_executed_flops()), int(L.load().cgs_last_tail_tiles()), int(L.load().cgs_last_tail_split()))
+        t = timeit(fn)
+        if t < best:
+            best, info = t, (L.last_kernel(), float(L.load().cgs_last_executed_flops()), int(L.load().cgs_last_tail_tiles()), int(L.load().cgs_last_tail_split()))
     return best, info
 
 
-def show(best, info):
-    out = []
-    for t, (k, f, tn, ts) in zip(best, info):
-        out.append(f"{t:8.1f} us {f / t / 1e6 / 157.3:.3f}" + (f" tail {tn}x{ts}" if ts else ""))
-    return " | ".join(out) + "  " + info[0][0].replace("igemm_ns_kernel", "ig-ns").replace("igemm_kernel", "ig")
+def show(t, info):
+    k, f, tn, ts = info
+    return (f"{t:8.1f} us {f / t / 1e6 / 157.3:.3f}" + (f" tail {tn}x{ts}" if ts else "") + "  " +
+            k.replace("igemm_ns_kernel", "ig-ns").replace("igemm_kernel", "ig"))
 
 
-tot = [0.0] * len(modes)
-print("modes:", modes)
+tot = 0.0
 for tape, tname in ((eng.g_tail, "G"), (eng.d, "D")):
     prev = eng.theta if tname == "G" else eng.g_tail.stages[-1].out
     for st in flat(tape.stages):
@@ -90,6 +74,6 @@ for tape, tname in ((eng.g_tail, "G"), (eng.d, "D")):
             bb, inb = timed(lambda: st.bwd(dy))
             print(f"{tname} {type(st).__name__[1:]:7s} {str(tuple(xin.shape)):22s} -> {str(tuple(st.out.shape)):22s} fwd {show(bf, inf)}")
             print(f"{'':57s} bwd {show(bb, inb)}")
-            tot = [a + b + c for a, b, c in zip(tot, bf, bb)]
+            tot += bf + bb
         prev = st.out if getattr(st, "out", None) is not None else prev
-print("sum of the contraction stages, forward + backward-data (ms): " + " | ".join(f"{t / 1e3:.3f}" for t in tot) + f"   ({arch}, {G} x {B})")
+print(f"sum of the contraction stages, forward + backward-data (ms): {tot / 1e3:.3f}   ({arch}, {G} x {B})")
