@@ -385,3 +385,396 @@ int cgs_mlp2d_d_step(float* const* w, float* const* b, int nlayers, int nhidden,
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------
+// The 2-D generator G (synthetic/GAN.py:39-49): z[B,2] -> dense -> BN -> ReLU -> [dense -> BN -> ReLU] x (nlayers-2) -> dense -> x[B,2],
+// BN = tf.contrib.layers.batch_norm(decay=0.9, epsilon=1e-5, scale=True, updates_collections=None).  Unlike D, the batch couples
+// every sample at every BN layer, so one launch per dense layer: launch l computes the pre-activations a_l of its samples from
+// BN+ReLU of a_{l-1} (L2-resident workspace), and the BN statistics of a_l come from per-wave partials that launch l+1 combines.
+//   * wave w owns the CONTIGUOUS samples [w*chunk, min(B, (w+1)*chunk)); lane = unit.  Its partial is (mean_w, M2_w) of its own
+//     samples (two passes over values the same lane just wrote); every wave of the next launch combines the W partials in index
+//     order (Chan et al.'s pairwise update), so mean / variance are deterministic and free of the E[a^2]-E[a]^2 cancellation.
+//   * the dense weights live in registers: lane j keeps column j (forward) or row j (backward) of the layer, and the 64-term dot
+//     products broadcast the other operand with v_readlane, no LDS.
+// Backward (g_optim, GAN.py:83-101): the BN backward needs two more per-unit batch sums (sum dxhat, sum dxhat*xhat); the same
+// partial / combine split, one launch per BN layer from the top down, then one block per dense layer sums its weight and bias
+// gradients over the samples in a fixed order and applies w -= lr*g (the D step's mlp_train_grad_kernel pattern).
+// ------------------------------------------------------------------------------------------------------------------
+#define GEN_WMAX 256          // at most 256 waves (partials) per layer; >= 8 samples per wave below that
+
+__device__ __forceinline__ float rlane(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
+
+#define GEN_PBATCH 16          // partials fetched per round trip: the combine is a serial chain, its loads need not be
+
+// (mean, biased variance) of the unit `lane` from the W wave partials [W][2][64], in wave order.  Every wave is non-empty (gen_plan).
+__device__ void gen_combine(const float* __restrict__ part, int W, int chunk, int B, int lane, float& mean, float& var) {
+    float n = 0.f, m = 0.f, M2 = 0.f;
+    for (int p0 = 0; p0 < W; p0 += GEN_PBATCH) {
+        float pm[GEN_PBATCH], pM[GEN_PBATCH];
+#pragma unroll
+        for (int q = 0; q < GEN_PBATCH; ++q) {
+            const bool in = p0 + q < W;
+            pm[q] = in ? part[(size_t)(p0 + q) * 128 + lane] : 0.f;
+            pM[q] = in ? part[(size_t)(p0 + q) * 128 + 64 + lane] : 0.f;
+        }
+#pragma unroll
+        for (int q = 0; q < GEN_PBATCH; ++q) {
+            if (p0 + q >= W) break;
+            const float nb = (float)min(chunk, B - (p0 + q) * chunk);
+            const float nab = n + nb, d = pm[q] - m;
+            m = m + d * (nb / nab);
+            M2 = M2 + pM[q] + d * d * (n * nb / nab);
+            n = nab;
+        }
+    }
+    mean = m; var = M2 / (float)B;
+}
+
+// (sum dxhat, sum dxhat*xhat) of the unit `lane` from the W wave partials, in wave order
+__device__ void gen_sum2(const float* __restrict__ part, int W, int lane, float& s1, float& s2) {
+    s1 = 0.f; s2 = 0.f;
+    for (int p0 = 0; p0 < W; p0 += GEN_PBATCH) {
+        float a[GEN_PBATCH], b[GEN_PBATCH];
+#pragma unroll
+        for (int q = 0; q < GEN_PBATCH; ++q) {
+            const bool in = p0 + q < W;
+            a[q] = in ? part[(size_t)(p0 + q) * 128 + lane] : 0.f;
+            b[q] = in ? part[(size_t)(p0 + q) * 128 + 64 + lane] : 0.f;
+        }
+#pragma unroll
+        for (int q = 0; q < GEN_PBATCH; ++q) { s1 += a[q]; s2 += b[q]; }
+    }
+}
+
+__device__ __forceinline__ float gen_xhat(float a, float mean, float rstd) { return (a - mean) * rstd; }
+__device__ __forceinline__ float gen_bn_relu(float a, float mean, float rstd, float g, float b) { return fmaxf(fmaf(gen_xhat(a, mean, rstd), g, b), 0.f); }
+
+struct GenFwd {
+    const float* w; const float* b;                    // dense layer l: [din][dout], [dout]
+    const float* gamma; const float* beta;             // BN of layer l-1 (l >= 1)
+    float* mmean; float* mvar;                         // its moving statistics (read: inference; updated: training)
+    const float* z;                                    // l == 0: [B][2]
+    const float* pre_in; const float* part_in;         // l >= 1: a_{l-1} [B][64]; training: its wave partials
+    float* stats_in;                                   // training: (mean, rstd) of layer l-1 [2][64] for the backward
+    float* bstat;                                      // optional: (mean, biased var) of layer l-1 [2][nh]
+    float* pre_out; float* part_out;                   // l < nlayers-1: a_l and its partials
+    float* x;                                          // l == nlayers-1: [B][2] (may be null)
+    int l, nlayers, nh, B, W, chunk, train;
+    float eps;
+};
+
+__global__ __launch_bounds__(256) void gen_fwd_kernel(GenFwd a) {
+    const int lane = threadIdx.x & 63, w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= a.W) return;                              // whole waves only
+    const bool last = a.l == a.nlayers - 1;
+    const int nh = a.nh, din = a.l == 0 ? 2 : nh, dout = last ? 2 : nh;
+    float mean = 0.f, rstd = 0.f, gam = 0.f, bet = 0.f;
+    if (a.l > 0 && lane < nh) {                        // BN of layer l-1, lane = its unit
+        float var;
+        if (a.train) gen_combine(a.part_in, a.W, a.chunk, a.B, lane, mean, var);
+        else { mean = a.mmean[lane]; var = a.mvar[lane]; }
+        rstd = 1.f / sqrtf(var + a.eps);
+        gam = a.gamma[lane]; bet = a.beta[lane];
+        if (a.train && w == 0) {
+#pragma clang fp contract(off)      // assign_moving_average: v -= (v - value) * (1 - decay), decay 0.9 -> 0.1f; moving_variance takes the
+                                    // Bessel-corrected batch variance of the fused kernel
+            a.stats_in[lane] = mean; a.stats_in[64 + lane] = rstd;
+            if (a.bstat) { a.bstat[lane] = mean; a.bstat[nh + lane] = var; }
+            const float vu = var * ((float)a.B / (float)(a.B - 1));
+            a.mmean[lane] = a.mmean[lane] - (a.mmean[lane] - mean) * 0.1f;
+            a.mvar[lane] = a.mvar[lane] - (a.mvar[lane] - vu) * 0.1f;
+        }
+    }
+    float wc[64];
+    float bias = 0.f, b0 = 0.f, b1 = 0.f;
+    if (!last) {
+#pragma unroll
+        for (int k = 0; k < 64; ++k) wc[k] = (k < din && lane < dout) ? a.w[k * dout + lane] : 0.f;     // column `lane`
+        bias = lane < dout ? a.b[lane] : 0.f;
+    } else {
+        wc[0] = lane < nh ? a.w[lane * 2] : 0.f;                                                      // row `lane`
+        wc[1] = lane < nh ? a.w[lane * 2 + 1] : 0.f;
+        b0 = a.b[0]; b1 = a.b[1];
+    }
+    const int s0 = w * a.chunk, s1 = min(a.B, s0 + a.chunk);
+    float sum = 0.f;
+    for (int s = s0; s < s1; ++s) {
+        if (a.l == 0) {
+            const float acc = fmaf(a.z[2 * s + 1], wc[1], fmaf(a.z[2 * s], wc[0], bias));
+            a.pre_out[(size_t)s * 64 + lane] = acc;
+            sum += acc;
+            continue;
+        }
+        const float h = lane < nh ? gen_bn_relu(a.pre_in[(size_t)s * 64 + lane], mean, rstd, gam, bet) : 0.f;
+        if (!last) {
+            float acc = bias;
+#pragma unroll
+            for (int k = 0; k < 64; ++k) acc = fmaf(rlane(h, k), wc[k], acc);
+            a.pre_out[(size_t)s * 64 + lane] = acc;
+            sum += acc;
+        } else {
+            float p0 = h * wc[0], p1 = h * wc[1];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) { p0 += __shfl_xor(p0, off, 64); p1 += __shfl_xor(p1, off, 64); }
+            if (lane == 0 && a.x) { a.x[2 * s] = p0 + b0; a.x[2 * s + 1] = p1 + b1; }
+        }
+    }
+    if (last || !a.train) return;
+    const float mw = sum / (float)(s1 - s0);
+    float M2 = 0.f;
+    for (int s = s0; s < s1; ++s) { const float d = a.pre_out[(size_t)s * 64 + lane] - mw; M2 = fmaf(d, d, M2); }
+    a.part_out[(size_t)w * 128 + lane] = mw;
+    a.part_out[(size_t)w * 128 + 64 + lane] = M2;
+}
+
+// One BN layer of the backward.  "Upper" is what feeds the gradient down: the output (top: grad_plugin through W_last) or hidden
+// layer u (its dxhat -> da, then through W_u).  "Lower" (has_low) is hidden layer l = u-1: dxhat_l = gamma_l * relu'(y_l) * dh_l and
+// its wave partials (sum dxhat, sum dxhat*xhat).  dbuf holds dxhat and is overwritten with da in place.
+struct GenBwd {
+    int top, has_low;
+    const float* gplug;                                // top: [B][2]
+    const float* w_up;                                 // W_last [nh][2] (top) or W_u [nh][nh]
+    const float* part_u; const float* pre_u; const float* stats_u; float* dbuf_u;
+    const float* pre_l; const float* stats_l; const float* gamma_l; const float* beta_l; float* dbuf_l; float* part_l;
+    int nh, B, W, chunk;
+};
+
+__global__ __launch_bounds__(256) void gen_bwd_kernel(GenBwd a) {
+    const int lane = threadIdx.x & 63, w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= a.W) return;
+    const int nh = a.nh;
+    const bool on = lane < nh;
+    float wr[64];
+    float mu = 0.f, ru = 0.f, c1 = 0.f, c2 = 0.f;
+    if (a.top) {
+        wr[0] = on ? a.w_up[lane * 2] : 0.f;
+        wr[1] = on ? a.w_up[lane * 2 + 1] : 0.f;
+    } else {
+        if (a.has_low) {
+#pragma unroll
+            for (int j = 0; j < 64; ++j) wr[j] = (on && j < nh) ? a.w_up[lane * nh + j] : 0.f;      // row `lane` of W_u
+        }
+        if (on) {
+            float s1, s2;
+            gen_sum2(a.part_u, a.W, lane, s1, s2);
+            const float invB = 1.f / (float)a.B;
+            c1 = s1 * invB; c2 = s2 * invB;
+            mu = a.stats_u[lane]; ru = a.stats_u[64 + lane];
+        }
+    }
+    float ml = 0.f, rl = 0.f, gl = 0.f, bl = 0.f;
+    if (a.has_low && on) { ml = a.stats_l[lane]; rl = a.stats_l[64 + lane]; gl = a.gamma_l[lane]; bl = a.beta_l[lane]; }
+    const int s0 = w * a.chunk, s1 = min(a.B, s0 + a.chunk);
+    float t1 = 0.f, t2 = 0.f;
+    for (int s = s0; s < s1; ++s) {
+        float dh;
+        if (a.top) {
+            dh = fmaf(a.gplug[2 * s + 1], wr[1], a.gplug[2 * s] * wr[0]);
+        } else {
+            const size_t o = (size_t)s * 64 + lane;
+            const float xh = on ? gen_xhat(a.pre_u[o], mu, ru) : 0.f;
+            const float da = on ? ru * (a.dbuf_u[o] - c1 - xh * c2) : 0.f;        // tf FusedBatchNormGrad, training
+            a.dbuf_u[o] = da;
+            if (!a.has_low) continue;
+            dh = 0.f;
+#pragma unroll
+            for (int j = 0; j < 64; ++j) dh = fmaf(rlane(da, j), wr[j], dh);
+        }
+        const size_t o = (size_t)s * 64 + lane;
+        float dx = 0.f, xh = 0.f;
+        if (on) {
+            xh = gen_xhat(a.pre_l[o], ml, rl);
+            dx = fmaf(xh, gl, bl) > 0.f ? dh * gl : 0.f;
+        }
+        a.dbuf_l[o] = dx;
+        t1 += dx; t2 = fmaf(dx, xh, t2);
+    }
+    if (!a.has_low) return;
+    a.part_l[(size_t)w * 128 + lane] = t1;
+    a.part_l[(size_t)w * 128 + 64 + lane] = t2;
+}
+
+struct GenGrad {
+    float* w[MLP_MAX_LAYERS]; float* b[MLP_MAX_LAYERS];
+    float* gw[MLP_MAX_LAYERS]; float* gb[MLP_MAX_LAYERS];           // may be null
+    const float* gamma[MLP_MAX_LAYERS - 1]; const float* beta[MLP_MAX_LAYERS - 1];
+    const float* z; const float* gplug; const float* pre; const float* stats; const float* dbuf;
+    int nlayers, nh, B;
+    float lr;
+};
+
+// block l: dW_l = in_l^T da_l, db_l = column sums of da_l (in_0 = z, in_l = relu(BN(a_{l-1})) recomputed exactly as the forward did;
+// da of the last layer = grad_plugin), samples in tiles of 64 in a fixed order; then w -= lr*g in place.
+__global__ __launch_bounds__(1024) void gen_grad_kernel(GenGrad q) {
+    __shared__ float As[64][65];
+    __shared__ __attribute__((aligned(16))) float Ds[64][64];
+    const int t = threadIdx.x, l = blockIdx.x, nh = q.nh, B = q.B;
+    const bool last = l == q.nlayers - 1;
+    const int din = l == 0 ? 2 : nh, dout = last ? 2 : nh;
+    const int i = t >> 4, j4 = (t & 15) * 4;
+    const float* pin = l > 0 ? q.pre + (size_t)(l - 1) * B * 64 : nullptr;
+    const float* sl = l > 0 ? q.stats + (size_t)(l - 1) * 128 : nullptr;
+    const float* dl = last ? nullptr : q.dbuf + (size_t)l * B * 64;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f}, accb[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        for (int e = t; e < 4096; e += 1024) {
+            const int bb = e >> 6, c = e & 63, b = b0 + bb;
+            float x = 0.f, d = 0.f;
+            if (b < B) {
+                if (l == 0) { if (c < 2) x = q.z[2 * b + c]; }
+                else if (c < nh) x = gen_bn_relu(pin[(size_t)b * 64 + c], sl[c], sl[64 + c], q.gamma[l - 1][c], q.beta[l - 1][c]);
+                if (last) { if (c < 2) d = q.gplug[2 * b + c]; }
+                else d = dl[(size_t)b * 64 + c];
+            }
+            As[bb][c] = x; Ds[bb][c] = d;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int bb = 0; bb < 64; ++bb) {
+            const float x = As[bb][i];
+            const float4 d = *(const float4*)&Ds[bb][j4];
+            acc[0] = fmaf(x, d.x, acc[0]); acc[1] = fmaf(x, d.y, acc[1]); acc[2] = fmaf(x, d.z, acc[2]); acc[3] = fmaf(x, d.w, acc[3]);
+            accb[0] += d.x; accb[1] += d.y; accb[2] += d.z; accb[3] += d.w;
+        }
+        __syncthreads();
+    }
+    for (int e = 0; e < 4; ++e) {
+#pragma clang fp contract(off)      // var -= lr * grad as two roundings (ApplyGradientDescent)
+        const int j = j4 + e;
+        if (i < din && j < dout) {
+            const size_t o = (size_t)i * dout + j;
+            if (q.gw[l]) q.gw[l][o] = acc[e];
+            if (q.lr != 0.f) q.w[l][o] = q.w[l][o] - q.lr * acc[e];
+        }
+        if (i == 0 && j < dout) {
+            if (q.gb[l]) q.gb[l][j] = accb[e];
+            if (q.lr != 0.f) q.b[l][j] = q.b[l][j] - q.lr * accb[e];
+        }
+    }
+}
+
+// waves per layer and samples per wave: <= GEN_WMAX waves, >= 8 samples each below that, none empty
+static void gen_plan(int B, int& W, int& chunk) {
+    W = cgs_ceil_div(B, 8);
+    if (W > GEN_WMAX) W = GEN_WMAX;
+    chunk = cgs_ceil_div(B, W);
+    W = cgs_ceil_div(B, chunk);
+}
+
+static size_t gen_ws_floats(int B, int nlayers, int with_backward) {
+    const size_t H = (size_t)(nlayers - 1);
+    return H * (size_t)B * 64 * (with_backward ? 2 : 1) + H * GEN_WMAX * 128 + H * 128;
+}
+
+static int gen_check(const char* who, const float* const* gamma, const float* const* beta, float* const* mm, float* const* mv, int nlayers,
+                     const float* z, int B, int train, float eps, size_t need, void* ws, size_t ws_bytes) {
+    if (!gamma || !beta || !mm || !mv) return cgs_set_error(CGS_EINVAL, "%s: null batch-norm array", who);
+    for (int l = 0; l < nlayers - 1; ++l)
+        if (!gamma[l] || !beta[l] || !mm[l] || !mv[l]) return cgs_set_error(CGS_EINVAL, "%s: null batch-norm variable", who);
+    if (!z || B < (train ? 2 : 1) || !(eps > 0.f)) return cgs_set_error(CGS_EINVAL, "%s: bad argument (B=%d, training=%d)", who, B, train);
+    if (!ws || ws_bytes < need) return cgs_set_error(CGS_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    return CGS_OK;
+}
+
+static int gen_forward(const MlpParams& p, const float* const* gamma, const float* const* beta, float* const* mm, float* const* mv,
+                       const float* z, float* x, int B, int train, float eps, float* bstat, float* ws, hipStream_t st) {
+    const int nl = p.nlayers, H = nl - 1;
+    int W, chunk;
+    gen_plan(B, W, chunk);
+    float* pre = ws;
+    float* part = pre + (size_t)H * B * 64;
+    float* stats = part + (size_t)H * GEN_WMAX * 128;
+    for (int l = 0; l < nl; ++l) {
+        GenFwd a = {};
+        a.w = p.w[l]; a.b = p.b[l];
+        if (l > 0) {
+            a.gamma = gamma[l - 1]; a.beta = beta[l - 1]; a.mmean = mm[l - 1]; a.mvar = mv[l - 1];
+            a.pre_in = pre + (size_t)(l - 1) * B * 64; a.part_in = part + (size_t)(l - 1) * GEN_WMAX * 128;
+            a.stats_in = stats + (size_t)(l - 1) * 128;
+            a.bstat = bstat ? bstat + (size_t)(l - 1) * 2 * p.nh : nullptr;
+        } else {
+            a.z = z;
+        }
+        if (l < nl - 1) { a.pre_out = pre + (size_t)l * B * 64; a.part_out = part + (size_t)l * GEN_WMAX * 128; }
+        else a.x = x;
+        a.l = l; a.nlayers = nl; a.nh = p.nh; a.B = B; a.W = W; a.chunk = chunk; a.train = train; a.eps = eps;
+        hipLaunchKernelGGL(gen_fwd_kernel, dim3(cgs_ceil_div(W, 4)), dim3(256), 0, st, a);
+        CGS_CHECK_LAUNCH("mlp2d_gen_fwd");
+    }
+    return CGS_OK;
+}
+
+extern "C" {
+
+size_t cgs_mlp2d_gen_ws_bytes(int B, int nlayers, int with_backward) {
+    if (B <= 0 || nlayers < 2 || nlayers > MLP_MAX_LAYERS) return 0;
+    return gen_ws_floats(B, nlayers, with_backward) * sizeof(float);
+}
+
+int cgs_mlp2d_gen_fwd(const float* const* w, const float* const* b, const float* const* gamma, const float* const* beta,
+                      float* const* moving_mean, float* const* moving_variance, int nlayers, int nhidden, const float* z, float* x, int B,
+                      int is_training, float eps, float* batch_stats, void* ws, size_t ws_bytes, void* stream) {
+    MlpParams p;
+    int rc = mlp_fill(p, w, b, nlayers, nhidden, "mlp2d_gen_fwd");
+    if (rc) return rc;
+    if (!x) return cgs_set_error(CGS_EINVAL, "mlp2d_gen_fwd: null output");
+    rc = gen_check("mlp2d_gen_fwd", gamma, beta, moving_mean, moving_variance, nlayers, z, B, is_training != 0, eps,
+                   gen_ws_floats(B, nlayers, 0) * sizeof(float), ws, ws_bytes);
+    if (rc) return rc;
+    return gen_forward(p, gamma, beta, moving_mean, moving_variance, z, x, B, is_training != 0, eps, is_training ? batch_stats : nullptr,
+                       (float*)ws, (hipStream_t)stream);
+}
+
+int cgs_mlp2d_g_step(float* const* w, float* const* b, const float* const* gamma, const float* const* beta, float* const* moving_mean,
+                     float* const* moving_variance, int nlayers, int nhidden, const float* z, const float* grad_plugin, int B, float eps,
+                     float lr, float* const* gw, float* const* gb, float* x, void* ws, size_t ws_bytes, void* stream) {
+    MlpParams p;
+    int rc = mlp_fill(p, (const float* const*)w, (const float* const*)b, nlayers, nhidden, "mlp2d_g_step");
+    if (rc) return rc;
+    if (!grad_plugin) return cgs_set_error(CGS_EINVAL, "mlp2d_g_step: null grad_plugin");
+    rc = gen_check("mlp2d_g_step", gamma, beta, moving_mean, moving_variance, nlayers, z, B, 1, eps,
+                   gen_ws_floats(B, nlayers, 1) * sizeof(float), ws, ws_bytes);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = gen_forward(p, gamma, beta, moving_mean, moving_variance, z, x, B, 1, eps, nullptr, (float*)ws, st);
+    if (rc) return rc;
+    const int nl = nlayers, H = nl - 1;
+    int W, chunk;
+    gen_plan(B, W, chunk);
+    float* pre = (float*)ws;
+    float* part = pre + (size_t)H * B * 64;
+    float* stats = part + (size_t)H * GEN_WMAX * 128;
+    float* dbuf = stats + (size_t)H * 128;
+    // top: output -> layer nl-2; then layer u -> u-1 for u = nl-2 .. 1; then layer 0 alone (its da)
+    for (int u = nl - 1; u >= 0; --u) {
+        GenBwd a = {};
+        a.top = u == nl - 1; a.has_low = u > 0;
+        a.w_up = w[u];
+        if (a.top) a.gplug = grad_plugin;
+        else {
+            a.part_u = part + (size_t)u * GEN_WMAX * 128; a.pre_u = pre + (size_t)u * B * 64; a.stats_u = stats + (size_t)u * 128;
+            a.dbuf_u = dbuf + (size_t)u * B * 64;
+        }
+        if (a.has_low) {
+            const int l = u - 1;
+            a.pre_l = pre + (size_t)l * B * 64; a.stats_l = stats + (size_t)l * 128; a.gamma_l = gamma[l]; a.beta_l = beta[l];
+            a.dbuf_l = dbuf + (size_t)l * B * 64; a.part_l = part + (size_t)l * GEN_WMAX * 128;
+        }
+        a.nh = nhidden; a.B = B; a.W = W; a.chunk = chunk;
+        hipLaunchKernelGGL(gen_bwd_kernel, dim3(cgs_ceil_div(W, 4)), dim3(256), 0, st, a);
+        CGS_CHECK_LAUNCH("mlp2d_gen_bwd");
+    }
+    GenGrad q = {};
+    for (int l = 0; l < nl; ++l) {
+        q.w[l] = w[l]; q.b[l] = b[l];
+        q.gw[l] = gw ? gw[l] : nullptr; q.gb[l] = gb ? gb[l] : nullptr;
+        if (l < nl - 1) { q.gamma[l] = gamma[l]; q.beta[l] = beta[l]; }
+    }
+    q.z = z; q.gplug = grad_plugin; q.pre = pre; q.stats = stats; q.dbuf = dbuf;
+    q.nlayers = nl; q.nh = nhidden; q.B = B; q.lr = lr;
+    hipLaunchKernelGGL(gen_grad_kernel, dim3(nl), dim3(1024), 0, st, q);
+    CGS_CHECK_LAUNCH("mlp2d_gen_grad");
+    return CGS_OK;
+}
+
+}  // extern "C"

@@ -7,17 +7,51 @@
 * ``Refiner``           -- same class surface as ``refiner_cpu.Refiner`` (``Refiner(args)``, ``set_env``,
   ``manipulate_sample``), but the whole K-step loop -- D forward, saliency, ladam / momentum / sgd update, best-loss
   tracking, trajectory -- is ONE kernel launch (one wave per sample, weights in LDS).
+* ``MLPGenerator`` / ``GStep`` -- the batch-normalised MLP G of synthetic/GAN.py:39-49 (training- and inference-mode forward)
+  and its update g_optim (GAN.py:83-101) on the device.
+* ``GanTrainer``        -- the iteration loop of synthetic/main.py:350-395 (train | calibrate | shape | test) on these pieces.
 
-Variable names follow tf.layers.dense: ``discriminator/d_fc<i>/kernel`` ([din, dout]) and ``.../bias``.
+Variable names follow tf.layers.dense: ``discriminator/d_fc<i>/kernel`` ([din, dout]) and ``.../bias``; G's are
+``generator/g_fc<i>/kernel|bias`` and ``generator/BatchNorm[_k]/gamma|beta|moving_mean|moving_variance``.
 """
 import ctypes as C
 
 import numpy as np
 import torch
 
+from . import checkpoint as CK
 from . import lib as L
+from .datasets import NoiseDataset
 
 _METHODS = {"sgd": 0, "momentum": 1, "ladam": 2}
+
+
+def glorot_uniform(rs, din, dout):
+    """tf.layers.dense's default kernel initializer (glorot_uniform: U(-l, l), l = sqrt(6 / (din + dout))) from a numpy RandomState."""
+    lim = np.sqrt(6.0 / (din + dout))
+    return rs.uniform(-lim, lim, size=(din, dout)).astype(np.float32)
+
+
+def _dense_init(prefix, dims, seed):
+    """{prefix<i>/kernel: glorot-uniform, prefix<i>/bias: zeros} for the dense chain ``dims`` (tf.layers.dense defaults)."""
+    rs = np.random.RandomState(seed)
+    P = {}
+    for i in range(len(dims) - 1):
+        P[f"{prefix}{i + 1}/kernel"] = glorot_uniform(rs, dims[i], dims[i + 1])
+        P[f"{prefix}{i + 1}/bias"] = np.zeros(dims[i + 1], np.float32)
+    return P
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _upload(x, dev):
+    """A host batch -> float32 device tensor without a host synchronisation (pinned staging, asynchronous copy); device tensors pass."""
+    if isinstance(x, torch.Tensor) and x.device == dev:
+        return x.float().contiguous()
+    t = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)) if not isinstance(x, torch.Tensor) else x.float().contiguous()
+    return t.pin_memory().to(dev, non_blocking=True)
 
 
 class MLPDiscriminator:
@@ -46,6 +80,22 @@ class MLPDiscriminator:
         for i, (w, b) in enumerate(zip(Ws, bs)):
             P[f"discriminator/d_fc{i + 1}/kernel"], P[f"discriminator/d_fc{i + 1}/bias"] = np.asarray(w), np.asarray(b)
         return cls(P, device)
+
+    @staticmethod
+    def init_params(seed, nhidden=64, nlayers=6):
+        """Seeded tf.layers.dense defaults (glorot-uniform kernels, zero biases) for 2 -> nhidden x (nlayers-1) -> 1, as host arrays."""
+        return _dense_init("discriminator/d_fc", [2] + [nhidden] * (nlayers - 1) + [1], seed)
+
+    @classmethod
+    def init(cls, seed, nhidden=64, nlayers=6, device="cuda:0"):
+        return cls(cls.init_params(seed, nhidden, nlayers), device)
+
+    def params(self):
+        """{TF variable name: device tensor} -- the D half of a synthetic/main.py checkpoint (``checkpoint.save`` writes it)."""
+        P = {}
+        for i in range(self.nlayers):
+            P[f"discriminator/d_fc{i + 1}/kernel"], P[f"discriminator/d_fc{i + 1}/bias"] = self.w[i], self.b[i]
+        return P
 
     def _x(self, x):
         return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(self.dev) if not isinstance(x, torch.Tensor) else x.float().contiguous().to(self.dev)
@@ -191,7 +241,8 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
     quality, then D-score -> MH fill (thinning T = 20, chain seeded with mean(real_sigmoid)) until ``len(eval_batch)`` samples
     are accepted (proposal counter advancing only for productive batches, :251) and report the collaborative sample's
     quality.  Returns {"refinement": {...}, "collaborate": {..., "eff": accepted / proposed}} with the reference's four 2-D
-    metrics (utils_sampling.py:132-184; ``thres`` = 4 std as in main.py:221)."""
+    metrics (utils_sampling.py:132-184; ``thres`` = 4 std as in main.py:221).  ``generate``: a callable returning a generator batch,
+    or an ``MLPGenerator`` (then each proposal batch is G in training mode on ``NoiseDataset().next_batch(len(eval_batch))``)."""
     from . import metrics as Mx
     from .evaluate import collaborate
     from .sampling import IndependenceSampler
@@ -202,6 +253,9 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
         return {"mean_dist": float(mean_dist), "good": float(good),
                 "kl": float(Mx.metrics_diversity(target_batch, samples, centeroids, thres)),
                 "js": float(Mx.metrics_distribution(target_batch, samples, centeroids, thres))}
+    if isinstance(generate, MLPGenerator):                                             # training-mode G on fresh noise, main.py:239-240
+        G, noise, n = generate, NoiseDataset(), len(eval_batch)
+        generate = lambda: G.generate(noise.next_batch(n)).cpu().numpy()
     _, score = proposer(refiner, generate, discriminator)
     real_sigmoid = score(target_batch)                                                 # main.py:116
     out = {"standard": quality(eval_batch)}
@@ -213,3 +267,217 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
                                base=(refined, score(refined)), count_only_productive=True)      # :229-253
     out["collaborate"] = dict(quality(samples), eff=float(eff))
     return out
+
+
+def _bn_name(k):
+    """tf.contrib.layers.batch_norm's default scopes in creation order: BatchNorm, BatchNorm_1, ..."""
+    return "generator/BatchNorm" if k == 0 else f"generator/BatchNorm_{k}"
+
+
+class MLPGenerator:
+    """The 2-D generator of synthetic/GAN.py:39-49 on the device: 2 -> nhidden x (nlayers-1) -> 2, every hidden dense layer followed by
+    tf.contrib.layers.batch_norm(decay=0.9, epsilon=1e-5, scale=True, updates_collections=None) and a ReLU.  The variables are device
+    tensors under their TF names; ``generate`` in training mode moves the BN moving averages in place, as every ``sess.run`` of
+    ``gan.generates`` does in the reference."""
+    # GAN.py:43,47 pass epsilon=1e-5, but rank-2 inputs take TF 1.x's fused path, whose nn_impl.fused_batch_norm raises any epsilon below
+    # cuDNN's minimum to 1.001e-5: the value the reference computes with (DESIGN.md section 10)
+    EPS = 1.001e-5
+
+    def __init__(self, params, device="cuda:0"):
+        self.dev = torch.device(device)
+        if self.dev.type != "cuda":
+            raise L.CgsError("MLPGenerator needs a GPU device")
+        L.load()
+        n = 1
+        while f"generator/g_fc{n + 1}/kernel" in params:
+            n += 1
+        self.nlayers = n
+        f32 = lambda name: torch.as_tensor(np.asarray(params[name]), dtype=torch.float32).contiguous().to(self.dev)
+        self.w = [f32(f"generator/g_fc{i + 1}/kernel") for i in range(n)]
+        self.b = [f32(f"generator/g_fc{i + 1}/bias") for i in range(n)]
+        self.nhidden = int(self.w[0].shape[1])
+        if self.w[0].shape[0] != 2 or self.w[-1].shape[1] != 2 or self.nhidden > 64 or not 2 <= n <= 6:
+            raise L.CgsError(f"MLPGenerator: unsupported shape (2 -> {self.nhidden} x {n - 1} -> 2; need nhidden <= 64, 2..6 layers)")
+        self.gamma, self.beta, self.moving_mean, self.moving_variance = ([f32(f"{_bn_name(k)}/{v}") for k in range(n - 1)]
+                                                                         for v in ("gamma", "beta", "moving_mean", "moving_variance"))
+        ptrs = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        self._wp, self._bp = ptrs(self.w), ptrs(self.b)
+        self._gp, self._betap = ptrs(self.gamma), ptrs(self.beta)
+        self._mmp, self._mvp = ptrs(self.moving_mean), ptrs(self.moving_variance)
+        self._ws = None
+
+    @staticmethod
+    def init_params(seed, nhidden=64, nlayers=6):
+        """Seeded TF defaults as host arrays: glorot-uniform kernels and zero biases (tf.layers.dense), gamma 1, beta 0, moving mean 0,
+        moving variance 1 (tf.contrib.layers.batch_norm)."""
+        P = _dense_init("generator/g_fc", [2] + [nhidden] * (nlayers - 1) + [2], seed)
+        for k in range(nlayers - 1):
+            one, zero = np.ones(nhidden, np.float32), np.zeros(nhidden, np.float32)
+            P.update({f"{_bn_name(k)}/gamma": one, f"{_bn_name(k)}/beta": zero.copy(),
+                      f"{_bn_name(k)}/moving_mean": zero.copy(), f"{_bn_name(k)}/moving_variance": one.copy()})
+        return P
+
+    @classmethod
+    def init(cls, seed, nhidden=64, nlayers=6, device="cuda:0"):
+        return cls(cls.init_params(seed, nhidden, nlayers), device)
+
+    @classmethod
+    def from_params(cls, params, device="cuda:0"):
+        """From a ``{name: array}`` map such as ``checkpoint.load`` returns; other (e.g. discriminator/...) names are ignored."""
+        return cls(params, device)
+
+    def params(self):
+        """{TF variable name: device tensor} -- the G half of a synthetic/main.py checkpoint."""
+        P = {}
+        for i in range(self.nlayers):
+            P[f"generator/g_fc{i + 1}/kernel"], P[f"generator/g_fc{i + 1}/bias"] = self.w[i], self.b[i]
+        for k in range(self.nlayers - 1):
+            for v, ts in (("gamma", self.gamma), ("beta", self.beta), ("moving_mean", self.moving_mean), ("moving_variance", self.moving_variance)):
+                P[f"{_bn_name(k)}/{v}"] = ts[k]
+        return P
+
+    def _workspace(self, B, with_backward):
+        need = int(L.load().cgs_mlp2d_gen_ws_bytes(B, self.nlayers, int(with_backward)))
+        if self._ws is None or self._ws.numel() * 4 < need:
+            self._ws = torch.empty(need // 4 + 4, dtype=torch.float32, device=self.dev)
+        return self._ws
+
+    def generate(self, z, is_training=True, batch_stats=False):
+        """G(z) as a device [B,2] tensor.  Training mode (``gan.generates``): batch statistics, moving averages updated in place;
+        inference mode (``gan.fake_samples``, GAN.py:105): the moving statistics.  ``batch_stats=True`` (training mode) also returns
+        the [nlayers-1, 2, nhidden] (mean, biased variance) of every BN layer."""
+        zd = _upload(z, self.dev)
+        B = zd.shape[0]
+        x = torch.empty((B, 2), dtype=torch.float32, device=self.dev)
+        st = torch.empty((self.nlayers - 1, 2, self.nhidden), dtype=torch.float32, device=self.dev) if batch_stats else None
+        ws = self._workspace(B, False)
+        L.call("cgs_mlp2d_gen_fwd", self._wp, self._bp, self._gp, self._betap, self._mmp, self._mvp, self.nlayers, self.nhidden,
+               zd.data_ptr(), x.data_ptr(), B, int(bool(is_training)), self.EPS, None if st is None else st.data_ptr(),
+               ws.data_ptr(), ws.numel() * 4, _stream(self.dev))
+        return (x, st) if batch_stats else x
+
+
+class GStep:
+    """The generator update g_optim (synthetic/GAN.py:83-101, run at synthetic/main.py:379-380): gradients of ``generates`` w.r.t.
+    g_vars (the g_fc kernels and biases only -- the BN gamma / beta do not carry 'g_' in their names) against a caller-supplied
+    grad_plugin [B,2], then GradientDescentOptimizer(lrg) IN PLACE on the ``MLPGenerator``'s tensors.  Its training-mode forward moves
+    the BN moving averages once more, like the reference's g_optim run."""
+
+    def __init__(self, generator, lrg=5e-3):                          # synthetic/main.py:38 (--lrg 5e-3)
+        self.G, self.lrg = generator, float(lrg)
+        self.gw = [torch.zeros_like(t) for t in generator.w]
+        self.gb = [torch.zeros_like(t) for t in generator.b]
+        n = generator.nlayers
+        self._gwp = (C.c_void_p * n)(*[t.data_ptr() for t in self.gw])
+        self._gbp = (C.c_void_p * n)(*[t.data_ptr() for t in self.gb])
+
+    def _run(self, z, grad_plugin, lr):
+        G = self.G
+        zd, gd = _upload(z, G.dev), _upload(grad_plugin, G.dev)
+        B = zd.shape[0]
+        if tuple(gd.shape) != (B, 2):
+            raise L.CgsError(f"GStep: grad_plugin shape {tuple(gd.shape)} != ({B}, 2)")
+        ws = G._workspace(B, True)
+        L.call("cgs_mlp2d_g_step", G._wp, G._bp, G._gp, G._betap, G._mmp, G._mvp, G.nlayers, G.nhidden, zd.data_ptr(), gd.data_ptr(), B,
+               G.EPS, float(lr), self._gwp, self._gbp, None, ws.data_ptr(), ws.numel() * 4, _stream(G.dev))
+
+    def grads(self, z, grad_plugin):
+        """([dW...], [db...]) device tensors; the weights stay as they are (the moving averages still move: the forward runs)."""
+        self._run(z, grad_plugin, 0.0)
+        return self.gw, self.gb
+
+    def step(self, z, grad_plugin):
+        self._run(z, grad_plugin, self.lrg)
+
+
+class GanTrainer:
+    """The iteration loop of synthetic/main.py:350-395 with d_steps = g_steps = 1, on the device, in the reference's order and with its
+    host RNG draws (``data`` / ``noise`` consume the global numpy stream exactly as ToyDataset / NoiseDataset do there):
+
+    * train:     real, z -> D step on (real, G(z))                        then  z' -> D saliency of G(z') -> G step on (z', saliency)
+    * calibrate: real, z -> D step on (real, G(z))
+    * shape:     real, z -> D step on (real, probabilistic refinement of G(z))   (``refiner``: a ``synthetic.Refiner``)
+    * test:      real, z drawn, nothing trained
+
+    G runs in training mode wherever the reference runs ``gan.generates``: once in the D step and twice (same z) in the G step, so the
+    BN moving averages move three times per train iteration.  Nothing inside an iteration waits for the device; the last D losses stay in
+    the device tensor ``d_loss`` (d_loss_real, d_loss_fake)."""
+
+    MODES = ("train", "calibrate", "shape", "test")
+
+    def __init__(self, G, D, data, noise=None, batch_size=1000, lrd=1e-2, lrg=5e-3, refiner=None):
+        self.G, self.D, self.data = G, D, data
+        self.noise = noise if noise is not None else NoiseDataset()
+        self.batch_size = int(batch_size)
+        self.dshaper, self.gstep = DShaper(D, lrd), GStep(G, lrg)
+        self.d_loss = self.dshaper.loss
+        self.refiner = refiner
+        self.eval_noise = self.eval_batch = self.target_batch = None
+
+    def prepare_eval(self, eval_size=10000):
+        """main.py:297-300: eval noise, its training-mode G batch, then the target batch (same draws, same order)."""
+        self.eval_noise = self.noise.next_batch(eval_size)
+        self.eval_batch = self.G.generate(self.eval_noise)
+        self.target_batch = self.data.next_batch(eval_size)
+        return self.eval_batch, self.target_batch
+
+    def _refine(self, fake):
+        """refiner.manipulate_sample(fake, 'probabilistic') (sampling/refiner_cpu.py:19-76) with the baseline and the trajectory kept on
+        the device: the same draws (real batch, then the per-sample step pick), no host round trip."""
+        r, D, dev = self.refiner, self.D, self.D.dev
+        n = fake.shape[0]
+        real = _upload(r.data.next_batch(n), dev)
+        real_sig, _ = D.sigmoid_and_saliency(real, want_saliency=False)
+        _, _, traj = D.refine(fake, real_sig.mean(), r.forward_steps, r.step_size, r.method, want_traj=True)
+        pick = torch.from_numpy(np.random.randint(r.forward_steps + 1, size=n)).pin_memory().to(dev, non_blocking=True)
+        return traj[torch.arange(n, device=dev), pick]
+
+    def iteration(self, mode="train"):
+        if mode not in self.MODES:
+            raise NotImplementedError(mode)
+        B = self.batch_size
+        real = _upload(self.data.next_batch(B), self.D.dev)              # main.py:356-357
+        z = self.noise.next_batch(B)
+        if mode in ("train", "calibrate"):
+            self.dshaper.step(real, self.G.generate(z))
+        elif mode == "shape":
+            if self.refiner is None:
+                raise ValueError("shape mode needs a refiner")
+            self.dshaper.step(real, self._refine(self.G.generate(z)))
+        if mode == "train":                                              # main.py:376-380
+            z = _upload(self.noise.next_batch(B), self.G.dev)
+            _, grad_default = self.D.sigmoid_and_saliency(self.G.generate(z))      # grad_default = d g_loss / d generates (1/B inside)
+            self.gstep.step(z, grad_default)
+        return self.d_loss
+
+    def run(self, niters, mode="train", save_every=0, save_prefix=None, eval_every=1000, on_eval=None):
+        """``niters`` iterations i = 0 .. niters-1.  Like main.py:384-395: at i % eval_every == 0 a train run regenerates the eval batch
+        (training-mode G on the eval noise, after ``prepare_eval``) and ``on_eval(i, self)`` is called; with ``save_every`` the {G, D}
+        checkpoint ``<save_prefix>-<i>.safetensors`` is written at every i % save_every == 0, i > 0 (so the iteration-1000 checkpoint
+        is the state after iterations 0 .. 1000).  Returns the paths written.
+
+        A bit-equal host RNG stream and bit-equal moving statistics (against a reference run with its evaluation) need ``prepare_eval()``
+        BEFORE ``run()``: main.py draws the eval noise and the target batch before its loop (:297-300), and every eval-batch regeneration
+        is one more training-mode G call.  Without it the loop draws only the iterations' own batches."""
+        written = []
+        for i in range(niters):
+            self.iteration(mode)
+            if i % eval_every == 0:
+                if mode == "train" and self.eval_noise is not None:
+                    self.eval_batch = self.G.generate(self.eval_noise)
+                if on_eval is not None:
+                    on_eval(i, self)
+            if save_every and i % save_every == 0 and i > 0:
+                path = f"{save_prefix}-{i}.safetensors"
+                self.save(path)
+                written.append(path)
+        return written
+
+    def save(self, path):
+        CK.save(path, {**self.G.params(), **self.D.params()})
+
+    @staticmethod
+    def load(path, device="cuda:0"):
+        """-> (MLPGenerator, MLPDiscriminator) from a {G, D} checkpoint (ours, or a converted synthetic/main.py one)."""
+        P = CK.load(path)
+        return MLPGenerator.from_params(P, device), MLPDiscriminator(P, device)

@@ -383,6 +383,28 @@ int cgs_mlp2d_d_step(float* const* w, float* const* b, int nlayers, int nhidden,
                      const float* fake, int B_fake, float lr, float* const* gw, float* const* gb, float* loss,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* The 2-D generator G (synthetic/GAN.py:39-49): z[B,2] -> dense(2->nh) -> BN -> ReLU -> [dense(nh->nh) -> BN -> ReLU] x (nlayers-2)
+ * -> dense(nh->2) -> x[B,2], BN = tf.contrib.layers.batch_norm(decay=0.9, epsilon, scale=True, updates_collections=None).
+ * w / b: HOST arrays of nlayers DEVICE pointers (w[l] the [din,dout] kernel of generator/g_fc<l+1>); gamma / beta / moving_mean /
+ * moving_variance: HOST arrays of nlayers-1 DEVICE pointers ([nhidden] each: generator/BatchNorm[_k]/...).  nlayers 2..6, nhidden <= 64.
+ * Training mode (is_training != 0, B >= 2; gan.generates, GAN.py:63): BN normalises with the batch mean and biased variance and, as part
+ * of the same call (updates_collections=None), moves moving_mean / moving_variance IN PLACE: v -= (v - value) * 0.1, value = the batch
+ * mean / the Bessel-corrected batch variance (what TF 1.x's FusedBatchNorm returns as batch_variance).  batch_stats (device, may be NULL): [nlayers-1][2][nhidden]
+ * <- (mean, biased variance) of every BN layer.  Inference mode (gan.fake_samples, GAN.py:105): the moving statistics, nothing
+ * written but x.  Deterministic (fixed summation order, no atomics).  ws: cgs_mlp2d_gen_ws_bytes(B, nlayers, 0). */
+size_t cgs_mlp2d_gen_ws_bytes(int B, int nlayers, int with_backward);
+int cgs_mlp2d_gen_fwd(const float* const* w, const float* const* b, const float* const* gamma, const float* const* beta,
+                      float* const* moving_mean, float* const* moving_variance, int nlayers, int nhidden, const float* z, float* x, int B,
+                      int is_training, float eps, float* batch_stats, void* ws, size_t ws_bytes, void* stream);
+/* The G update g_optim (GAN.py:83-101, run at synthetic/main.py:379-380): a training-mode forward on z (moving statistics updated as
+ * above; x[B,2] <- G(z) if x != NULL), the gradients tf.gradients(generates, g_vars, grad_plugin) of every g_fc kernel and bias back
+ * through the training-mode BN, and, if lr != 0, GradientDescentOptimizer(lr)'s w -= lr*g IN PLACE.  g_vars holds only the names with
+ * 'g_' (GAN.py:84): gamma / beta are never written.  gw / gb: optional gradient outputs like cgs_mlp2d_d_step's.  Deterministic.
+ * ws: cgs_mlp2d_gen_ws_bytes(B, nlayers, 1). */
+int cgs_mlp2d_g_step(float* const* w, float* const* b, const float* const* gamma, const float* const* beta, float* const* moving_mean,
+                     float* const* moving_variance, int nlayers, int nhidden, const float* z, const float* grad_plugin, int B, float eps,
+                     float lr, float* const* gw, float* const* gb, float* x, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- discriminator shaping step (the caller after the refinement path: nsgan/GAN.py:270-272, 126-146) ----------
  * Weight gradients of D's layers, the BCE seed with 0/1 targets, and the Adam update.  NOT part of the frozen-weight
  * refinement loop; provided so the method's only training step (shape D on refined samples) runs on the same ABI. */
