@@ -43,28 +43,66 @@ int cgs_get_contraction(void) { return g_contraction; }
 
 }  // extern "C"
 
+// One call of a conv / deconv op as the kernels see it: the layer relation and the direction it is contracted in.  The ONLY place that
+// knows which tensor of an op is the big one (conv: its input side (H, W, Cin); deconv: its output side (Ho, Wo, Cout)) and which ops
+// run small -> big (conv backward-data, deconv forward).  A conv's small side is derived; a deconv's big side is what the caller says
+// (the entry points check it with check_layer; a planning query may take it on trust or pass a bound).
+struct ConvCall { CgsLayer L; bool dirT, deconv, bwd; };
+
+static ConvCall conv_call_of(int op, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw) {
+    ConvCall c;
+    c.deconv = (op == CGS_DECONV_FWD || op == CGS_DECONV_BWD_DATA);
+    c.bwd = (op == CGS_CONV_BWD_DATA || op == CGS_DECONV_BWD_DATA);
+    c.dirT = (op == CGS_CONV_BWD_DATA || op == CGS_DECONV_FWD);
+    CgsLayer& L = c.L;
+    L.kh = kh; L.kw = kw; L.sh = sh; L.sw = sw;
+    // weights are [kh][kw][Cb][Cs]: conv Cb=Cin,Cs=Cout; deconv Cb=Cout,Cs=Cin
+    if (!c.deconv) { L.Hb = H; L.Wb = W; L.Cb = Cin; L.Hs = cgs_ceil_div(H, sh > 0 ? sh : 1); L.Ws = cgs_ceil_div(W, sw > 0 ? sw : 1); L.Cs = Cout; }
+    else { L.Hs = H; L.Ws = W; L.Cs = Cin; L.Hb = Ho; L.Wb = Wo; L.Cb = Cout; }
+    return c;
+}
+
+static int check_layer(const CgsLayer& L, const char* who) {
+    if (L.kh <= 0 || L.kw <= 0 || L.sh <= 0 || L.sw <= 0 || L.Hb <= 0 || L.Wb <= 0 || L.Cb <= 0 || L.Cs <= 0)
+        return cgs_set_error(CGS_EINVAL, "%s: non-positive dimension", who);
+    if (L.Hs != cgs_ceil_div(L.Hb, L.sh) || L.Ws != cgs_ceil_div(L.Wb, L.sw))
+        return cgs_set_error(CGS_EINVAL, "%s: 'SAME' geometry mismatch: big %dx%d stride %dx%d needs small %dx%d, got %dx%d", who,
+                             L.Hb, L.Wb, L.sh, L.sw, cgs_ceil_div(L.Hb, L.sh), cgs_ceil_div(L.Wb, L.sw), L.Hs, L.Ws);
+    return CGS_OK;
+}
+
+// The implicit-GEMM geometry of a call: every member determinate (pointers null, planner fields 0, the ns_* defaults), so it can be
+// handed to the planners of igemm.hip as it is; run_dir adds its pointers.  A transposed launch has sh * sw <= CGS_MAX_CLASSES parity
+// classes: for larger strides (which run_dir refuses and no planner is asked about) the geometry fields stay 0.
+static IgemmParams igemm_geometry(const CgsLayer& L, bool dirT, int B, int epilogue) {
+    IgemmParams p{};
+    p.B = B; p.epilogue = epilogue;
+    if (!dirT) cgs_geom_F(L, p);
+    else if (L.sh <= 2 && L.sw <= 2) cgs_geom_T(L, p);
+    return p;
+}
+
+// one launch addresses its tensors with 32-bit byte offsets: a call splits its batch so each launch stays < 2 GiB
+static size_t in_image_floats(const IgemmParams& p) { return (size_t)p.Hin * p.Win * p.Cred; }
+static size_t out_image_floats(const IgemmParams& p) { return (size_t)p.Hout * p.Wout * p.N; }
+static size_t images_per_launch(const IgemmParams& p) {
+    const size_t in_img = in_image_floats(p) * 4, out_img = out_image_floats(p) * 4;
+    return 0x7fffffffUL / (in_img > out_img ? in_img : out_img);
+}
+static bool whole_batch_in_one_launch(const IgemmParams& p) { return images_per_launch(p) >= (size_t)p.B; }
+
 static bool smalln_ok(const CgsLayer& L, int epilogue) {
     return L.Cb <= 4 && L.sh == 2 && L.sw == 2 && L.Hb == 2 * L.Hs && L.Wb == 2 * L.Ws && (L.Cs % 4) == 0 &&
            epilogue != CGS_EPI_AFFINE_RELU;
 }
 
-static int make_layer(CgsLayer& L, int kh, int kw, int sh, int sw, int Hb, int Wb, int Cb, int Hs, int Ws, int Cs,
-                      const char* who) {
-    if (kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || Hb <= 0 || Wb <= 0 || Cb <= 0 || Cs <= 0)
-        return cgs_set_error(CGS_EINVAL, "%s: non-positive dimension", who);
-    if (Hs != cgs_ceil_div(Hb, sh) || Ws != cgs_ceil_div(Wb, sw))
-        return cgs_set_error(CGS_EINVAL, "%s: 'SAME' geometry mismatch: big %dx%d stride %dx%d needs small %dx%d, got %dx%d", who,
-                             Hb, Wb, sh, sw, cgs_ceil_div(Hb, sh), cgs_ceil_div(Wb, sw), Hs, Ws);
-    L.kh = kh; L.kw = kw; L.sh = sh; L.sw = sw; L.Hb = Hb; L.Wb = Wb; L.Cb = Cb; L.Hs = Hs; L.Ws = Ws; L.Cs = Cs;
-    return CGS_OK;
-}
-
 // Which kernel family (and therefore which packed-weight layout in the workspace) serves a call.  ONE decision function:
 // run_dir() dispatches on it and cgs_conv_family() reports it, so a caller that caches packed workspaces can key them by
 // the family and never hand one family's packed image to another (the epilogue and the pointer alignment take
-// part in the choice, not only the geometry).
-static int choose_family(const CgsLayer& L, bool dirT, int B, int epilogue, bool have_ws, size_t ws_bytes, bool in_al,
-                         bool ws_al, bool rest_al) {
+// part in the choice, not only the geometry).  g = igemm_geometry() of the call (its batch size and epilogue are the call's).
+static int choose_family(const CgsLayer& L, bool dirT, const IgemmParams& g, bool have_ws, size_t ws_bytes, bool in_al, bool ws_al,
+                         bool rest_al) {
+    const int B = g.B, epilogue = g.epilogue;
     if (dirT && smalln_ok(L, epilogue)) {
         if ((L.Cs % 16) == 0 && have_ws && cgs_convt_quad_fits(L)) return CGS_FAMILY_QUAD;
         if (epilogue < CGS_EPI_RELU_BWD_AFFINE) return CGS_FAMILY_SMALLN_T;             // VALU form (any Cs % 4 == 0), packs nothing
@@ -81,38 +119,51 @@ static int choose_family(const CgsLayer& L, bool dirT, int B, int epilogue, bool
     // (... if the workspace can hold its three bf16 weight planes, 6 bytes per weight: an undersized one keeps the fp32 kernel, whose
     // packed image it was sized for, instead of failing with EWORKSPACE -- the patch family above falls back the same way)
     if (g_contraction != CGS_CONTRACTION_F32 && cgs_igemm_bx6_ok(L, dirT, B, g_contraction == CGS_CONTRACTION_BX6_ALL)) {
-        IgemmParams q;
-        q.B = B; q.stat_part = nullptr; q.sign_out = nullptr; q.sign_plane = 0; q.epilogue = epilogue;
-        if (dirT) cgs_geom_T(L, q); else cgs_geom_F(L, q);
-        if (have_ws && ws_bytes >= cgs_igemm_bx6_packed_bytes(q)) return CGS_FAMILY_IGEMM_BX6;
+        if (have_ws && ws_bytes >= cgs_igemm_bx6_packed_bytes(g)) return CGS_FAMILY_IGEMM_BX6;
     }
     return CGS_FAMILY_IGEMM;
 }
 
+// ... as the planning queries ask: a workspace of ws_bytes, every pointer aligned
+static int planned_family(const ConvCall& c, const IgemmParams& g, size_t ws_bytes) { return choose_family(c.L, c.dirT, g, ws_bytes > 0, ws_bytes, true, true, true); }
+
 // norm-backward statistics of a backward-data call (IgemmParams::ns_*; x rides in ep_aux)
 struct NsArgs { const float *mean, *invstd, *gamma, *beta; float leak; int group_images; };
 
-static int run_dir(const CgsLayer& L, bool dirT, int B, const float* in, const float* w, const float* bias, float* out,
-                   int epilogue, const float* ep_a, const float* ep_b, const float* ep_aux, void* ws, size_t ws_bytes,
-                   int prepacked, hipStream_t s, const char* who, float* stat_part = nullptr, unsigned* sign_out = nullptr,
-                   const unsigned* aux_signs = nullptr, const NsArgs* ns = nullptr) {
+// What an entry point passes beside the plain conv arguments.  FORM_STATS (*_fwd_stats): the launch leaves the column sums of its output
+// as partial rows in stat_part; FORM_NSTATS (*_bwd_data_nstats): the norm backward's two column sums, from ns and x_norm (in ep_aux);
+// FORM_SIGNS (*_signs): a forward leaves the sign mask of its output in sign_out, a backward-data takes aux_signs for the fp32 ep_aux.
+enum ConvForm { FORM_PLAIN, FORM_STATS, FORM_NSTATS, FORM_SIGNS };
+struct ConvExtras {
+    ConvForm form = FORM_PLAIN;
+    float* stat_part = nullptr; size_t stat_part_bytes = 0;
+    NsArgs ns = {};
+    unsigned* sign_out = nullptr; const unsigned* aux_signs = nullptr;
+};
+
+static int run_dir(const ConvCall& c, int B, const float* in, const float* w, const float* bias, float* out, int epilogue,
+                   const float* ep_a, const float* ep_b, const float* ep_aux, void* ws, size_t ws_bytes, int prepacked, hipStream_t s,
+                   const char* who, const ConvExtras& x) {
+    const CgsLayer& L = c.L;
+    const bool dirT = c.dirT, nstats = x.form == FORM_NSTATS;
     cgs_note_flops(0.0);
     cgs_note_tail(0, 0);
     if (B <= 0) return cgs_set_error(CGS_EINVAL, "%s: B=%d", who, B);
     if (!in || !w || !out) return cgs_set_error(CGS_EINVAL, "%s: null tensor", who);
     if (epilogue < CGS_EPI_NONE || epilogue > CGS_EPI_TANH_BWD) return cgs_set_error(CGS_EINVAL, "%s: epilogue %d", who, epilogue);
     if (epilogue == CGS_EPI_AFFINE_RELU && (!ep_a || !ep_b)) return cgs_set_error(CGS_EINVAL, "%s: affine epilogue needs a,b", who);
-    if (epilogue >= CGS_EPI_RELU_BWD_AFFINE && ((!ep_aux && !aux_signs) || (epilogue == CGS_EPI_RELU_BWD_AFFINE && !ep_a)))
+    if (epilogue >= CGS_EPI_RELU_BWD_AFFINE && ((!ep_aux && !x.aux_signs) || (epilogue == CGS_EPI_RELU_BWD_AFFINE && !ep_a)))
         return cgs_set_error(CGS_EINVAL, "%s: backward epilogue %d needs aux%s", who, epilogue, epilogue == CGS_EPI_RELU_BWD_AFFINE ? " and a" : "");
     if (dirT && (L.sh > 2 || L.sw > 2)) return cgs_set_error(CGS_EINVAL, "%s: transposed direction supports stride <= 2", who);
     const bool rest_al = !(((uintptr_t)out & 15) || ((uintptr_t)bias & 15) || ((uintptr_t)ep_a & 15) || ((uintptr_t)ep_b & 15) ||
                            ((uintptr_t)ep_aux & 15));
-    const int fam = choose_family(L, dirT, B, epilogue, ws != nullptr, ws_bytes, !((uintptr_t)in & 15), !((uintptr_t)ws & 15), rest_al);
-    if (stat_part && fam != CGS_FAMILY_IGEMM && fam != CGS_FAMILY_IGEMM_BX6) return cgs_set_error(CGS_EINVAL, "%s: fused statistics are an implicit-GEMM feature (see cgs_conv_stat_partials)", who);
-    if (ns && (!stat_part || fam != CGS_FAMILY_IGEMM)) return cgs_set_error(CGS_EINVAL, "%s: norm-backward statistics are a feature of the exact-fp32 implicit GEMM (see cgs_conv_stat_layout)", who);
-    if (sign_out && fam != CGS_FAMILY_IGEMM && fam != CGS_FAMILY_IGEMM_BX6) return cgs_set_error(CGS_EINVAL, "%s: this call cannot leave a sign mask (see cgs_conv_signs_ok)", who);
-    if (aux_signs && fam != CGS_FAMILY_PATCH && fam != CGS_FAMILY_TAPS) return cgs_set_error(CGS_EINVAL, "%s: this call cannot take a sign mask (see cgs_conv_signs_ok)", who);
-    if (((uintptr_t)sign_out & 3) || ((uintptr_t)aux_signs & 3)) return cgs_set_error(CGS_EINVAL, "%s: sign mask must be 4-byte aligned", who);
+    IgemmParams p = igemm_geometry(L, dirT, B, epilogue);
+    const int fam = choose_family(L, dirT, p, ws != nullptr, ws_bytes, !((uintptr_t)in & 15), !((uintptr_t)ws & 15), rest_al);
+    if (x.stat_part && fam != CGS_FAMILY_IGEMM && fam != CGS_FAMILY_IGEMM_BX6) return cgs_set_error(CGS_EINVAL, "%s: fused statistics are an implicit-GEMM feature (see cgs_conv_stat_partials)", who);
+    if (nstats && (!x.stat_part || fam != CGS_FAMILY_IGEMM)) return cgs_set_error(CGS_EINVAL, "%s: norm-backward statistics are a feature of the exact-fp32 implicit GEMM (see cgs_conv_stat_layout)", who);
+    if (x.sign_out && fam != CGS_FAMILY_IGEMM && fam != CGS_FAMILY_IGEMM_BX6) return cgs_set_error(CGS_EINVAL, "%s: this call cannot leave a sign mask (see cgs_conv_signs_ok)", who);
+    if (x.aux_signs && fam != CGS_FAMILY_PATCH && fam != CGS_FAMILY_TAPS) return cgs_set_error(CGS_EINVAL, "%s: this call cannot take a sign mask (see cgs_conv_signs_ok)", who);
+    if (((uintptr_t)x.sign_out & 3) || ((uintptr_t)x.aux_signs & 3)) return cgs_set_error(CGS_EINVAL, "%s: sign mask must be 4-byte aligned", who);
     switch (fam) {
         case CGS_FAMILY_QUAD:
             return cgs_convt_quad_launch(L, B, in, w, bias, out, epilogue, ep_a, ep_aux, (float*)ws, ws_bytes, prepacked, s);
@@ -123,18 +174,16 @@ static int run_dir(const CgsLayer& L, bool dirT, int B, const float* in, const f
         case CGS_FAMILY_DOT:
             return cgs_conv_dot_launch(L, B, in, w, bias, out, epilogue, ep_a, ep_b, s);
         case CGS_FAMILY_TAPS:
-            return cgs_conv_taps_launch(L, B, in, w, bias, out, epilogue, ep_a, ep_b, ep_aux, aux_signs, s);
+            return cgs_conv_taps_launch(L, B, in, w, bias, out, epilogue, ep_a, ep_b, ep_aux, x.aux_signs, s);
         case CGS_FAMILY_PATCH:
-            return cgs_conv_patch_launch(L, dirT, B, in, w, bias, out, epilogue, ep_a, ep_b, ep_aux, (float*)ws, ws_bytes, prepacked, s, aux_signs);
+            return cgs_conv_patch_launch(L, dirT, B, in, w, bias, out, epilogue, ep_a, ep_b, ep_aux, (float*)ws, ws_bytes, prepacked, s, x.aux_signs);
         default: break;
     }
-    IgemmParams p;
-    p.in = in; p.bias = bias; p.ep_a = ep_a; p.ep_b = ep_b; p.ep_aux = ep_aux; p.out = out; p.B = B; p.epilogue = epilogue;
-    p.stat_part = stat_part;
-    if (ns) { p.ns_mean = ns->mean; p.ns_inv = ns->invstd; p.ns_gamma = ns->gamma; p.ns_beta = ns->beta; p.ns_leak = ns->leak; p.ns_gimg = ns->group_images >= B ? 0 : ns->group_images; }
-    p.sign_out = sign_out;
+    p.in = in; p.bias = bias; p.ep_a = ep_a; p.ep_b = ep_b; p.ep_aux = ep_aux; p.out = out;
+    p.stat_part = x.stat_part;
+    if (nstats) { p.ns_mean = x.ns.mean; p.ns_inv = x.ns.invstd; p.ns_gamma = x.ns.gamma; p.ns_beta = x.ns.beta; p.ns_leak = x.ns.leak; p.ns_gimg = x.ns.group_images >= B ? 0 : x.ns.group_images; }
+    p.sign_out = x.sign_out;
     p.sign_plane = (long)B * (dirT ? L.Hb * L.Wb : L.Hs * L.Ws);
-    if (dirT) cgs_geom_T(L, p); else cgs_geom_F(L, p);
     const bool bx6 = fam == CGS_FAMILY_IGEMM_BX6;
     const size_t need = bx6 ? cgs_igemm_bx6_packed_bytes(p) : cgs_packed_floats(p) * sizeof(float);
     if (!ws || ws_bytes < need) return cgs_set_error(CGS_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
@@ -146,70 +195,85 @@ static int run_dir(const CgsLayer& L, bool dirT, int B, const float* in, const f
         int rc = bx6 ? cgs_pack_weights_bx6(p, L, dirT, w, ws, s) : cgs_pack_weights(p, L, dirT, w, (float*)ws, s);
         if (rc) return rc;
     }
-    // one launch addresses its tensors with 32-bit byte offsets: split the batch so each stays < 2 GiB
-    const size_t in_img = (size_t)p.Hin * p.Win * p.Cred * 4, out_img = (size_t)p.Hout * p.Wout * p.N * 4;
-    const size_t per = in_img > out_img ? in_img : out_img;
-    long chunk = (long)(0x7fffffffUL / per);
+    const size_t chunk = images_per_launch(p), in_img = in_image_floats(p), out_img = out_image_floats(p);
     if (chunk < 1) return cgs_set_error(CGS_EINVAL, "%s: one image exceeds 2 GiB", who);
-    if (stat_part && chunk < B) return cgs_set_error(CGS_EINVAL, "%s: fused statistics need the batch in one launch", who);
-    for (long b0 = 0; b0 < B; b0 += chunk) {
+    if (x.stat_part && !whole_batch_in_one_launch(p)) return cgs_set_error(CGS_EINVAL, "%s: fused statistics need the batch in one launch", who);
+    for (size_t b0 = 0; b0 < (size_t)B; b0 += chunk) {
         p.B = (int)(B - b0 < chunk ? B - b0 : chunk);
-        p.in = in + (size_t)b0 * (in_img / 4);
-        p.out = out + (size_t)b0 * (out_img / 4);
-        p.ep_aux = ep_aux ? ep_aux + (size_t)b0 * (out_img / 4) : nullptr;
-        p.sign_out = sign_out ? sign_out + (size_t)b0 * p.Hout * p.Wout : nullptr;      // (plane-major: the chunk's pixels inside every plane)
+        p.in = in + b0 * in_img;
+        p.out = out + b0 * out_img;
+        p.ep_aux = ep_aux ? ep_aux + b0 * out_img : nullptr;
+        p.sign_out = x.sign_out ? x.sign_out + b0 * p.Hout * p.Wout : nullptr;      // (plane-major: the chunk's pixels inside every plane)
         int rc = bx6 ? cgs_igemm_bx6_launch(p, s) : cgs_igemm_launch(p, (char*)ws + need, ws_bytes - need, s);
         if (rc) return rc;
     }
     return CGS_OK;
 }
 
+// cgs_conv_family's answer (< 0: bad argument) with, for cgs_conv_signs_ok, the call and the geometry it was decided on
+struct ConvPlan { int fam; ConvCall c; IgemmParams g; };
+
+static ConvPlan conv_plan_of(int op, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw, int epilogue,
+                             size_t ws_bytes) {
+    ConvPlan q{};
+    if (op < CGS_CONV_FWD || op > CGS_DECONV_BWD_DATA || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 ||
+        sh <= 0 || sw <= 0) {
+        q.fam = cgs_set_error(CGS_EINVAL, "conv_family: bad argument");
+    } else {
+        q.c = conv_call_of(op, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw);
+        q.g = igemm_geometry(q.c.L, q.c.dirT, B, epilogue);
+        q.fam = planned_family(q.c, q.g, ws_bytes);
+    }
+    return q;
+}
+
+// The norm-backward arguments of a *_bwd_data_nstats call: the backward-data of a conv / deconv whose result is the gradient w.r.t. the
+// OUTPUT of a norm (+ lrelu) over x_norm (same shape as the result): the launch also leaves the norm backward's two column sums as
+// partial rows (cgs_conv_stat_layout with the *_BWD_DATA op says where a group's rows lie; cgs_norm_lrelu_bwd_from_partials consumes
+// them).  The result itself is the plain backward-data (no epilogue).
+static int nstats_check(const char* who, const float* x_norm, const NsArgs& ns, const float* stat_part) {
+    if (!x_norm || !ns.mean || !ns.invstd || !ns.gamma || !ns.beta) return cgs_set_error(CGS_EINVAL, "%s: null statistics argument", who);
+    if (((uintptr_t)x_norm | (uintptr_t)ns.mean | (uintptr_t)ns.invstd | (uintptr_t)ns.gamma | (uintptr_t)ns.beta | (uintptr_t)stat_part) & 15)
+        return cgs_set_error(CGS_EINVAL, "%s: pointers must be 16-byte aligned", who);
+    return CGS_OK;
+}
+
+// The body of every conv / deconv / linear entry point: resolve the op, check what the form adds, dispatch.
+static int conv_entry(const char* who, int op, const float* in, const float* w, const float* bias, float* out, int B, int H, int W, int Cin,
+                      int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw, int epilogue, const float* ep_a, const float* ep_b,
+                      const float* ep_aux, void* ws, size_t ws_bytes, int prepacked, void* stream, const ConvExtras& x = ConvExtras()) {
+    const ConvCall c = conv_call_of(op, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw);
+    if (x.form == FORM_SIGNS) {
+        if (!x.sign_out && !x.aux_signs) return cgs_set_error(CGS_EINVAL, "%s: null sign mask", who);
+        if (!cgs_conv_signs_ok(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, ws_bytes))
+            return cgs_set_error(CGS_EINVAL, "%s: not available for this call (cgs_conv_signs_ok == 0)", who);
+    }
+    if (x.form == FORM_PLAIN && c.bwd && epilogue != CGS_EPI_NONE && epilogue < CGS_EPI_RELU_BWD_AFFINE)
+        return cgs_set_error(CGS_EINVAL, "%s: epilogue %d", who, epilogue);
+    int rc = check_layer(c.L, who);
+    if (rc) return rc;
+    if (x.form == FORM_STATS || x.form == FORM_NSTATS) {
+        const bool conv_fwd = x.form == FORM_STATS && !c.deconv;          // (has a query of its own; the other three ask for the layout)
+        int a, b, d;
+        const int G = conv_fwd ? cgs_conv_stat_partials(B, H, W, Cin, Cout, kh, kw, sh, sw, ws_bytes)
+                               : cgs_conv_stat_layout(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, x.form == FORM_NSTATS ? x.ns.group_images : B,
+                                                      ws_bytes, &a, &b, &d);
+        if (G == 0) return cgs_set_error(CGS_EINVAL, "%s: not available for this call (%s == 0)", who, conv_fwd ? "cgs_conv_stat_partials" : "cgs_conv_stat_layout");
+        if (x.form == FORM_NSTATS && (rc = nstats_check(who, ep_aux, x.ns, x.stat_part))) return rc;
+        const size_t need = (size_t)G * 2 * (c.bwd ? Cin : Cout) * sizeof(float);        // [rows][2][channels of the tensor the launch writes]
+        if (!x.stat_part || x.stat_part_bytes < need) return cgs_set_error(CGS_EWORKSPACE, "%s: partials buffer %zu < %zu bytes", who, x.stat_part_bytes, need);
+        if ((uintptr_t)x.stat_part & 15) return cgs_set_error(CGS_EINVAL, "%s: partials buffer must be 16-byte aligned", who);
+    }
+    return run_dir(c, B, in, w, bias, out, epilogue, ep_a, ep_b, ep_aux, ws, ws_bytes, prepacked, (hipStream_t)stream, who, x);
+}
+
 extern "C" {
 
-static size_t conv_packed_bytes(int op, int kh, int kw, int sh, int sw, int Cin, int Cout);
-
 size_t cgs_conv_ws_bytes(int op, int kh, int kw, int sh, int sw, int Cin, int Cout) {
-    return conv_packed_bytes(op, kh, kw, sh, sw, Cin, Cout);
-}
-
-size_t cgs_conv_ws_bytes_for(int op, int B, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw) {
-    const size_t packed = conv_packed_bytes(op, kh, kw, sh, sw, Cin, Cout);
-    if (B <= 0 || H <= 0 || W <= 0 || packed == 0) return packed;
-    // H, W are the op's INPUT spatial size for conv fwd / deconv fwd and for their backward-datas the size of
-    // the tensor the gradient is taken w.r.t. (the arguments of the entry points)
-    const bool deconv = (op == CGS_DECONV_FWD || op == CGS_DECONV_BWD_DATA);
-    const bool dirT = (op == CGS_CONV_BWD_DATA || op == CGS_DECONV_FWD);
-    CgsLayer L;
-    L.kh = kh; L.kw = kw; L.sh = sh; L.sw = sw;
-    if (!deconv) { L.Hb = H; L.Wb = W; L.Cb = Cin; L.Hs = cgs_ceil_div(H, sh); L.Ws = cgs_ceil_div(W, sw); L.Cs = Cout; }
-    else { L.Hs = H; L.Ws = W; L.Cs = Cin; L.Hb = H * sh; L.Wb = W * sw; L.Cb = Cout; }   // bound: output = stride * input
-    if (dirT && (sh > 2 || sw > 2)) return packed;
-    IgemmParams p;
-    p.B = B; p.stat_part = nullptr; p.sign_out = nullptr; p.sign_plane = 0;
-    if (dirT) cgs_geom_T(L, p); else cgs_geom_F(L, p);
-    return packed + cgs_igemm_slab_bytes(p);
-}
-
-int cgs_conv_family(int op, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw, int epilogue,
-                    size_t ws_bytes) {
-    if (op < CGS_CONV_FWD || op > CGS_DECONV_BWD_DATA || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 ||
-        sh <= 0 || sw <= 0)
-        return cgs_set_error(CGS_EINVAL, "conv_family: bad argument");
-    const bool deconv = (op == CGS_DECONV_FWD || op == CGS_DECONV_BWD_DATA);
-    const bool dirT = (op == CGS_CONV_BWD_DATA || op == CGS_DECONV_FWD);
-    CgsLayer L;
-    L.kh = kh; L.kw = kw; L.sh = sh; L.sw = sw;
-    if (!deconv) { L.Hb = H; L.Wb = W; L.Cb = Cin; L.Hs = cgs_ceil_div(H, sh); L.Ws = cgs_ceil_div(W, sw); L.Cs = Cout; }
-    else { L.Hs = H; L.Ws = W; L.Cs = Cin; L.Hb = Ho; L.Wb = Wo; L.Cb = Cout; }
-    return choose_family(L, dirT, B, epilogue, ws_bytes > 0, ws_bytes, true, true, true);
-}
-
-static size_t conv_packed_bytes(int op, int kh, int kw, int sh, int sw, int Cin, int Cout) {
     if (kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || Cin <= 0 || Cout <= 0) return 0;
-    // weights are [kh][kw][Cb][Cs]: conv Cb=Cin,Cs=Cout; deconv Cb=Cout,Cs=Cin
-    const bool deconv = (op == CGS_DECONV_FWD || op == CGS_DECONV_BWD_DATA);
-    const bool dirT = (op == CGS_CONV_BWD_DATA || op == CGS_DECONV_FWD);
-    const int Cb = deconv ? Cout : Cin, Cs = deconv ? Cin : Cout;
+    const ConvCall c = conv_call_of(op, 0, 0, Cin, 0, 0, Cout, kh, kw, sh, sw);       // (independent of the spatial size)
+    const int Cb = c.L.Cb, Cs = c.L.Cs;
+    const bool dirT = c.dirT;
     // (the split-bf16 form keeps three bf16 planes = 6 bytes per weight: sized for it wherever its geometry applies, whatever the
     // calling thread's contraction mode, so a workspace serves both)
     const int Cred = dirT ? Cs : Cb, Nn = dirT ? Cb : Cs;
@@ -229,23 +293,29 @@ static size_t conv_packed_bytes(int op, int kh, int kw, int sh, int sw, int Cin,
     return n * (per_w > sizeof(float) && !(Cb <= 4 && sh == 2 && sw == 2) ? per_w : sizeof(float));
 }
 
-int cgs_conv2d_nhwc_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
-                        int Cout, int kh, int kw, int sh, int sw, int epilogue, const float* ep_a, const float* ep_b,
-                        void* ws, size_t ws_bytes, int ws_prepacked, void* stream) {
-    CgsLayer L;
-    int rc = make_layer(L, kh, kw, sh, sw, H, W, Cin, cgs_ceil_div(H, sh > 0 ? sh : 1), cgs_ceil_div(W, sw > 0 ? sw : 1), Cout, "conv2d_nhwc_fwd");
-    if (rc) return rc;
-    return run_dir(L, false, B, x, w, bias, y, epilogue, ep_a, ep_b, nullptr, ws, ws_bytes, ws_prepacked, (hipStream_t)stream, "conv2d_nhwc_fwd");
+size_t cgs_conv_ws_bytes_for(int op, int B, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw) {
+    const size_t packed = cgs_conv_ws_bytes(op, kh, kw, sh, sw, Cin, Cout);
+    if (B <= 0 || H <= 0 || W <= 0 || packed == 0) return packed;
+    // H, W are the op's INPUT spatial size for conv fwd / deconv fwd and for their backward-datas the size of
+    // the tensor the gradient is taken w.r.t. (the arguments of the entry points); a deconv's output is bounded by stride * input
+    const ConvCall c = conv_call_of(op, H, W, Cin, H * sh, W * sw, Cout, kh, kw, sh, sw);
+    if (c.dirT && (sh > 2 || sw > 2)) return packed;
+    return packed + cgs_igemm_slab_bytes(igemm_geometry(c.L, c.dirT, B, CGS_EPI_NONE));
+}
+
+int cgs_conv_family(int op, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw, int epilogue,
+                    size_t ws_bytes) {
+    return conv_plan_of(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, ws_bytes).fam;
 }
 
 int cgs_conv_stat_partials(int B, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, size_t ws_bytes) {
-    CgsLayer L;
-    if (make_layer(L, kh, kw, sh, sw, H, W, Cin, cgs_ceil_div(H, sh > 0 ? sh : 1), cgs_ceil_div(W, sw > 0 ? sw : 1), Cout, "conv_stat_partials")) return 0;
-    const int fam = choose_family(L, false, B, CGS_EPI_NONE, ws_bytes > 0, ws_bytes, true, true, true);
+    const ConvCall c = conv_call_of(CGS_CONV_FWD, H, W, Cin, 0, 0, Cout, kh, kw, sh, sw);
+    if (check_layer(c.L, "conv_stat_partials")) return 0;
+    const IgemmParams g = igemm_geometry(c.L, c.dirT, B, CGS_EPI_NONE);
+    const int fam = planned_family(c, g, ws_bytes);
     if (B <= 0 || (Cout & 3) || (fam != CGS_FAMILY_IGEMM && fam != CGS_FAMILY_IGEMM_BX6)) return 0;       // (both leave the same partial rows)
-    const size_t per = (size_t)(L.Hb * L.Wb * L.Cb > L.Hs * L.Ws * L.Cs ? L.Hb * L.Wb * L.Cb : L.Hs * L.Ws * L.Cs) * 4;
-    if ((size_t)B * per > 0x7fffffffUL) return 0;                    // the entry point would split the batch
-    const long M = (long)B * L.Hs * L.Ws;
+    if (!whole_batch_in_one_launch(g)) return 0;                     // the entry point would split the batch
+    const long M = (long)B * c.L.Hs * c.L.Ws;
     return (int)(2 * ((M + 127) / 128));                             // one partial row per (128-row tile, wave row)
 }
 
@@ -257,22 +327,16 @@ int cgs_conv_stat_layout(int op, int B, int H, int W, int Cin, int Ho, int Wo, i
                          size_t ws_bytes, int* rows_per_seg, int* nseg, int* seg_stride) {
     if (op < CGS_CONV_FWD || op > CGS_DECONV_BWD_DATA || B <= 0 || group_images <= 0 || (B % group_images) || !rows_per_seg || !nseg || !seg_stride)
         return 0;
-    // the launch's direction and the channel count of the tensor it WRITES (the statistics' columns): the forward ops write Cout channels,
-    // the backward-data ops (norm-backward statistics, cgs_*_bwd_data_nstats) the gradient w.r.t. their input: Cin channels
-    const bool deconv = (op == CGS_DECONV_FWD || op == CGS_DECONV_BWD_DATA), bwd = (op == CGS_CONV_BWD_DATA || op == CGS_DECONV_BWD_DATA);
-    const bool dirT = (op == CGS_CONV_BWD_DATA || op == CGS_DECONV_FWD);
-    if ((bwd ? Cin : Cout) & 3) return 0;
-    CgsLayer L;
-    if (!deconv) { if (make_layer(L, kh, kw, sh, sw, H, W, Cin, cgs_ceil_div(H, sh > 0 ? sh : 1), cgs_ceil_div(W, sw > 0 ? sw : 1), Cout, "conv_stat_layout")) return 0; }
-    else if (make_layer(L, kh, kw, sh, sw, Ho, Wo, Cout, H, W, Cin, "conv_stat_layout")) return 0;
-    if (dirT && (sh > 2 || sw > 2)) return 0;
-    const int fam = choose_family(L, dirT, B, CGS_EPI_NONE, ws_bytes > 0, ws_bytes, true, true, true);
-    if (fam != CGS_FAMILY_IGEMM && (bwd || fam != CGS_FAMILY_IGEMM_BX6)) return 0;           // (the backward sums: the exact-fp32 kernel only)
-    const size_t per = (size_t)(L.Hb * L.Wb * L.Cb > L.Hs * L.Ws * L.Cs ? L.Hb * L.Wb * L.Cb : L.Hs * L.Ws * L.Cs) * 4;
-    if ((size_t)B * per > 0x7fffffffUL) return 0;                    // the entry point would split the batch
-    IgemmParams p;
-    p.B = B; p.stat_part = nullptr; p.sign_out = nullptr; p.sign_plane = 0; p.epilogue = CGS_EPI_NONE;
-    if (dirT) cgs_geom_T(L, p); else cgs_geom_F(L, p);
+    const ConvCall c = conv_call_of(op, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw);
+    // the channel count of the tensor the launch WRITES (the statistics' columns): the forward ops write Cout channels, the backward-data
+    // ops (norm-backward statistics, cgs_*_bwd_data_nstats) the gradient w.r.t. their input: Cin channels
+    if ((c.bwd ? Cin : Cout) & 3) return 0;
+    if (check_layer(c.L, "conv_stat_layout")) return 0;
+    if (c.dirT && (sh > 2 || sw > 2)) return 0;
+    const IgemmParams p = igemm_geometry(c.L, c.dirT, B, CGS_EPI_NONE);
+    const int fam = planned_family(c, p, ws_bytes);
+    if (fam != CGS_FAMILY_IGEMM && (c.bwd || fam != CGS_FAMILY_IGEMM_BX6)) return 0;         // (the backward sums: the exact-fp32 kernel only)
+    if (!whole_batch_in_one_launch(p)) return 0;                     // the entry point would split the batch
     const int RC = p.cls[0].R * p.cls[0].C;
     for (int i = 1; i < p.nclasses; ++i)
         if (p.cls[i].R * p.cls[i].C != RC) return 0;                 // (odd output sizes: parity classes of different size)
@@ -297,159 +361,93 @@ int cgs_conv_stat_layout(int op, int B, int H, int W, int Cin, int Ho, int Wo, i
     return (int)(cls_rows * p.nclasses);
 }
 
-// Backward-data of a conv / deconv whose result is the gradient w.r.t. the OUTPUT of a norm (+ lrelu) over x_norm (same shape as the
-// result): the launch also leaves the norm backward's two column sums as partial rows (cgs_conv_stat_layout with the *_BWD_DATA op says
-// where a group's rows lie; cgs_norm_lrelu_bwd_from_partials consumes them).  The result itself is the plain backward-data (no epilogue).
-static int nstats_check(const char* who, int G, int C, const float* x_norm, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                        float* stat_part, size_t stat_part_bytes) {
-    if (G == 0) return cgs_set_error(CGS_EINVAL, "%s: not available for this call (cgs_conv_stat_layout == 0)", who);
-    if (!x_norm || !mean || !invstd || !gamma || !beta) return cgs_set_error(CGS_EINVAL, "%s: null statistics argument", who);
-    if (((uintptr_t)x_norm | (uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)stat_part) & 15)
-        return cgs_set_error(CGS_EINVAL, "%s: pointers must be 16-byte aligned", who);
-    if (!stat_part || stat_part_bytes < (size_t)G * 2 * C * sizeof(float))
-        return cgs_set_error(CGS_EWORKSPACE, "%s: partials buffer %zu < %zu bytes", who, stat_part_bytes, (size_t)G * 2 * C * sizeof(float));
-    return CGS_OK;
+// ---- sign masks (cgs_hip.h): the activation gradient of relu / lrelu needs one bit per element of the saved activation ----
+int cgs_conv_signs_ok(int op, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw, int epilogue,
+                      size_t ws_bytes) {
+    const ConvPlan q = conv_plan_of(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, ws_bytes);
+    const int fam = q.fam;
+    if (fam < 0) return 0;
+    if (epilogue >= CGS_EPI_RELU_BWD_AFFINE)          // consumer: a backward-data whose epilogue applies relu' / lrelu'
+        return (fam == CGS_FAMILY_PATCH && cgs_conv_patch_signs_ok(q.c.L, q.c.dirT, epilogue)) || (fam == CGS_FAMILY_TAPS && cgs_conv_taps_signs_ok(q.c.L, epilogue));
+    if (fam == CGS_FAMILY_IGEMM_BX6)            // producer on the split-bf16 kernel: whole 64-column wave tiles, never split over K
+        return (epilogue == CGS_EPI_AFFINE_RELU || epilogue == CGS_EPI_LRELU) && whole_batch_in_one_launch(q.g);
+    if (fam != CGS_FAMILY_IGEMM || (q.c.dirT && (sh > 2 || sw > 2))) return 0;    // producer: a forward with the relu / lrelu epilogue
+    if (!whole_batch_in_one_launch(q.g)) return 0;                                // (a split batch may fall under the split-K threshold)
+    return cgs_igemm_signs_ok(q.g);
+}
+
+int cgs_conv2d_nhwc_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
+                        int Cout, int kh, int kw, int sh, int sw, int epilogue, const float* ep_a, const float* ep_b,
+                        void* ws, size_t ws_bytes, int ws_prepacked, void* stream) {
+    return conv_entry("conv2d_nhwc_fwd", CGS_CONV_FWD, x, w, bias, y, B, H, W, Cin, 0, 0, Cout, kh, kw, sh, sw, epilogue, ep_a, ep_b, nullptr, ws, ws_bytes,
+                      ws_prepacked, stream);
+}
+
+int cgs_conv2d_nhwc_bwd_data(const float* dy, const float* w, float* dx, int B, int H, int W, int Cin, int Cout, int kh,
+                             int kw, int sh, int sw, int epilogue, const float* ep_a, const float* ep_aux, void* ws,
+                             size_t ws_bytes, int ws_prepacked, void* stream) {
+    return conv_entry("conv2d_nhwc_bwd_data", CGS_CONV_BWD_DATA, dy, w, nullptr, dx, B, H, W, Cin, 0, 0, Cout, kh, kw, sh, sw, epilogue, ep_a, nullptr, ep_aux, ws,
+                      ws_bytes, ws_prepacked, stream);
+}
+
+int cgs_deconv2d_nhwc_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
+                          int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw, int epilogue, const float* ep_a,
+                          const float* ep_b, void* ws, size_t ws_bytes, int ws_prepacked, void* stream) {
+    return conv_entry("deconv2d_nhwc_fwd", CGS_DECONV_FWD, x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, ep_a, ep_b, nullptr, ws, ws_bytes,
+                      ws_prepacked, stream);
+}
+
+int cgs_deconv2d_nhwc_bwd_data(const float* dy, const float* w, float* dx, int B, int H, int W, int Cin, int Ho, int Wo,
+                               int Cout, int kh, int kw, int sh, int sw, int epilogue, const float* ep_a,
+                               const float* ep_aux, void* ws, size_t ws_bytes, int ws_prepacked, void* stream) {
+    return conv_entry("deconv2d_nhwc_bwd_data", CGS_DECONV_BWD_DATA, dy, w, nullptr, dx, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, ep_a, nullptr, ep_aux,
+                      ws, ws_bytes, ws_prepacked, stream);
+}
+
+int cgs_conv2d_nhwc_fwd_stats(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
+                              int Cout, int kh, int kw, int sh, int sw, void* ws, size_t ws_bytes, int ws_prepacked,
+                              float* stat_part, size_t stat_part_bytes, void* stream) {
+    return conv_entry("conv2d_nhwc_fwd_stats", CGS_CONV_FWD, x, w, bias, y, B, H, W, Cin, 0, 0, Cout, kh, kw, sh, sw, CGS_EPI_NONE, nullptr, nullptr, nullptr, ws,
+                      ws_bytes, ws_prepacked, stream, ConvExtras{FORM_STATS, stat_part, stat_part_bytes});
+}
+
+int cgs_deconv2d_nhwc_fwd_stats(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin, int Ho, int Wo,
+                                int Cout, int kh, int kw, int sh, int sw, void* ws, size_t ws_bytes, int ws_prepacked, float* stat_part,
+                                size_t stat_part_bytes, void* stream) {
+    return conv_entry("deconv2d_nhwc_fwd_stats", CGS_DECONV_FWD, x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, CGS_EPI_NONE, nullptr, nullptr, nullptr,
+                      ws, ws_bytes, ws_prepacked, stream, ConvExtras{FORM_STATS, stat_part, stat_part_bytes});
 }
 
 int cgs_conv2d_nhwc_bwd_data_nstats(const float* dy, const float* w, float* dx, int B, int H, int W, int Cin, int Cout, int kh, int kw, int sh,
                                     int sw, const float* x_norm, const float* mean, const float* invstd, const float* gamma, const float* beta,
                                     float leak, int group_images, void* ws, size_t ws_bytes, int ws_prepacked, float* stat_part,
                                     size_t stat_part_bytes, void* stream) {
-    CgsLayer L;
-    int rc = make_layer(L, kh, kw, sh, sw, H, W, Cin, cgs_ceil_div(H, sh > 0 ? sh : 1), cgs_ceil_div(W, sw > 0 ? sw : 1), Cout, "conv2d_nhwc_bwd_data_nstats");
-    if (rc) return rc;
-    int a, b, c;
-    const int G = cgs_conv_stat_layout(CGS_CONV_BWD_DATA, B, H, W, Cin, 0, 0, Cout, kh, kw, sh, sw, group_images, ws_bytes, &a, &b, &c);
-    if ((rc = nstats_check("conv2d_nhwc_bwd_data_nstats", G, Cin, x_norm, mean, invstd, gamma, beta, stat_part, stat_part_bytes))) return rc;
-    const NsArgs ns{mean, invstd, gamma, beta, leak, group_images};
-    return run_dir(L, true, B, dy, w, nullptr, dx, CGS_EPI_NONE, nullptr, nullptr, x_norm, ws, ws_bytes, ws_prepacked, (hipStream_t)stream,
-                   "conv2d_nhwc_bwd_data_nstats", stat_part, nullptr, nullptr, &ns);
+    return conv_entry("conv2d_nhwc_bwd_data_nstats", CGS_CONV_BWD_DATA, dy, w, nullptr, dx, B, H, W, Cin, 0, 0, Cout, kh, kw, sh, sw, CGS_EPI_NONE, nullptr, nullptr,
+                      x_norm, ws, ws_bytes, ws_prepacked, stream, ConvExtras{FORM_NSTATS, stat_part, stat_part_bytes, NsArgs{mean, invstd, gamma, beta, leak,
+                      group_images}});
 }
 
 int cgs_deconv2d_nhwc_bwd_data_nstats(const float* dy, const float* w, float* dx, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh,
                                       int kw, int sh, int sw, const float* x_norm, const float* mean, const float* invstd, const float* gamma,
                                       const float* beta, float leak, int group_images, void* ws, size_t ws_bytes, int ws_prepacked,
                                       float* stat_part, size_t stat_part_bytes, void* stream) {
-    CgsLayer L;
-    int rc = make_layer(L, kh, kw, sh, sw, Ho, Wo, Cout, H, W, Cin, "deconv2d_nhwc_bwd_data_nstats");
-    if (rc) return rc;
-    int a, b, c;
-    const int G = cgs_conv_stat_layout(CGS_DECONV_BWD_DATA, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, group_images, ws_bytes, &a, &b, &c);
-    if ((rc = nstats_check("deconv2d_nhwc_bwd_data_nstats", G, Cin, x_norm, mean, invstd, gamma, beta, stat_part, stat_part_bytes))) return rc;
-    const NsArgs ns{mean, invstd, gamma, beta, leak, group_images};
-    return run_dir(L, false, B, dy, w, nullptr, dx, CGS_EPI_NONE, nullptr, nullptr, x_norm, ws, ws_bytes, ws_prepacked, (hipStream_t)stream,
-                   "deconv2d_nhwc_bwd_data_nstats", stat_part, nullptr, nullptr, &ns);
-}
-
-int cgs_deconv2d_nhwc_fwd_stats(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin, int Ho, int Wo,
-                                int Cout, int kh, int kw, int sh, int sw, void* ws, size_t ws_bytes, int ws_prepacked, float* stat_part,
-                                size_t stat_part_bytes, void* stream) {
-    CgsLayer L;
-    int rc = make_layer(L, kh, kw, sh, sw, Ho, Wo, Cout, H, W, Cin, "deconv2d_nhwc_fwd_stats");
-    if (rc) return rc;
-    int a, b, c;
-    const int G = cgs_conv_stat_layout(CGS_DECONV_FWD, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, B, ws_bytes, &a, &b, &c);
-    if (G == 0) return cgs_set_error(CGS_EINVAL, "deconv2d_nhwc_fwd_stats: not available for this call (cgs_conv_stat_layout == 0)");
-    if (!stat_part || stat_part_bytes < (size_t)G * 2 * Cout * sizeof(float))
-        return cgs_set_error(CGS_EWORKSPACE, "deconv2d_nhwc_fwd_stats: partials buffer %zu < %zu bytes", stat_part_bytes, (size_t)G * 2 * Cout * sizeof(float));
-    if ((uintptr_t)stat_part & 15) return cgs_set_error(CGS_EINVAL, "deconv2d_nhwc_fwd_stats: partials buffer must be 16-byte aligned");
-    return run_dir(L, true, B, x, w, bias, y, CGS_EPI_NONE, nullptr, nullptr, nullptr, ws, ws_bytes, ws_prepacked, (hipStream_t)stream,
-                   "deconv2d_nhwc_fwd_stats", stat_part);
-}
-
-int cgs_conv2d_nhwc_fwd_stats(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
-                              int Cout, int kh, int kw, int sh, int sw, void* ws, size_t ws_bytes, int ws_prepacked,
-                              float* stat_part, size_t stat_part_bytes, void* stream) {
-    CgsLayer L;
-    int rc = make_layer(L, kh, kw, sh, sw, H, W, Cin, cgs_ceil_div(H, sh > 0 ? sh : 1), cgs_ceil_div(W, sw > 0 ? sw : 1), Cout, "conv2d_nhwc_fwd_stats");
-    if (rc) return rc;
-    const int G = cgs_conv_stat_partials(B, H, W, Cin, Cout, kh, kw, sh, sw, ws_bytes);
-    if (G == 0) return cgs_set_error(CGS_EINVAL, "conv2d_nhwc_fwd_stats: not available for this call (cgs_conv_stat_partials == 0)");
-    if (!stat_part || stat_part_bytes < (size_t)G * 2 * Cout * sizeof(float))
-        return cgs_set_error(CGS_EWORKSPACE, "conv2d_nhwc_fwd_stats: partials buffer %zu < %zu bytes", stat_part_bytes, (size_t)G * 2 * Cout * sizeof(float));
-    if ((uintptr_t)stat_part & 15) return cgs_set_error(CGS_EINVAL, "conv2d_nhwc_fwd_stats: partials buffer must be 16-byte aligned");
-    return run_dir(L, false, B, x, w, bias, y, CGS_EPI_NONE, nullptr, nullptr, nullptr, ws, ws_bytes, ws_prepacked, (hipStream_t)stream,
-                   "conv2d_nhwc_fwd_stats", stat_part);
-}
-
-int cgs_conv2d_nhwc_bwd_data(const float* dy, const float* w, float* dx, int B, int H, int W, int Cin, int Cout, int kh,
-                             int kw, int sh, int sw, int epilogue, const float* ep_a, const float* ep_aux, void* ws,
-                             size_t ws_bytes, int ws_prepacked, void* stream) {
-    if (epilogue != CGS_EPI_NONE && epilogue < CGS_EPI_RELU_BWD_AFFINE) return cgs_set_error(CGS_EINVAL, "conv2d_nhwc_bwd_data: epilogue %d", epilogue);
-    CgsLayer L;
-    int rc = make_layer(L, kh, kw, sh, sw, H, W, Cin, cgs_ceil_div(H, sh > 0 ? sh : 1), cgs_ceil_div(W, sw > 0 ? sw : 1), Cout, "conv2d_nhwc_bwd_data");
-    if (rc) return rc;
-    return run_dir(L, true, B, dy, w, nullptr, dx, epilogue, ep_a, nullptr, ep_aux, ws, ws_bytes, ws_prepacked, (hipStream_t)stream, "conv2d_nhwc_bwd_data");
-}
-
-int cgs_deconv2d_nhwc_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
-                          int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw, int epilogue, const float* ep_a,
-                          const float* ep_b, void* ws, size_t ws_bytes, int ws_prepacked, void* stream) {
-    CgsLayer L;
-    int rc = make_layer(L, kh, kw, sh, sw, Ho, Wo, Cout, H, W, Cin, "deconv2d_nhwc_fwd");
-    if (rc) return rc;
-    return run_dir(L, true, B, x, w, bias, y, epilogue, ep_a, ep_b, nullptr, ws, ws_bytes, ws_prepacked, (hipStream_t)stream, "deconv2d_nhwc_fwd");
-}
-
-int cgs_deconv2d_nhwc_bwd_data(const float* dy, const float* w, float* dx, int B, int H, int W, int Cin, int Ho, int Wo,
-                               int Cout, int kh, int kw, int sh, int sw, int epilogue, const float* ep_a,
-                               const float* ep_aux, void* ws, size_t ws_bytes, int ws_prepacked, void* stream) {
-    if (epilogue != CGS_EPI_NONE && epilogue < CGS_EPI_RELU_BWD_AFFINE) return cgs_set_error(CGS_EINVAL, "deconv2d_nhwc_bwd_data: epilogue %d", epilogue);
-    CgsLayer L;
-    int rc = make_layer(L, kh, kw, sh, sw, Ho, Wo, Cout, H, W, Cin, "deconv2d_nhwc_bwd_data");
-    if (rc) return rc;
-    return run_dir(L, false, B, dy, w, nullptr, dx, epilogue, ep_a, nullptr, ep_aux, ws, ws_bytes, ws_prepacked, (hipStream_t)stream, "deconv2d_nhwc_bwd_data");
-}
-
-// ---- sign masks (cgs_hip.h): the activation gradient of relu / lrelu needs one bit per element of the saved activation ----
-int cgs_conv_signs_ok(int op, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw, int epilogue,
-                      size_t ws_bytes) {
-    const int fam = cgs_conv_family(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, ws_bytes);
-    if (fam < 0) return 0;
-    const bool deconv = (op == CGS_DECONV_FWD || op == CGS_DECONV_BWD_DATA);
-    const bool dirT = (op == CGS_CONV_BWD_DATA || op == CGS_DECONV_FWD);
-    CgsLayer L;
-    L.kh = kh; L.kw = kw; L.sh = sh; L.sw = sw;
-    if (!deconv) { L.Hb = H; L.Wb = W; L.Cb = Cin; L.Hs = cgs_ceil_div(H, sh); L.Ws = cgs_ceil_div(W, sw); L.Cs = Cout; }
-    else { L.Hs = H; L.Ws = W; L.Cs = Cin; L.Hb = Ho; L.Wb = Wo; L.Cb = Cout; }
-    if (epilogue >= CGS_EPI_RELU_BWD_AFFINE)          // consumer: a backward-data whose epilogue applies relu' / lrelu'
-        return (fam == CGS_FAMILY_PATCH && cgs_conv_patch_signs_ok(L, dirT, epilogue)) || (fam == CGS_FAMILY_TAPS && cgs_conv_taps_signs_ok(L, epilogue));
-    if (fam == CGS_FAMILY_IGEMM_BX6)            // producer on the split-bf16 kernel: whole 64-column wave tiles, never split over K
-        return (epilogue == CGS_EPI_AFFINE_RELU || epilogue == CGS_EPI_LRELU) &&
-               (size_t)B * ((size_t)L.Hb * L.Wb * L.Cb > (size_t)L.Hs * L.Ws * L.Cs ? (size_t)L.Hb * L.Wb * L.Cb : (size_t)L.Hs * L.Ws * L.Cs) * 4 <= 0x7fffffffUL;
-    if (fam != CGS_FAMILY_IGEMM || (dirT && (sh > 2 || sw > 2))) return 0;        // producer: a forward with the relu / lrelu epilogue
-    IgemmParams p;
-    p.B = B; p.stat_part = nullptr; p.sign_out = nullptr; p.sign_plane = 0; p.epilogue = epilogue;
-    if (dirT) cgs_geom_T(L, p); else cgs_geom_F(L, p);
-    const size_t in_img = (size_t)p.Hin * p.Win * p.Cred * 4, out_img = (size_t)p.Hout * p.Wout * p.N * 4;
-    if ((size_t)B * (in_img > out_img ? in_img : out_img) > 0x7fffffffUL) return 0;      // (a split batch may fall under the split-K threshold)
-    return cgs_igemm_signs_ok(p);
+    return conv_entry("deconv2d_nhwc_bwd_data_nstats", CGS_DECONV_BWD_DATA, dy, w, nullptr, dx, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, CGS_EPI_NONE, nullptr,
+                      nullptr, x_norm, ws, ws_bytes, ws_prepacked, stream, ConvExtras{FORM_NSTATS, stat_part, stat_part_bytes, NsArgs{mean, invstd, gamma, beta,
+                      leak, group_images}});
 }
 
 int cgs_deconv2d_nhwc_fwd_signs(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
                                 int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw, int epilogue, const float* ep_a,
                                 const float* ep_b, unsigned* signs, void* ws, size_t ws_bytes, int ws_prepacked, void* stream) {
-    if (!signs) return cgs_set_error(CGS_EINVAL, "deconv2d_nhwc_fwd_signs: null sign mask");
-    if (!cgs_conv_signs_ok(CGS_DECONV_FWD, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, ws_bytes))
-        return cgs_set_error(CGS_EINVAL, "deconv2d_nhwc_fwd_signs: not available for this call (cgs_conv_signs_ok == 0)");
-    CgsLayer L;
-    int rc = make_layer(L, kh, kw, sh, sw, Ho, Wo, Cout, H, W, Cin, "deconv2d_nhwc_fwd_signs");
-    if (rc) return rc;
-    return run_dir(L, true, B, x, w, bias, y, epilogue, ep_a, ep_b, nullptr, ws, ws_bytes, ws_prepacked, (hipStream_t)stream,
-                   "deconv2d_nhwc_fwd_signs", nullptr, signs);
+    return conv_entry("deconv2d_nhwc_fwd_signs", CGS_DECONV_FWD, x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, ep_a, ep_b, nullptr, ws,
+                      ws_bytes, ws_prepacked, stream, ConvExtras{FORM_SIGNS, nullptr, 0, NsArgs{}, signs, nullptr});
 }
 
 int cgs_deconv2d_nhwc_bwd_data_signs(const float* dy, const float* w, float* dx, int B, int H, int W, int Cin, int Ho, int Wo,
                                      int Cout, int kh, int kw, int sh, int sw, int epilogue, const float* ep_a,
                                      const unsigned* aux_signs, void* ws, size_t ws_bytes, int ws_prepacked, void* stream) {
-    if (!aux_signs) return cgs_set_error(CGS_EINVAL, "deconv2d_nhwc_bwd_data_signs: null sign mask");
-    if (!cgs_conv_signs_ok(CGS_DECONV_BWD_DATA, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, ws_bytes))
-        return cgs_set_error(CGS_EINVAL, "deconv2d_nhwc_bwd_data_signs: not available for this call (cgs_conv_signs_ok == 0)");
-    CgsLayer L;
-    int rc = make_layer(L, kh, kw, sh, sw, Ho, Wo, Cout, H, W, Cin, "deconv2d_nhwc_bwd_data_signs");
-    if (rc) return rc;
-    return run_dir(L, false, B, dy, w, nullptr, dx, epilogue, ep_a, nullptr, nullptr, ws, ws_bytes, ws_prepacked, (hipStream_t)stream,
-                   "deconv2d_nhwc_bwd_data_signs", nullptr, nullptr, aux_signs);
+    return conv_entry("deconv2d_nhwc_bwd_data_signs", CGS_DECONV_BWD_DATA, dy, w, nullptr, dx, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, ep_a, nullptr,
+                      nullptr, ws, ws_bytes, ws_prepacked, stream, ConvExtras{FORM_SIGNS, nullptr, 0, NsArgs{}, nullptr, aux_signs});
 }
 
 }  // extern "C"
@@ -529,10 +527,9 @@ int cgs_linear_fwd(const float* x, const float* w, const float* bias, float* y, 
         CGS_CHECK_LAUNCH("linear_out1_fwd");
         return CGS_OK;
     }
-    CgsLayer L;
-    int rc = make_layer(L, 1, 1, 1, 1, 1, 1, in, 1, 1, out, "linear_fwd");
-    if (rc) return rc;
-    return run_dir(L, false, B, x, w, bias, y, epilogue, nullptr, nullptr, nullptr, ws, ws_bytes, ws_prepacked, (hipStream_t)stream, "linear_fwd");
+    // a 1x1 convolution over a 1x1 image
+    return conv_entry("linear_fwd", CGS_CONV_FWD, x, w, bias, y, B, 1, 1, in, 0, 0, out, 1, 1, 1, 1, epilogue, nullptr, nullptr, nullptr, ws, ws_bytes, ws_prepacked,
+                      stream);
 }
 
 int cgs_linear_out1_bce(const float* x, const float* w, const float* bias, float* logits, float* dlogits, float* logit_mean, int B, int in,
@@ -553,10 +550,8 @@ int cgs_linear_bwd_data(const float* dy, const float* w, float* dx, int B, int i
         CGS_CHECK_LAUNCH("linear_out1_bwd");
         return CGS_OK;
     }
-    CgsLayer L;
-    int rc = make_layer(L, 1, 1, 1, 1, 1, 1, in, 1, 1, out, "linear_bwd_data");
-    if (rc) return rc;
-    return run_dir(L, true, B, dy, w, nullptr, dx, CGS_EPI_NONE, nullptr, nullptr, nullptr, ws, ws_bytes, ws_prepacked, (hipStream_t)stream, "linear_bwd_data");
+    return conv_entry("linear_bwd_data", CGS_CONV_BWD_DATA, dy, w, nullptr, dx, B, 1, 1, in, 0, 0, out, 1, 1, 1, 1, CGS_EPI_NONE, nullptr, nullptr, nullptr, ws,
+                      ws_bytes, ws_prepacked, stream);
 }
 
 }  // extern "C"
