@@ -178,6 +178,13 @@ __device__ __forceinline__ float epilogue_apply(float v, int mode, float a, floa
         }                                                                                                               \
     } while (0)
 
+// the 2-D discriminator at 64 < nhidden <= 256 (mlp2d_wide.hip); arguments already checked by the entry points of mlp2d.hip
+int cgs_mlp2d_wide_saliency(const float* const* w, const float* const* b, int nlayers, int nh, const float* x, float* sig, float* sal, int B,
+                            float inv_batch, hipStream_t st);
+int cgs_refine2d_wide(const float* const* w, const float* const* b, int nlayers, int nh, const float* x, float mean_host,
+                      const float* mean_dev, float inv_batch, int steps, float rate, int method, float* best_x, float* best_step,
+                      float* traj, int B, hipStream_t st);
+
 bool cgs_convt_quad_fits(const CgsLayer& L);
 int cgs_conv_smalln_f_ok(const CgsLayer& L, int B, int epilogue);
 size_t cgs_conv_smalln_f_ws_floats(const CgsLayer& L);

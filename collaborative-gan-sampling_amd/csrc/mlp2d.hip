@@ -10,6 +10,7 @@
 #include "cgs_internal.h"
 
 #define MLP_MAX_LAYERS 6      // all layers (and their transposes) LDS-resident: 6 layers = 133 KB of 160 KB
+#define MLP_WIDE_MAX 256      // D evaluation only (sigmoid / saliency / refiner): 65 .. 256 units go to the sample-tile kernels of mlp2d_wide.hip
 
 struct MlpParams {
     const float* w[MLP_MAX_LAYERS];   // layer l: [din_l][dout_l] row-major (tf.layers.dense kernel)
@@ -289,8 +290,10 @@ __global__ __launch_bounds__(1024) void mlp_train_grad_kernel(MlpTrainPtrs q, in
     }
 }
 
-static int mlp_fill(MlpParams& p, const float* const* w, const float* const* b, int nlayers, int nh, const char* who) {
-    if (nlayers < 2 || nlayers > MLP_MAX_LAYERS || nh < 1 || nh > 64) return cgs_set_error(CGS_EINVAL, "%s: nlayers=%d nhidden=%d (need 2..6, 1..64)", who, nlayers, nh);
+// max_nh: 64 for the kernels of this file; MLP_WIDE_MAX for the entry points that mlp2d_wide.hip serves past 64
+static int mlp_fill(MlpParams& p, const float* const* w, const float* const* b, int nlayers, int nh, int max_nh, const char* who) {
+    if (nlayers < 2 || nlayers > MLP_MAX_LAYERS || nh < 1 || nh > max_nh) return cgs_set_error(CGS_EINVAL, "%s: nlayers=%d nhidden=%d (need 2..6, 1..%d)", who, nlayers, nh, max_nh);
+    if (!w || !b) return cgs_set_error(CGS_EINVAL, "%s: null weight array", who);
     for (int l = 0; l < nlayers; ++l) {
         if (!w[l] || !b[l]) return cgs_set_error(CGS_EINVAL, "%s: null weight", who);
         p.w[l] = w[l]; p.b[l] = b[l];
@@ -306,9 +309,10 @@ extern "C" {
 int cgs_mlp2d_sigmoid_saliency(const float* const* w, const float* const* b, int nlayers, int nhidden, const float* x,
                                float* sigmoid, float* saliency, int B, float inv_batch, void* stream) {
     MlpParams p;
-    int rc = mlp_fill(p, w, b, nlayers, nhidden, "mlp2d_sigmoid_saliency");
+    int rc = mlp_fill(p, w, b, nlayers, nhidden, MLP_WIDE_MAX, "mlp2d_sigmoid_saliency");
     if (rc) return rc;
     if (B <= 0 || !x || !sigmoid) return cgs_set_error(CGS_EINVAL, "mlp2d_sigmoid_saliency: bad argument");
+    if (nhidden > 64) return cgs_mlp2d_wide_saliency(w, b, nlayers, nhidden, x, sigmoid, saliency, B, inv_batch, (hipStream_t)stream);
     const size_t smem = mlp_smem(nlayers);
     CGS_SMEM_ATTR(160 * 1024, "mlp2d_sigmoid_saliency", mlp_saliency_kernel);
     int blocks = (B + 15) / 16; if (blocks > 256) blocks = 256;
@@ -321,9 +325,12 @@ static int refine2d_launch(const float* const* w, const float* const* b, int nla
                            const float* mean_dev, float inv_batch, int steps, float rate, int method, float* best_x, float* best_step,
                            float* traj, int B, void* stream) {
     MlpParams p;
-    int rc = mlp_fill(p, w, b, nlayers, nhidden, "refine2d");
+    int rc = mlp_fill(p, w, b, nlayers, nhidden, MLP_WIDE_MAX, "refine2d");
     if (rc) return rc;
     if (B <= 0 || steps < 0 || method < 0 || method > 2 || !x || !best_x || !best_step) return cgs_set_error(CGS_EINVAL, "refine2d: bad argument");
+    if (nhidden > 64)
+        return cgs_refine2d_wide(w, b, nlayers, nhidden, x, mean_host, mean_dev, inv_batch, steps, rate, method, best_x, best_step, traj, B,
+                                 (hipStream_t)stream);
     const size_t smem = mlp_smem(nlayers);
     CGS_SMEM_ATTR(160 * 1024, "refine2d", refine2d_kernel);
     int blocks = (B + 15) / 16; if (blocks > 256) blocks = 256;
@@ -354,7 +361,7 @@ size_t cgs_mlp2d_train_ws_bytes(int B_total, int nlayers) {
 int cgs_mlp2d_d_step(float* const* w, float* const* b, int nlayers, int nhidden, const float* real, int B_real, const float* fake,
                      int B_fake, float lr, float* const* gw, float* const* gb, float* loss, void* ws, size_t ws_bytes, void* stream) {
     MlpParams p;
-    int rc = mlp_fill(p, (const float* const*)w, (const float* const*)b, nlayers, nhidden, "mlp2d_d_step");
+    int rc = mlp_fill(p, (const float* const*)w, (const float* const*)b, nlayers, nhidden, 64, "mlp2d_d_step");
     if (rc) return rc;
     if (B_real <= 0 || B_fake <= 0 || !real || !fake) return cgs_set_error(CGS_EINVAL, "mlp2d_d_step: bad argument");
     const int Bt = B_real + B_fake;
@@ -715,7 +722,7 @@ int cgs_mlp2d_gen_fwd(const float* const* w, const float* const* b, const float*
                       float* const* moving_mean, float* const* moving_variance, int nlayers, int nhidden, const float* z, float* x, int B,
                       int is_training, float eps, float* batch_stats, void* ws, size_t ws_bytes, void* stream) {
     MlpParams p;
-    int rc = mlp_fill(p, w, b, nlayers, nhidden, "mlp2d_gen_fwd");
+    int rc = mlp_fill(p, w, b, nlayers, nhidden, 64, "mlp2d_gen_fwd");
     if (rc) return rc;
     if (!x) return cgs_set_error(CGS_EINVAL, "mlp2d_gen_fwd: null output");
     rc = gen_check("mlp2d_gen_fwd", gamma, beta, moving_mean, moving_variance, nlayers, z, B, is_training != 0, eps,
@@ -729,7 +736,7 @@ int cgs_mlp2d_g_step(float* const* w, float* const* b, const float* const* gamma
                      float* const* moving_variance, int nlayers, int nhidden, const float* z, const float* grad_plugin, int B, float eps,
                      float lr, float* const* gw, float* const* gb, float* x, void* ws, size_t ws_bytes, void* stream) {
     MlpParams p;
-    int rc = mlp_fill(p, (const float* const*)w, (const float* const*)b, nlayers, nhidden, "mlp2d_g_step");
+    int rc = mlp_fill(p, (const float* const*)w, (const float* const*)b, nlayers, nhidden, 64, "mlp2d_g_step");
     if (rc) return rc;
     if (!grad_plugin) return cgs_set_error(CGS_EINVAL, "mlp2d_g_step: null grad_plugin");
     rc = gen_check("mlp2d_g_step", gamma, beta, moving_mean, moving_variance, nlayers, z, B, 1, eps,

@@ -6,7 +6,8 @@
   ``sampling.refiner_cpu.Refiner`` drives the GPU discriminator unchanged (K+2 launches per batch).
 * ``Refiner``           -- same class surface as ``refiner_cpu.Refiner`` (``Refiner(args)``, ``set_env``,
   ``manipulate_sample``), but the whole K-step loop -- D forward, saliency, ladam / momentum / sgd update, best-loss
-  tracking, trajectory -- is ONE kernel launch (one wave per sample, weights in LDS).
+  tracking, trajectory -- is ONE kernel launch (up to 64 hidden units: one wave per sample, weights in LDS; 65..256 units, the
+  25-Gaussians D: a tile of samples per workgroup on the fp32 MFMA, weights streamed from L2).
 * ``MLPGenerator`` / ``GStep`` -- the batch-normalised MLP G of synthetic/GAN.py:39-49 (training- and inference-mode forward)
   and its update g_optim (GAN.py:83-101) on the device.
 * ``GanTrainer``        -- the iteration loop of synthetic/main.py:350-395 (train | calibrate | shape | test) on these pieces.
@@ -68,9 +69,10 @@ class MLPDiscriminator:
         self.w = [torch.as_tensor(np.asarray(params[f"discriminator/d_fc{i + 1}/kernel"]), dtype=torch.float32).contiguous().to(self.dev) for i in range(n)]
         self.b = [torch.as_tensor(np.asarray(params[f"discriminator/d_fc{i + 1}/bias"]), dtype=torch.float32).contiguous().to(self.dev) for i in range(n)]
         self.nhidden = int(self.w[0].shape[1])
-        if self.w[0].shape[0] != 2 or self.w[-1].shape[1] != 1 or self.nhidden > 64 or not 2 <= n <= 6:
-            # every layer's weights (and their transposes) are LDS-resident: 6 layers = 133 KB of the CU's 160 KB
-            raise L.CgsError(f"MLPDiscriminator: unsupported shape (2 -> {self.nhidden} x {n - 1} -> 1; need nhidden <= 64, 2..6 layers)")
+        if self.w[0].shape[0] != 2 or self.w[-1].shape[1] != 1 or self.nhidden > 256 or not 2 <= n <= 6:
+            # up to 64 units every layer's weights (and their transposes) are LDS-resident: 6 layers = 133 KB of the CU's 160 KB; from 65 to
+            # 256 the sample-tile kernels keep only a tile's activations in LDS (T = 64 at 256 units: 143 KB) and stream the weights from L2
+            raise L.CgsError(f"MLPDiscriminator: unsupported shape (2 -> {self.nhidden} x {n - 1} -> 1; need nhidden <= 256, 2..6 layers)")
         self._wp = (C.c_void_p * n)(*[t.data_ptr() for t in self.w])
         self._bp = (C.c_void_p * n)(*[t.data_ptr() for t in self.b])
 
@@ -180,6 +182,13 @@ class Refiner:
         return best.cpu().numpy().astype(fake_batch.dtype, copy=False)
 
 
+def _need_narrow(discriminator, who):
+    """Scoring and refining run up to 256 units; what trains (the D step, and the generator it is paired with) is 64-unit kernels."""
+    if discriminator.nhidden > 64:
+        raise L.CgsError(f"{who}: discriminator has {discriminator.nhidden} hidden units, the limit here is 64: the D step and the "
+                         "generator are still 64-unit kernels (sigmoid_and_saliency / refine / Refiner serve up to 256)")
+
+
 class DShaper:
     """The D update of the 2-D shaping loop (synthetic/main.py:366-370): one ``tf.train.GradientDescentOptimizer(lrd)`` step on
     d_loss = mean BCE(D(real), 1) + mean BCE(D(refined), 0) (synthetic/GAN.py:69-74,98-99), run on the device IN PLACE on the
@@ -187,6 +196,7 @@ class DShaper:
     The refiner reads the same tensors, so the next ``manipulate_sample`` sees the shaped D."""
 
     def __init__(self, discriminator, lrd=1e-2):                      # synthetic/main.py:39 (--lrd 1e-2)
+        _need_narrow(discriminator, "DShaper")
         self.D, self.lrd = discriminator, float(lrd)
         self.loss = torch.zeros(2, dtype=torch.float32, device=discriminator.dev)
         self.gw = [torch.zeros_like(t) for t in discriminator.w]
@@ -406,6 +416,7 @@ class GanTrainer:
     MODES = ("train", "calibrate", "shape", "test")
 
     def __init__(self, G, D, data, noise=None, batch_size=1000, lrd=1e-2, lrg=5e-3, refiner=None):
+        _need_narrow(D, "GanTrainer")
         self.G, self.D, self.data = G, D, data
         self.noise = noise if noise is not None else NoiseDataset()
         self.batch_size = int(batch_size)

@@ -353,13 +353,17 @@ int cgs_refine_select_rows(const float* src, const float* logit, const int32_t* 
 
 /* ---- the 2-D path (BASELINE config 1: synthetic/ MLP GAN) ----------------------------------------------------------
  * ReLU MLP discriminator on 2-D points, 2 -> nhidden x (nlayers-1) -> 1 (synthetic/GAN.py:28-37); w[l] is layer l's
- * [din,dout] kernel (tf.layers.dense), b[l] its bias; w / b are HOST arrays of nlayers DEVICE pointers; nhidden <= 64.
+ * [din,dout] kernel (tf.layers.dense), b[l] its bias; w / b are HOST arrays of nlayers DEVICE pointers; nlayers 2..6.
+ * cgs_mlp2d_sigmoid_saliency, cgs_refine2d and cgs_refine2d_devbase take 1 <= nhidden <= 256, chosen by nhidden alone: up to 64 the
+ * one-wave-per-sample kernels with every layer in LDS (mlp2d.hip); 65..256 (the 25-Gaussians D: 256 x 6) the sample-tile kernels on
+ * v_mfma_f32_32x32x2_f32 with the weights streamed from L2 (mlp2d_wide.hip).  The training entry points below stay at nhidden <= 64.
  *   sigmoid[B]    = sigmoid(D(x))                                              synthetic/GAN.py:108
  *   saliency[B,2] = inv_batch * d sum_b softplus(-logit_b) / dx  (inv_batch = 1/B keeps the reduce_mean factor of :109-111)
  * saliency may be NULL. */
 int cgs_mlp2d_sigmoid_saliency(const float* const* w, const float* const* b, int nlayers, int nhidden, const float* x,
                                float* sigmoid, float* saliency, int B, float inv_batch, void* stream);
-/* The whole host loop of sampling/refiner_cpu.py:26-66 in one launch (one wave per sample): K steps of
+/* The whole host loop of sampling/refiner_cpu.py:26-66 in one launch (nhidden <= 64: one wave per sample; 65..256: a tile of 32 or
+ * 64 samples per workgroup, no workspace either way): K steps of
  * sgd (method 0) / momentum (1) / ladam (2) (sampling/policy.py:26-61) on x[B,2] with loss = real_sigmoid_mean - sigmoid,
  * best-loss tracking (best_x[B,2], best_step[B]) and, if traj != NULL, the trajectory traj[B,K+1,2]. */
 int cgs_refine2d(const float* const* w, const float* const* b, int nlayers, int nhidden, const float* x,
@@ -367,7 +371,7 @@ int cgs_refine2d(const float* const* w, const float* const* b, int nlayers, int 
                  float* best_x, float* best_step, float* traj, int B, void* stream);
 
 /* The same with the baseline read from DEVICE memory (one float): the real batch's mean sigmoid never visits the host, so
- * consecutive batches queue without a synchronisation. */
+ * consecutive batches queue without a synchronisation.  nhidden <= 256 like cgs_refine2d. */
 int cgs_refine2d_devbase(const float* const* w, const float* const* b, int nlayers, int nhidden, const float* x,
                          const float* real_sigmoid_mean_dev, float inv_batch, int steps, float rate, int method,
                          float* best_x, float* best_step, float* traj, int B, void* stream);
@@ -377,7 +381,7 @@ int cgs_refine2d_devbase(const float* const* w, const float* const* b, int nlaye
  * w.r.t. every D variable and, if lr != 0, tf.train.GradientDescentOptimizer(lr)'s step w -= lr*g IN PLACE (synthetic/GAN.py:98-99).
  * w / b (and the optional gw / gb gradient outputs, same shapes; NULL or NULL entries = not returned) are HOST arrays of nlayers
  * DEVICE pointers; loss (device, 2 floats, may be NULL) <- (d_loss_real, d_loss_fake) BEFORE the update.  Deterministic
- * (fixed summation order).  ws: cgs_mlp2d_train_ws_bytes(B_real + B_fake, nlayers). */
+ * (fixed summation order).  nhidden <= 64.  ws: cgs_mlp2d_train_ws_bytes(B_real + B_fake, nlayers). */
 size_t cgs_mlp2d_train_ws_bytes(int B_total, int nlayers);
 int cgs_mlp2d_d_step(float* const* w, float* const* b, int nlayers, int nhidden, const float* real, int B_real,
                      const float* fake, int B_fake, float lr, float* const* gw, float* const* gb, float* loss,
