@@ -10,7 +10,7 @@
 #include "cgs_internal.h"
 
 #define MLP_MAX_LAYERS 6      // all layers (and their transposes) LDS-resident: 6 layers = 133 KB of 160 KB
-#define MLP_WIDE_MAX 256      // D evaluation only (sigmoid / saliency / refiner): 65 .. 256 units go to the sample-tile kernels of mlp2d_wide.hip
+#define MLP_WIDE_MAX 256      // D only (sigmoid / saliency / refiner, and the D step under its own name): 65 .. 256 units go to the sample-tile kernels of mlp2d_wide*.hip
 
 struct MlpParams {
     const float* w[MLP_MAX_LAYERS];   // layer l: [din_l][dout_l] row-major (tf.layers.dense kernel)
@@ -290,9 +290,10 @@ __global__ __launch_bounds__(1024) void mlp_train_grad_kernel(MlpTrainPtrs q, in
     }
 }
 
-// max_nh: 64 for the kernels of this file; MLP_WIDE_MAX for the entry points that mlp2d_wide.hip serves past 64
-static int mlp_fill(MlpParams& p, const float* const* w, const float* const* b, int nlayers, int nh, int max_nh, const char* who) {
-    if (nlayers < 2 || nlayers > MLP_MAX_LAYERS || nh < 1 || nh > max_nh) return cgs_set_error(CGS_EINVAL, "%s: nlayers=%d nhidden=%d (need 2..6, 1..%d)", who, nlayers, nh, max_nh);
+// max_nh: 64 for the kernels of this file; MLP_WIDE_MAX for the entry points that mlp2d_wide.hip serves past 64.  min_nh: 65 for the
+// entry point that only mlp2d_wide_train.hip serves
+static int mlp_fill(MlpParams& p, const float* const* w, const float* const* b, int nlayers, int nh, int max_nh, const char* who, int min_nh = 1) {
+    if (nlayers < 2 || nlayers > MLP_MAX_LAYERS || nh < min_nh || nh > max_nh) return cgs_set_error(CGS_EINVAL, "%s: nlayers=%d nhidden=%d (need 2..6, %d..%d)", who, nlayers, nh, min_nh, max_nh);
     if (!w || !b) return cgs_set_error(CGS_EINVAL, "%s: null weight array", who);
     for (int l = 0; l < nlayers; ++l) {
         if (!w[l] || !b[l]) return cgs_set_error(CGS_EINVAL, "%s: null weight", who);
@@ -389,6 +390,22 @@ int cgs_mlp2d_d_step(float* const* w, float* const* b, int nlayers, int nhidden,
                        B_fake, acts, deltas, dlast, bce, lr, loss);
     CGS_CHECK_LAUNCH("mlp_train_grad");
     return CGS_OK;
+}
+
+size_t cgs_mlp2d_wide_train_ws_bytes(int B_total, int nlayers, int nhidden) {
+    if (B_total <= 0 || nlayers < 2 || nlayers > MLP_MAX_LAYERS || nhidden <= 64 || nhidden > MLP_WIDE_MAX) return 0;
+    return cgs_mlp2d_wide_train_ws(B_total, nlayers, nhidden);
+}
+
+int cgs_mlp2d_wide_d_step(float* const* w, float* const* b, int nlayers, int nhidden, const float* real, int B_real, const float* fake,
+                          int B_fake, float lr, float* const* gw, float* const* gb, float* loss, void* ws, size_t ws_bytes, void* stream) {
+    MlpParams p;
+    int rc = mlp_fill(p, (const float* const*)w, (const float* const*)b, nlayers, nhidden, MLP_WIDE_MAX, "mlp2d_wide_d_step", 65);
+    if (rc) return rc;
+    if (B_real <= 0 || B_fake <= 0 || (long)B_real + B_fake > (1 << 24) || !real || !fake) return cgs_set_error(CGS_EINVAL, "mlp2d_wide_d_step: bad argument");
+    const size_t need = cgs_mlp2d_wide_train_ws_bytes(B_real + B_fake, nlayers, nhidden);
+    if (!ws || ws_bytes < need) return cgs_set_error(CGS_EWORKSPACE, "mlp2d_wide_d_step: workspace %zu < %zu bytes", ws_bytes, need);
+    return cgs_mlp2d_wide_train(w, b, nlayers, nhidden, real, B_real, fake, B_fake, lr, gw, gb, loss, ws, (hipStream_t)stream);
 }
 
 }  // extern "C"

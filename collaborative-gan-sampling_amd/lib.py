@@ -87,6 +87,8 @@ SIGNATURES = {
     "cgs_refine2d_devbase": (_i, [_p, _p, _i, _i, _p, _p, _f, _i, _f, _i, _p, _p, _p, _i, _p]),
     "cgs_mlp2d_train_ws_bytes": (_z, [_i, _i]),
     "cgs_mlp2d_d_step": (_i, [_p, _p, _i, _i, _p, _i, _p, _i, _f, _p, _p, _p, _p, _z, _p]),
+    "cgs_mlp2d_wide_train_ws_bytes": (_z, [_i, _i, _i]),
+    "cgs_mlp2d_wide_d_step": (_i, [_p, _p, _i, _i, _p, _i, _p, _i, _f, _p, _p, _p, _p, _z, _p]),
     "cgs_mlp2d_gen_ws_bytes": (_z, [_i, _i, _i]),
     "cgs_mlp2d_gen_fwd": (_i, [_p] * 6 + [_i, _i, _p, _p, _i, _i, _f, _p, _p, _z, _p]),
     "cgs_mlp2d_g_step": (_i, [_p] * 6 + [_i, _i, _p, _p, _i, _f, _f, _p, _p, _p, _p, _z, _p]),

@@ -8,6 +8,8 @@
   ``manipulate_sample``), but the whole K-step loop -- D forward, saliency, ladam / momentum / sgd update, best-loss
   tracking, trajectory -- is ONE kernel launch (up to 64 hidden units: one wave per sample, weights in LDS; 65..256 units, the
   25-Gaussians D: a tile of samples per workgroup on the fp32 MFMA, weights streamed from L2).
+* ``DShaper`` / ``WideDShaper`` -- the D update of the calibrate / shape modes (synthetic/main.py:361-370), in place on the
+  discriminator's tensors: up to 64 units and 65..256 units; ``d_shaper`` picks the class by width.  ``shape_step`` takes either.
 * ``MLPGenerator`` / ``GStep`` -- the batch-normalised MLP G of synthetic/GAN.py:39-49 (training- and inference-mode forward)
   and its update g_optim (GAN.py:83-101) on the device.
 * ``GanTrainer``        -- the iteration loop of synthetic/main.py:350-395 (train | calibrate | shape | test) on these pieces.
@@ -183,7 +185,7 @@ class Refiner:
 
 
 def _need_narrow(discriminator, who):
-    """Scoring and refining run up to 256 units; what trains (the D step, and the generator it is paired with) is 64-unit kernels."""
+    """DShaper, GanTrainer and the generator are 64-unit kernels; scoring, refining and WideDShaper's D step run up to 256 units."""
     if discriminator.nhidden > 64:
         raise L.CgsError(f"{who}: discriminator has {discriminator.nhidden} hidden units, the limit here is 64: the D step and the "
                          "generator are still 64-unit kernels (sigmoid_and_saliency / refine / Refiner serve up to 256)")
@@ -195,8 +197,13 @@ class DShaper:
     ``MLPDiscriminator``'s own weight tensors (two per-sample forward/backward launches + one gradient/update launch).
     The refiner reads the same tensors, so the next ``manipulate_sample`` sees the shaped D."""
 
+    _entry = "cgs_mlp2d_d_step"
+
     def __init__(self, discriminator, lrd=1e-2):                      # synthetic/main.py:39 (--lrd 1e-2)
         _need_narrow(discriminator, "DShaper")
+        self._setup(discriminator, lrd)
+
+    def _setup(self, discriminator, lrd):
         self.D, self.lrd = discriminator, float(lrd)
         self.loss = torch.zeros(2, dtype=torch.float32, device=discriminator.dev)
         self.gw = [torch.zeros_like(t) for t in discriminator.w]
@@ -209,13 +216,16 @@ class DShaper:
     def _run(self, real, refined, lr):
         D = self.D
         xr, xf = D._x(real), D._x(refined)
-        need = int(L.load().cgs_mlp2d_train_ws_bytes(xr.shape[0] + xf.shape[0], D.nlayers))
+        need = self._ws_bytes(xr.shape[0] + xf.shape[0])
         if self._ws is None or self._ws.numel() * 4 < need:
             self._ws = torch.empty(need // 4 + 4, dtype=torch.float32, device=D.dev)
-        L.call("cgs_mlp2d_d_step", D._wp, D._bp, D.nlayers, D.nhidden, xr.data_ptr(), xr.shape[0], xf.data_ptr(), xf.shape[0],
+        L.call(self._entry, D._wp, D._bp, D.nlayers, D.nhidden, xr.data_ptr(), xr.shape[0], xf.data_ptr(), xf.shape[0],
                float(lr), self._gwp, self._gbp, self.loss.data_ptr(), self._ws.data_ptr(), self._ws.numel() * 4,
                torch.cuda.current_stream(D.dev).cuda_stream)
         return self.loss
+
+    def _ws_bytes(self, B_total):
+        return int(L.load().cgs_mlp2d_train_ws_bytes(B_total, self.D.nlayers))
 
     def loss_and_grads(self, real, refined):
         """((d_loss_real, d_loss_fake) device tensor, [dW...], [db...]) without touching the weights."""
@@ -224,6 +234,28 @@ class DShaper:
     def step(self, real, refined):
         """One SGD step of D; returns (d_loss_real, d_loss_fake) as evaluated BEFORE the update (device tensor)."""
         return self._run(real, refined, self.lrd)
+
+
+class WideDShaper(DShaper):
+    """``DShaper`` for a D of 65..256 hidden units (the 25-Gaussians runs: 256 x 6), same surface, same in-place update: a sample tile
+    per workgroup keeps every layer's activation and pre-activation gradient, the hidden -> hidden weight gradients are MFMA products
+    over sample chunks of a size fixed by the batch alone, added in chunk order (csrc/mlp2d_wide_train.hip; deterministic)."""
+
+    _entry = "cgs_mlp2d_wide_d_step"
+
+    def __init__(self, discriminator, lrd=1e-2):
+        if discriminator.nhidden <= 64:
+            raise L.CgsError(f"WideDShaper: discriminator has {discriminator.nhidden} hidden units; up to 64 units the D step is DShaper "
+                             "(d_shaper() picks the class by width)")
+        self._setup(discriminator, lrd)
+
+    def _ws_bytes(self, B_total):
+        return int(L.load().cgs_mlp2d_wide_train_ws_bytes(B_total, self.D.nlayers, self.D.nhidden))
+
+
+def d_shaper(discriminator, lrd=1e-2):
+    """The D update for this discriminator's width: ``DShaper`` up to 64 hidden units, ``WideDShaper`` above."""
+    return (DShaper if discriminator.nhidden <= 64 else WideDShaper)(discriminator, lrd)
 
 
 def shape_step(refiner, shaper, noise_sample, real_batch):

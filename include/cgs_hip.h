@@ -356,7 +356,8 @@ int cgs_refine_select_rows(const float* src, const float* logit, const int32_t* 
  * [din,dout] kernel (tf.layers.dense), b[l] its bias; w / b are HOST arrays of nlayers DEVICE pointers; nlayers 2..6.
  * cgs_mlp2d_sigmoid_saliency, cgs_refine2d and cgs_refine2d_devbase take 1 <= nhidden <= 256, chosen by nhidden alone: up to 64 the
  * one-wave-per-sample kernels with every layer in LDS (mlp2d.hip); 65..256 (the 25-Gaussians D: 256 x 6) the sample-tile kernels on
- * v_mfma_f32_32x32x2_f32 with the weights streamed from L2 (mlp2d_wide.hip).  The training entry points below stay at nhidden <= 64.
+ * v_mfma_f32_32x32x2_f32 with the weights streamed from L2 (mlp2d_wide.hip).  The training entry points below stay at nhidden <= 64, except the D step, which has a
+ * second entry point for 65..256 (cgs_mlp2d_wide_d_step).
  *   sigmoid[B]    = sigmoid(D(x))                                              synthetic/GAN.py:108
  *   saliency[B,2] = inv_batch * d sum_b softplus(-logit_b) / dx  (inv_batch = 1/B keeps the reduce_mean factor of :109-111)
  * saliency may be NULL. */
@@ -386,6 +387,16 @@ size_t cgs_mlp2d_train_ws_bytes(int B_total, int nlayers);
 int cgs_mlp2d_d_step(float* const* w, float* const* b, int nlayers, int nhidden, const float* real, int B_real,
                      const float* fake, int B_fake, float lr, float* const* gw, float* const* gb, float* loss,
                      void* ws, size_t ws_bytes, void* stream);
+
+/* The same step for 65 <= nhidden <= 256 (mlp2d_wide_train.hip; nlayers 2..6; anything else: CGS_EINVAL): arguments and meaning as
+ * cgs_mlp2d_d_step.  A sample tile per workgroup keeps every layer's activation and masked pre-activation gradient in the workspace;
+ * the hidden -> hidden weight gradients are [nhidden x B_total] . [B_total x nhidden] products on v_mfma_f32_32x32x2_f32 over sample
+ * chunks whose size depends on B_total alone, their partial tiles added in chunk order: deterministic, no atomics.  The workspace layout
+ * is internal; ws: cgs_mlp2d_wide_train_ws_bytes(B_real + B_fake, nlayers, nhidden) (0 on a bad argument), CGS_EWORKSPACE if smaller. */
+size_t cgs_mlp2d_wide_train_ws_bytes(int B_total, int nlayers, int nhidden);
+int cgs_mlp2d_wide_d_step(float* const* w, float* const* b, int nlayers, int nhidden, const float* real, int B_real,
+                          const float* fake, int B_fake, float lr, float* const* gw, float* const* gb, float* loss,
+                          void* ws, size_t ws_bytes, void* stream);
 
 /* The 2-D generator G (synthetic/GAN.py:39-49): z[B,2] -> dense(2->nh) -> BN -> ReLU -> [dense(nh->nh) -> BN -> ReLU] x (nlayers-2)
  * -> dense(nh->2) -> x[B,2], BN = tf.contrib.layers.batch_norm(decay=0.9, epsilon, scale=True, updates_collections=None).
