@@ -54,7 +54,8 @@ __device__ __forceinline__ void mlpw_load(const MlpWParams& p, const MlpWLds& L)
 
 // One hidden -> hidden layer for the tile.  Forward: H <- relu(H W + bias), mask bits of layer `ml` written.  Backward: H <- (H W^T) with
 // the mask of layer `ml` (the layer below) applied to the result, which is what the next pass down, or the first layer's adjoint, needs.
-template <int T, bool BWD>
+// RAW (the generator, mlp2d_wide_gen.hip; forward only): H <- H W + bias as it leaves the accumulators, no ReLU, no mask read or written.
+template <int T, bool BWD, bool RAW = false>
 __device__ __forceinline__ void mlpw_pass(const MlpWParams& p, const MlpWLds& L, const float* __restrict__ W, const float* __restrict__ bias,
                                           int ml) {
     constexpr int NRB = T / 32, KS = T / 2, NSL = KS / 4, CPS = 16 / NSL;
@@ -149,6 +150,7 @@ __device__ __forceinline__ void mlpw_pass(const MlpWParams& p, const MlpWLds& L,
             for (int r = 0; r < 16; ++r) {
                 const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                 float v = acc[cbi][rb][r];
+                if constexpr (RAW) { L.H[row * HS + q] = v; continue; }
                 unsigned* mw = &L.masks[(ml * T + row) * NB + cb];
                 if (!BWD) {
                     const unsigned long long m = __ballot(v > 0.f);       // low word: row of h = 0; high word: row + 4 of h = 1

@@ -11,8 +11,11 @@
 * ``DShaper`` / ``WideDShaper`` -- the D update of the calibrate / shape modes (synthetic/main.py:361-370), in place on the
   discriminator's tensors: up to 64 units and 65..256 units; ``d_shaper`` picks the class by width.  ``shape_step`` takes either.
 * ``MLPGenerator`` / ``GStep`` -- the batch-normalised MLP G of synthetic/GAN.py:39-49 (training- and inference-mode forward)
-  and its update g_optim (GAN.py:83-101) on the device.
-* ``GanTrainer``        -- the iteration loop of synthetic/main.py:350-395 (train | calibrate | shape | test) on these pieces.
+  and its update g_optim (GAN.py:83-101) on the device, up to 64 hidden units.
+* ``WideMLPGenerator``  -- the same forward, both modes, at 65..256 units (the 25-Gaussians G: 256 x 6); ``mlp_generator`` picks the class
+  by width.  The G update at that width is not built.
+* ``GanTrainer``        -- the iteration loop of synthetic/main.py:350-395 (train | calibrate | shape | test) on the 64-unit pieces.
+* ``WideGanTrainer``    -- the same loop for a D and a G of any supported width: calibrate, shape and test always, train while G is narrow.
 
 Variable names follow tf.layers.dense: ``discriminator/d_fc<i>/kernel`` ([din, dout]) and ``.../bias``; G's are
 ``generator/g_fc<i>/kernel|bias`` and ``generator/BatchNorm[_k]/gamma|beta|moving_mean|moving_variance``.
@@ -324,6 +327,7 @@ class MLPGenerator:
     # GAN.py:43,47 pass epsilon=1e-5, but rank-2 inputs take TF 1.x's fused path, whose nn_impl.fused_batch_norm raises any epsilon below
     # cuDNN's minimum to 1.001e-5: the value the reference computes with
     EPS = 1.001e-5
+    _entry = "cgs_mlp2d_gen_fwd"
 
     def __init__(self, params, device="cuda:0"):
         self.dev = torch.device(device)
@@ -338,8 +342,7 @@ class MLPGenerator:
         self.w = [f32(f"generator/g_fc{i + 1}/kernel") for i in range(n)]
         self.b = [f32(f"generator/g_fc{i + 1}/bias") for i in range(n)]
         self.nhidden = int(self.w[0].shape[1])
-        if self.w[0].shape[0] != 2 or self.w[-1].shape[1] != 2 or self.nhidden > 64 or not 2 <= n <= 6:
-            raise L.CgsError(f"MLPGenerator: unsupported shape (2 -> {self.nhidden} x {n - 1} -> 2; need nhidden <= 64, 2..6 layers)")
+        self._check_shape()
         self.gamma, self.beta, self.moving_mean, self.moving_variance = ([f32(f"{_bn_name(k)}/{v}") for k in range(n - 1)]
                                                                          for v in ("gamma", "beta", "moving_mean", "moving_variance"))
         ptrs = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
@@ -347,6 +350,13 @@ class MLPGenerator:
         self._gp, self._betap = ptrs(self.gamma), ptrs(self.beta)
         self._mmp, self._mvp = ptrs(self.moving_mean), ptrs(self.moving_variance)
         self._ws = None
+
+    def _shape_ok(self):
+        return self.w[0].shape[0] == 2 and self.w[-1].shape[1] == 2 and 2 <= self.nlayers <= 6
+
+    def _check_shape(self):
+        if self.nhidden > 64 or not self._shape_ok():
+            raise L.CgsError(f"MLPGenerator: unsupported shape (2 -> {self.nhidden} x {self.nlayers - 1} -> 2; need nhidden <= 64, 2..6 layers)")
 
     @staticmethod
     def init_params(seed, nhidden=64, nlayers=6):
@@ -379,10 +389,13 @@ class MLPGenerator:
         return P
 
     def _workspace(self, B, with_backward):
-        need = int(L.load().cgs_mlp2d_gen_ws_bytes(B, self.nlayers, int(with_backward)))
+        need = self._ws_bytes(B, with_backward)
         if self._ws is None or self._ws.numel() * 4 < need:
             self._ws = torch.empty(need // 4 + 4, dtype=torch.float32, device=self.dev)
         return self._ws
+
+    def _ws_bytes(self, B, with_backward):
+        return int(L.load().cgs_mlp2d_gen_ws_bytes(B, self.nlayers, int(with_backward)))
 
     def generate(self, z, is_training=True, batch_stats=False):
         """G(z) as a device [B,2] tensor.  Training mode (``gan.generates``): batch statistics, moving averages updated in place;
@@ -393,10 +406,44 @@ class MLPGenerator:
         x = torch.empty((B, 2), dtype=torch.float32, device=self.dev)
         st = torch.empty((self.nlayers - 1, 2, self.nhidden), dtype=torch.float32, device=self.dev) if batch_stats else None
         ws = self._workspace(B, False)
-        L.call("cgs_mlp2d_gen_fwd", self._wp, self._bp, self._gp, self._betap, self._mmp, self._mvp, self.nlayers, self.nhidden,
+        L.call(self._entry, self._wp, self._bp, self._gp, self._betap, self._mmp, self._mvp, self.nlayers, self.nhidden,
                zd.data_ptr(), x.data_ptr(), B, int(bool(is_training)), self.EPS, None if st is None else st.data_ptr(),
                ws.data_ptr(), ws.numel() * 4, _stream(self.dev))
         return (x, st) if batch_stats else x
+
+
+class WideMLPGenerator(MLPGenerator):
+    """``MLPGenerator`` for 65..256 hidden units (the 25-Gaussians runs: 256 x 6), same surface: the forward in both modes on sample tiles,
+    the hidden -> hidden layers on the fp32 MFMA with the weights streamed from L2, the batch statistics combined from fixed 32-row groups
+    in row order (csrc/mlp2d_wide_gen.hip; deterministic).  ``GStep`` does not take it: the G update at this width is not built."""
+
+    _entry = "cgs_mlp2d_wide_gen_fwd"
+
+    def _check_shape(self):
+        if self.nhidden <= 64:
+            raise L.CgsError(f"WideMLPGenerator: generator has {self.nhidden} hidden units; up to 64 units the generator is MLPGenerator "
+                             "(mlp_generator() picks the class by width)")
+        if self.nhidden > 256 or not self._shape_ok():
+            raise L.CgsError(f"WideMLPGenerator: unsupported shape (2 -> {self.nhidden} x {self.nlayers - 1} -> 2; need 65 <= nhidden <= 256, 2..6 layers)")
+
+    @staticmethod
+    def init_params(seed, nhidden=256, nlayers=6):
+        return MLPGenerator.init_params(seed, nhidden, nlayers)
+
+    @classmethod
+    def init(cls, seed, nhidden=256, nlayers=6, device="cuda:0"):
+        return cls(cls.init_params(seed, nhidden, nlayers), device)
+
+    def _ws_bytes(self, B, with_backward):
+        if with_backward:
+            raise L.CgsError("WideMLPGenerator: the G step at 65..256 hidden units is not built (the forward keeps what it will need)")
+        return int(L.load().cgs_mlp2d_wide_gen_ws_bytes(B, self.nlayers, self.nhidden))
+
+
+def mlp_generator(params, device="cuda:0"):
+    """The generator for this checkpoint's width: ``MLPGenerator`` up to 64 hidden units, ``WideMLPGenerator`` above."""
+    nh = int(np.asarray(params["generator/g_fc1/kernel"]).shape[1])
+    return (MLPGenerator if nh <= 64 else WideMLPGenerator)(params, device)
 
 
 class GStep:
@@ -524,3 +571,31 @@ class GanTrainer:
         """-> (MLPGenerator, MLPDiscriminator) from a {G, D} checkpoint (ours, or a converted synthetic/main.py one)."""
         P = CK.load(path)
         return MLPGenerator.from_params(P, device), MLPDiscriminator(P, device)
+
+
+class WideGanTrainer(GanTrainer):
+    """``GanTrainer`` for a discriminator of any supported width (``d_shaper``) and either generator class.  calibrate, shape and test run
+    whatever the widths (the reference's 25-Gaussians command lines: 256 x 6 for both nets, from a checkpoint); train needs the G update and
+    so a generator of at most 64 units, with the narrow ``GStep`` and the saliency of whichever D there is."""
+
+    def __init__(self, G, D, data, noise=None, batch_size=1000, lrd=1e-2, lrg=5e-3, refiner=None):
+        self.G, self.D, self.data = G, D, data
+        self.noise = noise if noise is not None else NoiseDataset()
+        self.batch_size = int(batch_size)
+        self.dshaper = d_shaper(D, lrd)
+        self.gstep = None if isinstance(G, WideMLPGenerator) else GStep(G, lrg)
+        self.d_loss = self.dshaper.loss
+        self.refiner = refiner
+        self.eval_noise = self.eval_batch = self.target_batch = None
+
+    def iteration(self, mode="train"):
+        if mode == "train" and self.gstep is None:                       # before any draw: the host RNG stream stays where it was
+            raise L.CgsError(f"WideGanTrainer: train mode needs the G step, which is not built for a generator of {self.G.nhidden} hidden "
+                             "units (65..256: forward only); calibrate, shape and test run")
+        return super().iteration(mode)
+
+    @staticmethod
+    def load(path, device="cuda:0"):
+        """-> (MLPGenerator or WideMLPGenerator, MLPDiscriminator) from a {G, D} checkpoint, each class by its width."""
+        P = CK.load(path)
+        return mlp_generator(P, device), MLPDiscriminator(P, device)

@@ -356,8 +356,8 @@ int cgs_refine_select_rows(const float* src, const float* logit, const int32_t* 
  * [din,dout] kernel (tf.layers.dense), b[l] its bias; w / b are HOST arrays of nlayers DEVICE pointers; nlayers 2..6.
  * cgs_mlp2d_sigmoid_saliency, cgs_refine2d and cgs_refine2d_devbase take 1 <= nhidden <= 256, chosen by nhidden alone: up to 64 the
  * one-wave-per-sample kernels with every layer in LDS (mlp2d.hip); 65..256 (the 25-Gaussians D: 256 x 6) the sample-tile kernels on
- * v_mfma_f32_32x32x2_f32 with the weights streamed from L2 (mlp2d_wide.hip).  The training entry points below stay at nhidden <= 64, except the D step, which has a
- * second entry point for 65..256 (cgs_mlp2d_wide_d_step).
+ * v_mfma_f32_32x32x2_f32 with the weights streamed from L2 (mlp2d_wide.hip).  The training entry points below stay at nhidden <= 64, except the D step and the
+ * generator's forward, which have second entry points for 65..256 (cgs_mlp2d_wide_d_step, cgs_mlp2d_wide_gen_fwd).
  *   sigmoid[B]    = sigmoid(D(x))                                              synthetic/GAN.py:108
  *   saliency[B,2] = inv_batch * d sum_b softplus(-logit_b) / dx  (inv_batch = 1/B keeps the reduce_mean factor of :109-111)
  * saliency may be NULL. */
@@ -411,6 +411,18 @@ size_t cgs_mlp2d_gen_ws_bytes(int B, int nlayers, int with_backward);
 int cgs_mlp2d_gen_fwd(const float* const* w, const float* const* b, const float* const* gamma, const float* const* beta,
                       float* const* moving_mean, float* const* moving_variance, int nlayers, int nhidden, const float* z, float* x, int B,
                       int is_training, float eps, float* batch_stats, void* ws, size_t ws_bytes, void* stream);
+/* The same forward for 65 <= nhidden <= 256 (mlp2d_wide_gen.hip; nlayers 2..6; anything else: CGS_EINVAL): arguments and meaning as
+ * cgs_mlp2d_gen_fwd, B <= 2^24.  A sample tile per workgroup, the hidden -> hidden layers on v_mfma_f32_32x32x2_f32 with the weights
+ * streamed from L2; training mode is one launch per dense layer, inference mode one launch.  The batch statistics are (mean, M2) partials
+ * of fixed groups of 32 consecutive rows combined in ascending order: a function of the inputs and B alone.  Deterministic, no atomics.
+ * The workspace keeps every BN layer's pre-activations [nlayers-1][B][nhp] (nhp = nhidden rounded up to 32, padded units zero), which the
+ * generator's backward needs, then the group partials and the per-layer (mean, rstd) rows:
+ *   cgs_mlp2d_wide_gen_ws_bytes(B, nlayers, nhidden) = 4 (nlayers-1) nhp (B + 2 ceil(B / 32) + 2)   (0 on a bad argument);
+ * CGS_EWORKSPACE if smaller (both modes).  The G update at this width is not built. */
+size_t cgs_mlp2d_wide_gen_ws_bytes(int B, int nlayers, int nhidden);
+int cgs_mlp2d_wide_gen_fwd(const float* const* w, const float* const* b, const float* const* gamma, const float* const* beta,
+                           float* const* moving_mean, float* const* moving_variance, int nlayers, int nhidden, const float* z, float* x,
+                           int B, int is_training, float eps, float* batch_stats, void* ws, size_t ws_bytes, void* stream);
 /* The G update g_optim (GAN.py:83-101, run at synthetic/main.py:379-380): a training-mode forward on z (moving statistics updated as
  * above; x[B,2] <- G(z) if x != NULL), the gradients tf.gradients(generates, g_vars, grad_plugin) of every g_fc kernel and bias back
  * through the training-mode BN, and, if lr != 0, GradientDescentOptimizer(lr)'s w -= lr*g IN PLACE.  g_vars holds only the names with
