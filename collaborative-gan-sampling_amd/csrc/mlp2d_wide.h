@@ -6,6 +6,11 @@
 
 #define MLPW_MAX_LAYERS 6
 #define MLPW_THREADS 256
+#define MLPW_MAX_CHUNKS 16
+
+// Sample chunk of the weight-gradient products (mlp2d_wide_train.hip, mlp2d_wide_gstep.hip): a function of the batch alone, at most
+// MLPW_MAX_CHUNKS chunks, a multiple of 128 samples
+static int mlpw_chunk(int Bt) { return 128 * cgs_ceil_div(Bt, 128 * MLPW_MAX_CHUNKS); }
 
 typedef float mlpw_f16 __attribute__((ext_vector_type(16)));
 
@@ -54,7 +59,8 @@ __device__ __forceinline__ void mlpw_load(const MlpWParams& p, const MlpWLds& L)
 
 // One hidden -> hidden layer for the tile.  Forward: H <- relu(H W + bias), mask bits of layer `ml` written.  Backward: H <- (H W^T) with
 // the mask of layer `ml` (the layer below) applied to the result, which is what the next pass down, or the first layer's adjoint, needs.
-// RAW (the generator, mlp2d_wide_gen.hip; forward only): H <- H W + bias as it leaves the accumulators, no ReLU, no mask read or written.
+// RAW (the generator): no ReLU, no mask read or written.  Forward (mlp2d_wide_gen.hip): H <- H W + bias as it leaves the accumulators;
+// backward (mlp2d_wide_gstep.hip): H <- H W^T from a zero accumulator.
 template <int T, bool BWD, bool RAW = false>
 __device__ __forceinline__ void mlpw_pass(const MlpWParams& p, const MlpWLds& L, const float* __restrict__ W, const float* __restrict__ bias,
                                           int ml) {

@@ -28,10 +28,6 @@
 // At 256 x 6 and 1000 + 1000 rows: 20.5 MB of activations and gradients + 16.8 MB of partial tiles = 37.3 MB.
 #include "mlp2d_wide.h"
 
-#define MLPW_MAX_CHUNKS 16
-
-static int mlpw_chunk(int Bt) { return 128 * cgs_ceil_div(Bt, 128 * MLPW_MAX_CHUNKS); }
-
 struct MlpWTrainWs {
     float* acts;
     float* deltas;

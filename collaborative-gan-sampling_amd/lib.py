@@ -94,6 +94,8 @@ SIGNATURES = {
     "cgs_mlp2d_wide_gen_ws_bytes": (_z, [_i, _i, _i]),
     "cgs_mlp2d_wide_gen_fwd": (_i, [_p] * 6 + [_i, _i, _p, _p, _i, _i, _f, _p, _p, _z, _p]),
     "cgs_mlp2d_g_step": (_i, [_p] * 6 + [_i, _i, _p, _p, _i, _f, _f, _p, _p, _p, _p, _z, _p]),
+    "cgs_mlp2d_wide_g_step_ws_bytes": (_z, [_i, _i, _i]),
+    "cgs_mlp2d_wide_g_step": (_i, [_p] * 6 + [_i, _i, _p, _p, _i, _f, _f, _p, _p, _p, _p, _z, _p]),
     "cgs_conv_wgrad_ws_bytes": (_z, [_i] * 9),
     "cgs_conv2d_nhwc_bwd_weight": (_i, [_p] * 3 + [_i] * 9 + [_i, _p, _z, _p]),
     "cgs_linear_bwd_weight": (_i, [_p] * 3 + [_i] * 3 + [_i, _p, _z, _p]),

@@ -13,9 +13,11 @@
 * ``MLPGenerator`` / ``GStep`` -- the batch-normalised MLP G of synthetic/GAN.py:39-49 (training- and inference-mode forward)
   and its update g_optim (GAN.py:83-101) on the device, up to 64 hidden units.
 * ``WideMLPGenerator``  -- the same forward, both modes, at 65..256 units (the 25-Gaussians G: 256 x 6); ``mlp_generator`` picks the class
-  by width.  The G update at that width is not built.
+  by width.
+* ``WideGStep``         -- ``GStep`` for a ``WideMLPGenerator`` (cgs_mlp2d_wide_g_step); ``g_stepper`` picks the class by width.
 * ``GanTrainer``        -- the iteration loop of synthetic/main.py:350-395 (train | calibrate | shape | test) on the 64-unit pieces.
 * ``WideGanTrainer``    -- the same loop for a D and a G of any supported width: calibrate, shape and test always, train while G is narrow.
+* ``Gan2DTrainer``      -- the same loop, all four modes, for any supported widths of G and D (``g_stepper`` and ``d_shaper``).
 
 Variable names follow tf.layers.dense: ``discriminator/d_fc<i>/kernel`` ([din, dout]) and ``.../bias``; G's are
 ``generator/g_fc<i>/kernel|bias`` and ``generator/BatchNorm[_k]/gamma|beta|moving_mean|moving_variance``.
@@ -415,7 +417,7 @@ class MLPGenerator:
 class WideMLPGenerator(MLPGenerator):
     """``MLPGenerator`` for 65..256 hidden units (the 25-Gaussians runs: 256 x 6), same surface: the forward in both modes on sample tiles,
     the hidden -> hidden layers on the fp32 MFMA with the weights streamed from L2, the batch statistics combined from fixed 32-row groups
-    in row order (csrc/mlp2d_wide_gen.hip; deterministic).  ``GStep`` does not take it: the G update at this width is not built."""
+    in row order (csrc/mlp2d_wide_gen.hip; deterministic).  ``GStep`` does not take it: the G update at this width is ``WideGStep``."""
 
     _entry = "cgs_mlp2d_wide_gen_fwd"
 
@@ -452,6 +454,8 @@ class GStep:
     grad_plugin [B,2], then GradientDescentOptimizer(lrg) IN PLACE on the ``MLPGenerator``'s tensors.  Its training-mode forward moves
     the BN moving averages once more, like the reference's g_optim run."""
 
+    _entry = "cgs_mlp2d_g_step"
+
     def __init__(self, generator, lrg=5e-3):                          # synthetic/main.py:38 (--lrg 5e-3)
         self.G, self.lrg = generator, float(lrg)
         self.gw = [torch.zeros_like(t) for t in generator.w]
@@ -460,23 +464,58 @@ class GStep:
         self._gwp = (C.c_void_p * n)(*[t.data_ptr() for t in self.gw])
         self._gbp = (C.c_void_p * n)(*[t.data_ptr() for t in self.gb])
 
-    def _run(self, z, grad_plugin, lr):
+    def _workspace(self, B):
+        return self.G._workspace(B, True)
+
+    def _run(self, z, grad_plugin, lr, want_x=False):
         G = self.G
         zd, gd = _upload(z, G.dev), _upload(grad_plugin, G.dev)
         B = zd.shape[0]
         if tuple(gd.shape) != (B, 2):
-            raise L.CgsError(f"GStep: grad_plugin shape {tuple(gd.shape)} != ({B}, 2)")
-        ws = G._workspace(B, True)
-        L.call("cgs_mlp2d_g_step", G._wp, G._bp, G._gp, G._betap, G._mmp, G._mvp, G.nlayers, G.nhidden, zd.data_ptr(), gd.data_ptr(), B,
-               G.EPS, float(lr), self._gwp, self._gbp, None, ws.data_ptr(), ws.numel() * 4, _stream(G.dev))
+            raise L.CgsError(f"{type(self).__name__}: grad_plugin shape {tuple(gd.shape)} != ({B}, 2)")
+        ws = self._workspace(B)
+        x = torch.empty((B, 2), dtype=torch.float32, device=G.dev) if want_x else None
+        L.call(self._entry, G._wp, G._bp, G._gp, G._betap, G._mmp, G._mvp, G.nlayers, G.nhidden, zd.data_ptr(), gd.data_ptr(), B,
+               G.EPS, float(lr), self._gwp, self._gbp, None if x is None else x.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(G.dev))
+        return x
 
     def grads(self, z, grad_plugin):
         """([dW...], [db...]) device tensors; the weights stay as they are (the moving averages still move: the forward runs)."""
         self._run(z, grad_plugin, 0.0)
         return self.gw, self.gb
 
-    def step(self, z, grad_plugin):
-        self._run(z, grad_plugin, self.lrg)
+    def step(self, z, grad_plugin, want_x=False):
+        """One SGD step of G; ``want_x``: also return G(z) [B,2] of the step's own forward (before the update)."""
+        return self._run(z, grad_plugin, self.lrg, want_x)
+
+
+class WideGStep(GStep):
+    """``GStep`` for a ``WideMLPGenerator`` (65..256 hidden units; the 25-Gaussians runs: 256 x 6), same surface, same in-place update:
+    the wide forward, then one launch per BN layer back down the net on the same sample tiles, the batch sums of the BN backward from
+    fixed 32-row groups in row order, the hidden -> hidden weight gradients as MFMA products over sample chunks of a size fixed by the
+    batch alone, added in chunk order (csrc/mlp2d_wide_gstep.hip; deterministic).  The step keeps its own workspace, whose first bytes
+    are the forward's; the generator's stays the forward-only one."""
+
+    _entry = "cgs_mlp2d_wide_g_step"
+
+    def __init__(self, generator, lrg=5e-3):
+        if not isinstance(generator, WideMLPGenerator):
+            raise L.CgsError(f"WideGStep: generator has {generator.nhidden} hidden units; up to 64 units the G step is GStep "
+                             "(g_stepper() picks the class by width)")
+        super().__init__(generator, lrg)
+        self._ws = None
+
+    def _workspace(self, B):
+        G = self.G
+        need = int(L.load().cgs_mlp2d_wide_g_step_ws_bytes(B, G.nlayers, G.nhidden))
+        if self._ws is None or self._ws.numel() * 4 < need:
+            self._ws = torch.empty(need // 4 + 4, dtype=torch.float32, device=G.dev)
+        return self._ws
+
+
+def g_stepper(generator, lrg=5e-3):
+    """The G update for this generator's width: ``GStep`` up to 64 hidden units, ``WideGStep`` above."""
+    return (WideGStep if isinstance(generator, WideMLPGenerator) else GStep)(generator, lrg)
 
 
 class GanTrainer:
@@ -599,3 +638,14 @@ class WideGanTrainer(GanTrainer):
         """-> (MLPGenerator or WideMLPGenerator, MLPDiscriminator) from a {G, D} checkpoint, each class by its width."""
         P = CK.load(path)
         return mlp_generator(P, device), MLPDiscriminator(P, device)
+
+
+class Gan2DTrainer(WideGanTrainer):
+    """The loop for any supported widths of G and D in all four modes (``g_stepper``, ``d_shaper``): at the reference's 25-Gaussians
+    widths (256 x 6 for both nets) ``train`` runs generate -> wide D step -> generate -> saliency -> wide G step, with the reference's
+    host RNG draws in its order and the moving averages moving three times per iteration.  ``WideGanTrainer`` keeps its refusal of train
+    with a wide G; this class is the one that trains there."""
+
+    def __init__(self, G, D, data, noise=None, batch_size=1000, lrd=1e-2, lrg=5e-3, refiner=None):
+        super().__init__(G, D, data, noise, batch_size, lrd, lrg, refiner)
+        self.gstep = g_stepper(G, lrg)

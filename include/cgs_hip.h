@@ -356,8 +356,8 @@ int cgs_refine_select_rows(const float* src, const float* logit, const int32_t* 
  * [din,dout] kernel (tf.layers.dense), b[l] its bias; w / b are HOST arrays of nlayers DEVICE pointers; nlayers 2..6.
  * cgs_mlp2d_sigmoid_saliency, cgs_refine2d and cgs_refine2d_devbase take 1 <= nhidden <= 256, chosen by nhidden alone: up to 64 the
  * one-wave-per-sample kernels with every layer in LDS (mlp2d.hip); 65..256 (the 25-Gaussians D: 256 x 6) the sample-tile kernels on
- * v_mfma_f32_32x32x2_f32 with the weights streamed from L2 (mlp2d_wide.hip).  The training entry points below stay at nhidden <= 64, except the D step and the
- * generator's forward, which have second entry points for 65..256 (cgs_mlp2d_wide_d_step, cgs_mlp2d_wide_gen_fwd).
+ * v_mfma_f32_32x32x2_f32 with the weights streamed from L2 (mlp2d_wide.hip).  The training entry points below stay at nhidden <= 64; the D step, the
+ * generator's forward and the G step have second entry points for 65..256 (cgs_mlp2d_wide_d_step, cgs_mlp2d_wide_gen_fwd, cgs_mlp2d_wide_g_step).
  *   sigmoid[B]    = sigmoid(D(x))                                              synthetic/GAN.py:108
  *   saliency[B,2] = inv_batch * d sum_b softplus(-logit_b) / dx  (inv_batch = 1/B keeps the reduce_mean factor of :109-111)
  * saliency may be NULL. */
@@ -418,7 +418,7 @@ int cgs_mlp2d_gen_fwd(const float* const* w, const float* const* b, const float*
  * The workspace keeps every BN layer's pre-activations [nlayers-1][B][nhp] (nhp = nhidden rounded up to 32, padded units zero), which the
  * generator's backward needs, then the group partials and the per-layer (mean, rstd) rows:
  *   cgs_mlp2d_wide_gen_ws_bytes(B, nlayers, nhidden) = 4 (nlayers-1) nhp (B + 2 ceil(B / 32) + 2)   (0 on a bad argument);
- * CGS_EWORKSPACE if smaller (both modes).  The G update at this width is not built. */
+ * CGS_EWORKSPACE if smaller (both modes).  The G update at this width is cgs_mlp2d_wide_g_step below. */
 size_t cgs_mlp2d_wide_gen_ws_bytes(int B, int nlayers, int nhidden);
 int cgs_mlp2d_wide_gen_fwd(const float* const* w, const float* const* b, const float* const* gamma, const float* const* beta,
                            float* const* moving_mean, float* const* moving_variance, int nlayers, int nhidden, const float* z, float* x,
@@ -431,6 +431,16 @@ int cgs_mlp2d_wide_gen_fwd(const float* const* w, const float* const* b, const f
 int cgs_mlp2d_g_step(float* const* w, float* const* b, const float* const* gamma, const float* const* beta, float* const* moving_mean,
                      float* const* moving_variance, int nlayers, int nhidden, const float* z, const float* grad_plugin, int B, float eps,
                      float lr, float* const* gw, float* const* gb, float* x, void* ws, size_t ws_bytes, void* stream);
+/* The same update for 65 <= nhidden <= 256 (mlp2d_wide_gstep.hip; nlayers 2..6; anything else: CGS_EINVAL), 2 <= B <= 2^24: arguments,
+ * meaning and order of checks as cgs_mlp2d_g_step.  The forward is cgs_mlp2d_wide_gen_fwd on the first bytes of the workspace; the way
+ * back is one launch per BN layer on the same sample tiles (hidden -> hidden layers on v_mfma_f32_32x32x2_f32), the batch sums of the BN
+ * backward from fixed groups of 32 rows added in ascending order, the hidden -> hidden weight gradients MFMA products over sample chunks
+ * whose size depends on B alone, added in chunk order: a function of the inputs and B alone, no atomics.  The rest of the workspace is
+ * internal; ws: cgs_mlp2d_wide_g_step_ws_bytes(B, nlayers, nhidden) (0 on a bad argument), CGS_EWORKSPACE if smaller. */
+size_t cgs_mlp2d_wide_g_step_ws_bytes(int B, int nlayers, int nhidden);
+int cgs_mlp2d_wide_g_step(float* const* w, float* const* b, const float* const* gamma, const float* const* beta, float* const* moving_mean,
+                          float* const* moving_variance, int nlayers, int nhidden, const float* z, const float* grad_plugin, int B, float eps,
+                          float lr, float* const* gw, float* const* gb, float* x, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- discriminator shaping step (the caller after the refinement path: nsgan/GAN.py:270-272, 126-146) ----------
  * Weight gradients of D's layers, the BCE seed with 0/1 targets, and the Adam update.  NOT part of the frozen-weight
