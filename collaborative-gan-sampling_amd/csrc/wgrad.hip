@@ -267,6 +267,35 @@ int cgs_conv2d_nhwc_bwd_weight(const float* x, const float* dy, float* dw, int B
     return wgrad_run(p, dw, accumulate, ws, ws_bytes, (hipStream_t)stream, "conv2d_nhwc_bwd_weight");
 }
 
+// The weight gradient of a transposed convolution (the generator's update, nsgan/GAN.py:132-146): w[kh][kw][Cout][Cin] is the HWIO filter
+// of the 'SAME' conv (Hout, Wout, Cout) -> (Hin, Win, Cin) that deconv2d is the adjoint of, so the roles swap: big = dy, small = x, padding
+// from that conv, the reduction over the B*Hin*Win small pixels.  Same kernels, same split plan, same slab reduction as the conv entry.
+static bool deconv_wgrad_same(int Hin, int Win, int Hout, int Wout, int sh, int sw) {
+    return cgs_ceil_div(Hout, sh) == Hin && cgs_ceil_div(Wout, sw) == Win;
+}
+
+size_t cgs_deconv_wgrad_ws_bytes(int B, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int kh, int kw, int sh, int sw) {
+    if (B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Hout <= 0 || Wout <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0) return 0;
+    if (!deconv_wgrad_same(Hin, Win, Hout, Wout, sh, sw)) return 0;
+    WgradParams p;
+    wgrad_geom(p, B, Hout, Wout, Cout, Hin, Win, Cin, kh, kw, sh, sw);
+    return wgrad_ws(p);
+}
+
+int cgs_deconv2d_nhwc_bwd_weight(const float* x, const float* dy, float* dw, int B, int Hin, int Win, int Cin, int Hout, int Wout, int Cout,
+                                 int kh, int kw, int sh, int sw, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+    if (B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Hout <= 0 || Wout <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 ||
+        !x || !dy || !dw)
+        return cgs_set_error(CGS_EINVAL, "deconv2d_nhwc_bwd_weight: bad argument");
+    if (!deconv_wgrad_same(Hin, Win, Hout, Wout, sh, sw))
+        return cgs_set_error(CGS_EINVAL, "deconv2d_nhwc_bwd_weight: 'SAME' geometry mismatch: big %dx%d stride %dx%d needs small %dx%d, got %dx%d",
+                             Hout, Wout, sh, sw, cgs_ceil_div(Hout, sh), cgs_ceil_div(Wout, sw), Hin, Win);
+    WgradParams p;
+    wgrad_geom(p, B, Hout, Wout, Cout, Hin, Win, Cin, kh, kw, sh, sw);
+    p.big = dy; p.small = x;
+    return wgrad_run(p, dw, accumulate, ws, ws_bytes, (hipStream_t)stream, "deconv2d_nhwc_bwd_weight");
+}
+
 int cgs_linear_bwd_weight(const float* x, const float* dy, float* dw, int B, int in, int out, int accumulate, void* ws,
                           size_t ws_bytes, void* stream) {
     if (B <= 0 || in <= 0 || out <= 0 || !x || !dy || !dw) return cgs_set_error(CGS_EINVAL, "linear_bwd_weight: bad argument");

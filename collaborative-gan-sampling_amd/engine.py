@@ -394,7 +394,8 @@ def compile_layers(layers, in_shape, P, scope, B, k, stride, bn_training, dev, f
         elif t == "bn":
             s = f"{scope}/{Lr[1]}"
             if bn_training:
-                leak, used = (K.LEAK, 2) if kind(i + 1) == "lrelu" else (1.0, 1)
+                # (a relu is the same kernels at leak 0: the generator in training mode, training.GStepper; no tape built before it has this pair)
+                leak, used = (K.LEAK, 2) if kind(i + 1) == "lrelu" else (0.0, 2) if kind(i + 1) == "relu" else (1.0, 1)
                 bn_stage = _BnTrainLrelu(B, shape, P[s + "/gamma"], P[s + "/beta"], leak, dev)
                 if stages and isinstance(stages[-1], _Conv):      # statistics ride on the producing conv's epilogue
                     bn_stage.part = stages[-1].want_stats(B)

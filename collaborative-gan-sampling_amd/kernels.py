@@ -772,6 +772,22 @@ def conv2d_bwd_weight(x, dy, kh, kw, sh=2, sw=2, out=None, accumulate=False):
     return dw
 
 
+def deconv2d_bwd_weight(x, dy, kh, kw, sh=2, sw=2, out=None, accumulate=False):
+    """dw[kh,kw,Cout,Cin] (+)= weight gradient of deconv2d_fwd(x, w) contracted with dy[B,Ho,Wo,Cout] (the generator's update)."""
+    _chk(x, "x"); _chk(dy, "dy")
+    B, H, W, Cin = x.shape
+    _, Ho, Wo, Cout = dy.shape
+    dw = out if out is not None else torch.empty((kh, kw, Cout, Cin), dtype=torch.float32, device=x.device)
+    need = int(L.load().cgs_deconv_wgrad_ws_bytes(B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw))
+    ws = _wgrad_workspace(need, x.device)
+    pr = _Prof(2.0 * B * H * W * Cin * kh * kw * Cout, "", _nb(x, dy, dw), op="wgrad_kernel") if PROFILE is not None else None
+    L.call("cgs_deconv2d_nhwc_bwd_weight", _ptr(x), _ptr(dy), _ptr(dw), B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw,
+           1 if accumulate else 0, _ptr(ws), ws.numel() * 4, _stream())
+    if pr is not None:
+        pr.done()
+    return dw
+
+
 def linear_bwd_weight(x, dy, out=None, accumulate=False):
     """dw[in,out] (+)= x^T dy."""
     _chk(x, "x"); _chk(dy, "dy")

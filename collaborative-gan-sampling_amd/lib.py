@@ -98,6 +98,8 @@ SIGNATURES = {
     "cgs_mlp2d_wide_g_step": (_i, [_p] * 6 + [_i, _i, _p, _p, _i, _f, _f, _p, _p, _p, _p, _z, _p]),
     "cgs_conv_wgrad_ws_bytes": (_z, [_i] * 9),
     "cgs_conv2d_nhwc_bwd_weight": (_i, [_p] * 3 + [_i] * 9 + [_i, _p, _z, _p]),
+    "cgs_deconv_wgrad_ws_bytes": (_z, [_i] * 11),
+    "cgs_deconv2d_nhwc_bwd_weight": (_i, [_p] * 3 + [_i] * 11 + [_i, _p, _z, _p]),
     "cgs_linear_bwd_weight": (_i, [_p] * 3 + [_i] * 3 + [_i, _p, _z, _p]),
     "cgs_bias_grad": (_i, [_p, _p, _i, _i, _i, _p, _z, _p]),
     "cgs_bn_train_param_grads": (_i, [_p, _i, _i, _p, _p, _i, _p]),

@@ -449,6 +449,14 @@ int cgs_mlp2d_wide_g_step(float* const* w, float* const* b, const float* const* 
 size_t cgs_conv_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw);
 int cgs_conv2d_nhwc_bwd_weight(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout,
                                int kh, int kw, int sh, int sw, int accumulate, void* ws, size_t ws_bytes, void* stream);
+/* dw[kh,kw,Cout,Cin] (+)= d/dw of deconv2d_nhwc_fwd(x, w) contracted with dy[B,Hout,Wout,Cout]: the generator's update (nsgan/GAN.py:132-146
+ * through nsgan/ops.py:48-67).  The same kernels, split plan and fixed-order slab reduction as the conv entry with the roles swapped (the filter
+ * is that of the 'SAME' conv Hout -> Hin: big = dy, small = x, reduction over the B*Hin*Win pixels of x); no atomics, a function of the inputs
+ * alone.  CGS_EINVAL unless (Hout, Wout) is a 'SAME' pre-image of (Hin, Win) (ceil(Hout/sh) == Hin, ceil(Wout/sw) == Win; the query then
+ * returns 0); CGS_EWORKSPACE below cgs_deconv_wgrad_ws_bytes of the same arguments. */
+size_t cgs_deconv_wgrad_ws_bytes(int B, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int kh, int kw, int sh, int sw);
+int cgs_deconv2d_nhwc_bwd_weight(const float* x, const float* dy, float* dw, int B, int Hin, int Win, int Cin, int Hout, int Wout, int Cout,
+                                 int kh, int kw, int sh, int sw, int accumulate, void* ws, size_t ws_bytes, void* stream);
 /* dw[in,out] (+)= x[B,in]^T dy[B,out]   (ws: cgs_conv_wgrad_ws_bytes(B,1,1,in,out,1,1,1,1)). */
 int cgs_linear_bwd_weight(const float* x, const float* dy, float* dw, int B, int in, int out, int accumulate,
                           void* ws, size_t ws_bytes, void* stream);
