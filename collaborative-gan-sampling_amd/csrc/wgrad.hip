@@ -227,15 +227,45 @@ __global__ void bce_grad_kernel(const float* __restrict__ l, float target, float
     if (loss_sum && threadIdx.x == 0) loss_sum[blockIdx.x] = red[0] * scale;
 }
 
+// One element of the Adam update: shared by adam_kernel and adam_multi_kernel, so both round every element the same way.
+__device__ __forceinline__ void adam_update(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ v, float lr_t, float b1, float b2, float eps, size_t i) {
+    const float gi = g[i];
+    const float mi = b1 * m[i] + (1.f - b1) * gi;
+    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi; v[i] = vi;
+    w[i] -= lr_t * mi / (sqrtf(vi) + eps);
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, float lr_t, float b1, float b2, float eps, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float gi = g[i];
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        w[i] -= lr_t * mi / (sqrtf(vi) + eps);
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        adam_update(w, g, m, v, lr_t, b1, b2, eps, i);
+}
+
+// The Adam step of a whole stepper in one launch: block b serves chunk plan[b] = elements [begin, begin + count) of slot plan[b].slot.
+// Table and plan live in device memory (built once by the host), and so does lr_t: the launch has the same arguments at every step,
+// so a captured hipGraph replays it unchanged.  Chunks are disjoint: no atomics.
+__global__ __launch_bounds__(256) void adam_multi_kernel(const cgs_adam_slot* __restrict__ table, const cgs_adam_chunk* __restrict__ plan,
+                                                         int n_slots, const float* __restrict__ lr_t_dev, float b1, float b2, float eps) {
+    const cgs_adam_chunk c = plan[blockIdx.x];
+    if ((unsigned)c.slot >= (unsigned)n_slots) return;          // (a plan that names no slot of the table: nothing is touched)
+    const cgs_adam_slot s = table[c.slot];
+    const float lr_t = *lr_t_dev;
+    const size_t end = (size_t)c.begin + (size_t)c.count < (size_t)s.n ? (size_t)c.begin + (size_t)c.count : (size_t)s.n;     // never past the slot
+    for (size_t i = (size_t)c.begin + threadIdx.x; i < end; i += blockDim.x)
+        adam_update(s.w, s.g, s.m, s.v, lr_t, b1, b2, eps, i);
+}
+
+// ops.bn's moving averages (nsgan/ops.py:19-26) of one norm from the batch statistics its training-mode forward saved
+__global__ void bn_moving_update_kernel(const float* __restrict__ mean, const float* __restrict__ invstd, float* __restrict__ moving_mean,
+                                        float* __restrict__ moving_var, int C, float keep, float take, float eps) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const float is = invstd[c];
+    const float var = 1.f / (is * is) - eps;           // the (biased) batch variance behind invstd = 1 / sqrt(var + eps)
+    moving_mean[c] = moving_mean[c] * keep + take * mean[c];
+    moving_var[c] = moving_var[c] * keep + take * var;
 }
 
 // gamma / beta gradients from the statistics cgs_bn_train_lrelu_bwd_data left in its workspace
@@ -318,6 +348,27 @@ int cgs_adam_step(float* w, const float* g, float* m, float* v, float lr_t, floa
     const unsigned blocks = (unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
     hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, g, m, v, lr_t, beta1, beta2, eps, n);
     CGS_CHECK_LAUNCH("adam_step");
+    return CGS_OK;
+}
+
+int cgs_adam_multi(const cgs_adam_slot* table, int n_slots, const cgs_adam_chunk* plan, int n_chunks, const float* lr_t, float beta1,
+                   float beta2, float eps, void* stream) {
+    if (n_slots <= 0 || !table) return cgs_set_error(CGS_EINVAL, "adam_multi: n_slots=%d table=%p", n_slots, (const void*)table);
+    if (n_chunks < 0 || (n_chunks > 0 && !plan) || !lr_t)
+        return cgs_set_error(CGS_EINVAL, "adam_multi: n_chunks=%d plan=%p lr_t=%p", n_chunks, (const void*)plan, (const void*)lr_t);
+    if (n_chunks == 0) return CGS_OK;              // every slot is empty
+    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, plan, n_slots, lr_t, beta1, beta2, eps);
+    CGS_CHECK_LAUNCH("adam_multi");
+    return CGS_OK;
+}
+
+int cgs_bn_moving_update(const float* mean, const float* invstd, float* moving_mean, float* moving_var, int C, double decay, float eps,
+                         void* stream) {
+    if (C <= 0 || !mean || !invstd || !moving_mean || !moving_var || !(decay >= 0.0 && decay <= 1.0))
+        return cgs_set_error(CGS_EINVAL, "bn_moving_update: bad argument (C=%d decay=%g)", C, decay);
+    hipLaunchKernelGGL(bn_moving_update_kernel, dim3(cgs_ceil_div(C, 128)), dim3(128), 0, (hipStream_t)stream, mean, invstd, moving_mean,
+                       moving_var, C, (float)decay, (float)(1.0 - decay), eps);
+    CGS_CHECK_LAUNCH("bn_moving_update");
     return CGS_OK;
 }
 

@@ -835,3 +835,68 @@ def bce_logits_grad(logits, target, scale, dlogits=None, loss=None):
 
 def adam_step(w, g, m, v, lr_t, beta1, beta2, eps):
     L.call("cgs_adam_step", _ptr(w), _ptr(g), _ptr(m), _ptr(v), float(lr_t), float(beta1), float(beta2), float(eps), w.numel(), _stream())
+
+
+# ----------------------------------------------------------------------------- one Adam launch per optimizer, lr_t in device memory
+ADAM_CHUNK = 2048       # elements per block of cgs_adam_multi (8 per thread): a 6.4 M-element weight is 3136 blocks, a bias one
+
+
+def adam_chunk_plan(sizes, chunk=ADAM_CHUNK):
+    """The block -> (slot, begin, count) map of ``cgs_adam_multi`` for slots of ``sizes`` elements: chunks of at most ``chunk`` elements,
+    in slot order, none crossing a slot, every element in exactly one; a slot of 0 elements gets none.  len(result) is the grid size."""
+    if chunk <= 0:
+        raise ValueError(f"adam_chunk_plan: chunk={chunk}")
+    plan = []
+    for slot, n in enumerate(sizes):
+        if n < 0:
+            raise ValueError(f"adam_chunk_plan: slot {slot} has {n} elements")
+        for begin in range(0, n, chunk):
+            plan.append((slot, begin, min(chunk, n - begin)))
+    return plan
+
+
+class AdamTable:
+    """The (w, g, m, v) slots of one optimizer as ``cgs_adam_multi`` reads them: the slot table, the chunk plan and the ``lr_t`` scalar, all in
+    device memory and built once.  Holds the tensors, so the raw addresses in the table stay valid as long as the table lives."""
+
+    def __init__(self, slots):
+        import numpy as np
+        self.slots = [tuple(s) for s in slots]
+        if not self.slots:
+            raise L.CgsError("AdamTable: no slots")
+        dev = self.slots[0][0].device
+        for i, (w, g, m, v) in enumerate(self.slots):
+            for t, what in ((w, "w"), (g, "g"), (m, "m"), (v, "v")):
+                _chk(t, f"AdamTable slot {i} {what}")
+                if t.device != dev or t.numel() != w.numel():
+                    raise L.CgsError(f"AdamTable slot {i}: {what} has {t.numel()} elements on {t.device}, w {w.numel()} on {dev}")
+        table = np.zeros(len(self.slots), dtype=np.dtype([("w", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<u8")]))
+        for i, (w, g, m, v) in enumerate(self.slots):
+            table[i] = (w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), w.numel())
+        chunks = adam_chunk_plan([s[0].numel() for s in self.slots])
+        plan = np.zeros(len(chunks), dtype=np.dtype([("slot", "<i4"), ("count", "<u4"), ("begin", "<u8")]))
+        for i, c in enumerate(chunks):
+            plan[i] = (c[0], c[2], c[1])
+        self.n_chunks = len(chunks)
+        self.table = torch.from_numpy(table.view(np.uint8).copy()).to(dev)
+        self.plan = torch.from_numpy(plan.view(np.uint8).copy()).to(dev) if chunks else None
+        self.lr_t = torch.zeros(1, dtype=torch.float32, device=dev)
+
+    def step(self, lr_t, b1, b2, eps):
+        """One Adam step of every slot.  ``lr_t`` reaches the device scalar by a stream-ordered fill (the value rides as that kernel's
+        argument: nothing on the host has to outlive the call); the update launch itself has the same arguments every time.
+        ``lr_t=None``: the update alone, at whatever the device scalar holds -- what a captured program records, its owner filling
+        ``self.lr_t`` before every replay."""
+        if lr_t is not None:
+            self.lr_t.fill_(float(lr_t))
+        L.call("cgs_adam_multi", _ptr(self.table), len(self.slots), _ptr(self.plan), self.n_chunks, _ptr(self.lr_t),
+               float(b1), float(b2), float(eps), _stream())
+
+
+def bn_moving_update(mean, invstd, moving_mean, moving_var, decay, eps=BN_EPS):
+    """ops.bn's moving averages of one norm from its saved batch statistics, in place, in one launch."""
+    _chk(mean, "mean"); _chk(invstd, "invstd"); _chk(moving_mean, "moving_mean"); _chk(moving_var, "moving_var")
+    C = mean.numel()
+    if invstd.numel() != C or moving_mean.numel() != C or moving_var.numel() != C:
+        raise L.CgsError(f"bn_moving_update: {C} / {invstd.numel()} / {moving_mean.numel()} / {moving_var.numel()} channels")
+    L.call("cgs_bn_moving_update", _ptr(mean), _ptr(invstd), _ptr(moving_mean), _ptr(moving_var), C, float(decay), float(eps), _stream())

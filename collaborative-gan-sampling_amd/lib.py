@@ -105,6 +105,8 @@ SIGNATURES = {
     "cgs_bn_train_param_grads": (_i, [_p, _i, _i, _p, _p, _i, _p]),
     "cgs_bce_logits_grad": (_i, [_p, _f, _f, _p, _p, _i, _p]),
     "cgs_adam_step": (_i, [_p, _p, _p, _p, _f, _f, _f, _f, _z, _p]),
+    "cgs_adam_multi": (_i, [_p, _i, _p, _i, _p, _f, _f, _f, _p]),
+    "cgs_bn_moving_update": (_i, [_p, _p, _p, _p, _i, C.c_double, _f, _p]),
 }
 
 _lib = None

@@ -39,6 +39,7 @@ class DShaper:
                     g = torch.zeros_like(p)
                     setattr(st, "g_" + n, g)
                     self.slots.append((p, g, torch.zeros_like(p), torch.zeros_like(p)))
+        self.table = None       # a kernels.AdamTable over ``slots`` while a GanTrainer records this step into a hipGraph (training.py)
 
     # -- one backward pass with parameter gradients ------------------------------------------------------
     def _backward(self, dy, accumulate):
@@ -83,6 +84,11 @@ class DShaper:
     def step(self, real, refined):
         """One Adam step of D (nsgan/GAN.py:272).  Returns d_loss before the update."""
         loss = self.loss_and_grads(real, refined)
+        if self.table is not None:          # being recorded: one launch at the lr_t its owner writes into device memory; ``t`` is the owner's
+            with torch.cuda.device(self.dev):
+                self.table.step(None, self.b1, self.b2, self.eps)
+            K.WS.invalidate()
+            return loss
         self.t += 1
         lr_t = self.lr * math.sqrt(1.0 - self.b2 ** self.t) / (1.0 - self.b1 ** self.t)      # tf.train.AdamOptimizer
         with torch.cuda.device(self.dev):

@@ -7,6 +7,7 @@ gradients (wgrad.hip: ``cgs_deconv2d_nhwc_bwd_weight`` for the transposed convol
 place on the same parameter tensors the ``RefineEngine`` and the ``DShaper`` read.  ``GanTrainer`` strings the two steps into the
 reference's iteration, so the package can produce the checkpoint it then shapes and refines.
 """
+import gc
 import math
 
 import torch
@@ -56,6 +57,7 @@ class GStepper:
                     setattr(st, "g_" + n, g)
                     self.slots.append((p, g, torch.zeros_like(p), torch.zeros_like(p)))
                     self.names.append(name_of[id(p)])
+        self.table = None       # a kernels.AdamTable over ``slots`` while a GanTrainer records the step into a hipGraph
 
     # -- G in training mode ------------------------------------------------------------------------------
     def forward(self, z):
@@ -66,6 +68,10 @@ class GStepper:
             for i, st in enumerate(self.g.stages):
                 self.x_in[i] = x
                 x = st.fwd(x)
+            if self.table is not None:                         # being recorded: one launch per norm
+                for st, mm, mv in self.moving:
+                    K.bn_moving_update(st.mean, st.invstd, mm, mv, BN_DECAY, K.BN_EPS)
+                return x
             with torch.no_grad():
                 for st, mm, mv in self.moving:
                     var = st.invstd.pow(-2).sub_(K.BN_EPS)     # the (biased) batch variance behind invstd = 1 / sqrt(var + eps)
@@ -114,6 +120,11 @@ class GStepper:
     def step(self, z):
         """One Adam step of G (nsgan/GAN.py:223).  Returns g_loss before the update."""
         loss = self.loss_and_grads(z)
+        if self.table is not None:          # being recorded: one launch at the lr_t its owner writes into device memory; ``t`` is the owner's
+            with torch.cuda.device(self.dev):
+                self.table.step(None, self.b1, self.b2, self.eps)
+            K.WS.invalidate()
+            return loss
         self.t += 1
         lr_t = self.lr * math.sqrt(1.0 - self.b2 ** self.t) / (1.0 - self.b1 ** self.t)      # tf.train.AdamOptimizer
         with torch.cuda.device(self.dev):
@@ -127,22 +138,104 @@ class GStepper:
 
 
 class GanTrainer:
-    """The reference's train loop body (nsgan/GAN.py:219-223) on one parameter store: a D step on (real, G(z)), then a G step on the same z."""
+    """The reference's train loop body (nsgan/GAN.py:219-223) on one parameter store: a D step on (real, G(z)), then a G step on the same z.
 
-    def __init__(self, arch, params, batch_size, device="cuda:0", learning_rate=2e-4, beta1=0.5, engine=None):
+    ``use_graph=True``: the whole iteration is captured once as a hipGraph and replayed.  The first call runs eagerly on the trainer's own
+    side stream (a train step has side effects, so the warm-up is a real iteration; it also brings the stream-keyed workspaces to their final
+    size), the second captures and replays, later ones replay.  ``path`` names what the last call ran, ``graph_fallback`` why a capture was
+    refused (the trainer then goes on with eager launches)."""
+
+    def __init__(self, arch, params, batch_size, device="cuda:0", learning_rate=2e-4, beta1=0.5, engine=None, use_graph=False):
         self.arch, self.P = arch, params
         self.dshaper = DShaper(arch, params, batch_size, device, learning_rate=learning_rate, beta1=beta1)
         self.gstepper = GStepper(arch, params, batch_size, device, learning_rate=learning_rate, beta1=beta1)
         self.engine = engine                # an optional RefineEngine on the same parameter tensors: kept coherent after every iteration
+        self.use_graph = bool(use_graph)
+        self.path, self.graph_fallback = "eager", None
+        self._graph = self._gstream = self._out = self._tables = None
+        self._warm = False
+        if self.use_graph:
+            gs = self.gstepper
+            f32 = dict(dtype=torch.float32, device=gs.dev)
+            self._real = torch.empty((gs.B,) + tuple(gs.A["img"]), **f32)
+            self._z = torch.empty((gs.B,) + tuple(g_input_shape(gs.A)), **f32)
 
-    def iteration(self, real, z):
-        """-> (d_loss, g_loss), both before their update.  G runs in training mode in both steps: its moving averages move twice."""
+    def _program(self, real, z):
         fake = self.gstepper.forward(z)
         d_loss = self.dshaper.step(real, fake)
         g_loss = self.gstepper.step(z)
+        return d_loss, g_loss
+
+    def iteration(self, real, z):
+        """-> (d_loss, g_loss), both before their update.  G runs in training mode in both steps: its moving averages move twice."""
+        if self.use_graph and self.graph_fallback is None and K.PROFILE is None:
+            out = self._graph_iteration(real, z)
+        else:
+            self.path = "eager"
+            out = self._program(real, z)
         if self.engine is not None:
             self.engine.refresh_weights()
-        return d_loss, g_loss
+        return out
+
+    # -- the captured form ---------------------------------------------------------------------------------
+    def _capture(self):
+        """Record ``_program`` on the static inputs.  Weights change at every replay, so the program must CONTAIN the pack kernels: every
+        packed copy is marked stale first, and the first use of each weight (and again after D's Adam) re-packs into the buffer the warm-up made."""
+        steppers = (self.dshaper, self.gstepper)
+        if self._tables is None:
+            self._tables = [K.AdamTable(st.slots) for st in steppers]
+        torch.cuda.synchronize(self.gstepper.dev)
+        gc_was_on = gc.isenabled()
+        gc.disable()                        # (a finalizer that reaches HIP inside a capture aborts the process: engine.py, refine)
+        for st, tb in zip(steppers, self._tables):
+            st.table = tb
+        try:
+            K.WS.invalidate()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=self._gstream, capture_error_mode="thread_local"):
+                out = self._program(self._real, self._z)
+        except L.CgsError:
+            raise
+        except Exception as ex:             # noqa: BLE001 (HIP / the allocator / another thread's HIP call refused the capture)
+            raise L.GraphCaptureError(f"{type(ex).__name__}: {str(ex)[:300]}") from ex
+        finally:
+            for st in steppers:
+                st.table = None
+            K.WS.invalidate()               # the host cache's versions describe a program that was recorded, not run
+            if gc_was_on:
+                gc.enable()
+        self._graph, self._out = g, out
+
+    def _graph_iteration(self, real, z):
+        gs = self.gstepper
+        for t, buf, what in ((real, self._real, "real"), (z, self._z, "z")):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(buf.shape):
+                raise L.CgsError(f"GanTrainer.iteration: {what} is {tuple(getattr(t, 'shape', ()))}, the trainer was built for {tuple(buf.shape)}")
+        with torch.cuda.device(gs.dev):
+            if self._gstream is None:
+                self._gstream = torch.cuda.Stream(gs.dev)
+            cur = torch.cuda.current_stream(gs.dev)
+            self._gstream.wait_stream(cur)
+            with torch.cuda.stream(self._gstream):
+                self._real.copy_(real)
+                self._z.copy_(z)
+                if self._warm and self._graph is None:
+                    try:
+                        self._capture()
+                    except L.GraphCaptureError as ex:
+                        self.graph_fallback = str(ex)
+                if not self._warm or self._graph is None:
+                    self.path, self._warm = "eager", True
+                    out = self._program(self._real, self._z)
+                else:
+                    for st, tb in zip((self.dshaper, gs), self._tables):
+                        st.t += 1
+                        tb.lr_t.fill_(st.lr * math.sqrt(1.0 - st.b2 ** st.t) / (1.0 - st.b1 ** st.t))      # tf.train.AdamOptimizer
+                    self._graph.replay()
+                    K.WS.invalidate()       # the replay re-packed and then updated the weights behind the host cache's back
+                    self.path, out = "graph", self._out
+            cur.wait_stream(self._gstream)
+            return out[0].clone(), out[1].clone()        # fresh tensors on the caller's stream: later iterations leave them alone
 
     def save(self, path):
         """The TF key space of ``checkpoint.py`` (variables only: Adam's slots are not part of it, as ``clean_tf_names`` drops them)."""

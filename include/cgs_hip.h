@@ -472,6 +472,33 @@ int cgs_bce_logits_grad(const float* logits, float target, float scale, float* d
  * w -= lr_t * m / (sqrt(v) + eps), lr_t = lr*sqrt(1-b2^t)/(1-b1^t) supplied by the caller. */
 int cgs_adam_step(float* w, const float* g, float* m, float* v, float lr_t, float beta1, float beta2, float eps,
                   size_t n, void* stream);
+/* The Adam step of EVERY variable of one optimizer in one launch (the d_optim / g_optim of nsgan/GAN.py:141-146, as
+ * training.GanTrainer's captured iteration runs them: cgs_amd/kernels.py::AdamTable.step).  `table` [n_slots] and `plan` [n_chunks] are
+ * DEVICE arrays the host builds once: block b of the launch updates elements [begin, begin + count) of slot plan[b].slot, chunks are
+ * disjoint, never cross a slot, and cover every element once (kernels.adam_chunk_plan).  A slot with n == 0 is legal and gets no chunk.
+ * `lr_t` is read from DEVICE memory, so the launch has the same arguments at every step and a captured hipGraph replays it; the
+ * host writes the step's value there in stream order.  Per element the arithmetic is cgs_adam_step's own (one shared device
+ * function).  No atomics, no host synchronisation.  Refuses n_slots <= 0, a null table, a null lr_t, a null plan with n_chunks > 0. */
+typedef struct cgs_adam_slot {
+    float* w;
+    const float* g;
+    float* m;
+    float* v;
+    unsigned long long n;
+} cgs_adam_slot;
+typedef struct cgs_adam_chunk {
+    int slot;
+    unsigned count;
+    unsigned long long begin;
+} cgs_adam_chunk;
+int cgs_adam_multi(const cgs_adam_slot* table, int n_slots, const cgs_adam_chunk* plan, int n_chunks, const float* lr_t,
+                   float beta1, float beta2, float eps, void* stream);
+/* The moving averages of one batch norm (ops.bn, nsgan/ops.py:19-26, as generator(z, is_training=True) moves them at nsgan/GAN.py:120) from
+ * the statistics its training-mode forward saved: moving_mean = decay * moving_mean + (1 - decay) * mean, and the same for moving_var with
+ * the biased batch variance 1 / invstd^2 - eps.  One launch per norm (training.GStepper.forward on the captured path).  `decay` is a
+ * double so that 1 - decay is rounded to float once. */
+int cgs_bn_moving_update(const float* mean, const float* invstd, float* moving_mean, float* moving_var, int C, double decay,
+                         float eps, void* stream);
 
 #ifdef __cplusplus
 }
