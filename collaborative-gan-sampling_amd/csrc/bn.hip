@@ -743,6 +743,12 @@ size_t cgs_instnorm_ws_bytes(int B, int HW, int C) {
     return ((size_t)B * g.G * 2 * C + (size_t)B * 6 * C) * sizeof(float);   // partials | stat[B][4][C] | stat2[B][2][C]
 }
 
+// floats in front of stat2[B][2][C] in that workspace: where cgs_instnorm_lrelu_bwd_data leaves {mean(d), mean(d * xhat)} of every
+// sample (on both of its paths) and cgs_instnorm_param_grads (wgrad_dot.hip) reads them
+size_t cgs_instnorm_stat2_offset(int B, int HW, int C) {
+    return (size_t)B * in_geom(B, HW).G * 2 * C + (size_t)B * 4 * C;
+}
+
 int cgs_instnorm_lrelu_fwd(const float* x, const float* scale, const float* offset, float eps, float leak, float* y,
                            float* mean, float* invstd, int B, int HW, int C, void* ws, size_t ws_bytes, void* stream) {
     if (B <= 0 || HW <= 0 || C <= 0 || (C & 3) || B > 65535) return cgs_set_error(CGS_EINVAL, "instnorm fwd: B=%d HW=%d C=%d", B, HW, C);
@@ -834,8 +840,7 @@ int cgs_instnorm_lrelu_bwd_data(const float* dy, const float* x, const float* sc
     hipStream_t s = (hipStream_t)stream;
     const BnGeom g = in_geom(B, HW);
     float* part = (float*)ws;
-    float* stat = part + (size_t)B * g.G * 2 * C;
-    float* stat2 = stat + (size_t)B * 4 * C;
+    float* stat2 = part + cgs_instnorm_stat2_offset(B, HW, C);
     if (norm_small_ok(HW)) {
         hipLaunchKernelGGL(norm_small_kernel<true>, dim3(cgs_ceil_div(C, 64), B), dim3(256), 0, s, x, dy, scale, offset, 0.f, leak, dx, (float*)mean, (float*)invstd, stat2, HW, C);
         CGS_CHECK_LAUNCH("instnorm_lrelu_bwd_data");

@@ -43,6 +43,7 @@ struct CgsLayer {
 };
 
 #define CGS_BN_MAX_BLOCKS 512   // stage-1 partial blocks of the per-channel reductions (bn.hip workspace layout)
+size_t cgs_instnorm_stat2_offset(int B, int HW, int C);   // floats in front of stat2[B][2][C] in an instance norm's workspace (bn.hip)
 #define CGS_BK 32           // K-tile of the implicit GEMM
 #define CGS_MAX_CLASSES 4   // stride <= 2 for the T direction
 

@@ -772,6 +772,29 @@ def conv2d_bwd_weight(x, dy, kh, kw, sh=2, sw=2, out=None, accumulate=False):
     return dw
 
 
+def conv_wgrad_cout1_ok(x_shape, kh, kw, sh, sw):
+    """Does the one-output-channel weight gradient (conv2d_bwd_weight_cout1) take this call?  (the library's own answer: its workspace query)"""
+    B, H, W, Cin = x_shape
+    return int(L.load().cgs_conv_wgrad_cout1_ws_bytes(B, H, W, Cin, kh, kw, sh, sw)) > 0
+
+
+def conv2d_bwd_weight_cout1(x, dy, kh, kw, sh=2, sw=2, out=None, accumulate=False):
+    """dw[kh,kw,Cin,1] (+)= weight gradient of conv2d_fwd to ONE output channel over a deep reduction (Cin % 4 == 0,
+    kh * kw * Cin >= 1024, sh == sw: the PatchGAN logit head); dy: [B,Ho,Wo,1].  Any other shape is an error: conv2d_bwd_weight serves it."""
+    _chk(x, "x"); _chk(dy, "dy")
+    B, H, W, Cin = x.shape
+    if dy.shape[3] != 1:
+        raise L.CgsError(f"conv2d_bwd_weight_cout1: dy has {dy.shape[3]} channels")
+    dw = out if out is not None else torch.empty((kh, kw, Cin, 1), dtype=torch.float32, device=x.device)
+    ws = _wgrad_workspace(int(L.load().cgs_conv_wgrad_cout1_ws_bytes(B, H, W, Cin, kh, kw, sh, sw)), x.device)
+    pr = _Prof(2.0 * B * dy.shape[1] * dy.shape[2] * kh * kw * Cin, "", _nb(x, dy, dw), op="wgrad_cout1_kernel") if PROFILE is not None else None
+    L.call("cgs_conv2d_nhwc_bwd_weight_cout1", _ptr(x), _ptr(dy), _ptr(dw), B, H, W, Cin, kh, kw, sh, sw,
+           1 if accumulate else 0, _ptr(ws), ws.numel() * 4, _stream())
+    if pr is not None:
+        pr.done()
+    return dw
+
+
 def deconv2d_bwd_weight(x, dy, kh, kw, sh=2, sw=2, out=None, accumulate=False):
     """dw[kh,kw,Cout,Cin] (+)= weight gradient of deconv2d_fwd(x, w) contracted with dy[B,Ho,Wo,Cout] (the generator's update)."""
     _chk(x, "x"); _chk(dy, "dy")
@@ -823,6 +846,15 @@ def bn_train_param_grads(x, dgamma, dbeta, accumulate=False):
     M = x.numel() // C
     ws = _bn_workspace(M, C, x.device)
     L.call("cgs_bn_train_param_grads", _ptr(ws), M, C, _ptr(dgamma), _ptr(dbeta), 1 if accumulate else 0, _stream())
+
+
+def instnorm_param_grads(x, dscale, doffset, accumulate=False):
+    """(dscale, doffset) (+)= from the per-sample sums the instnorm_lrelu_bwd_data call JUST made on ``x`` (same stream, so the same
+    workspace) left in its workspace; x: the norm's input [B,H,W,C]."""
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * C)
+    ws = _in_workspace(B, HW, C, x.device)
+    L.call("cgs_instnorm_param_grads", _ptr(ws), B, HW, C, _ptr(dscale), _ptr(doffset), 1 if accumulate else 0, _stream())
 
 
 def bce_logits_grad(logits, target, scale, dlogits=None, loss=None):

@@ -103,6 +103,9 @@ SIGNATURES = {
     "cgs_linear_bwd_weight": (_i, [_p] * 3 + [_i] * 3 + [_i, _p, _z, _p]),
     "cgs_bias_grad": (_i, [_p, _p, _i, _i, _i, _p, _z, _p]),
     "cgs_bn_train_param_grads": (_i, [_p, _i, _i, _p, _p, _i, _p]),
+    "cgs_instnorm_param_grads": (_i, [_p, _i, _i, _i, _p, _p, _i, _p]),
+    "cgs_conv_wgrad_cout1_ws_bytes": (_z, [_i] * 8),
+    "cgs_conv2d_nhwc_bwd_weight_cout1": (_i, [_p] * 3 + [_i] * 8 + [_i, _p, _z, _p]),
     "cgs_bce_logits_grad": (_i, [_p, _f, _f, _p, _p, _i, _p]),
     "cgs_adam_step": (_i, [_p, _p, _p, _p, _f, _f, _f, _f, _z, _p]),
     "cgs_adam_multi": (_i, [_p, _i, _p, _i, _p, _f, _f, _f, _p]),

@@ -6,6 +6,10 @@ mode: batch statistics in both passes; Adam beta1 = 0.5, learning rate 1e-5 in r
 that step on the GPU over the same stage tape the refiner uses: forward, backward-data with the activation
 gradients folded into the epilogues, plus the weight / bias / gamma / beta gradients (wgrad.hip) and the Adam update,
 in place on the parameter tensors the ``RefineEngine`` reads -- so the next refinement sees the shaped D.
+
+The same step serves the PatchGAN discriminator of BASELINE config 5 (``cyclegan*``: instance norms, a logit MAP): the loss is the mean
+over every patch logit, the instance norms' ``scale`` / ``offset`` are trained like a batch norm's gamma / beta, and the one-channel
+logit head takes its weight gradient from the dot-product kernel (csrc/wgrad_dot.hip).
 """
 import math
 
@@ -13,8 +17,13 @@ import torch
 
 from . import kernels as K
 from . import lib as L
-from .engine import Tape, _BnTrainLrelu, _Conv, _Linear, _View, link_backward_fusion
+from .engine import Tape, _BnTrainLrelu, _Conv, _InstNormAct, _Linear, _View, link_backward_fusion
 from .nets import ARCHS
+
+
+# A conv stage with ONE output channel that the dot-product weight gradient takes (Cin % 4 == 0, kh * kw * Cin >= 1024: cyclegan's d_c5)
+# uses it instead of the 128-column GEMM tile (the same-process A/B: DESIGN.md section 17).  False: every conv on the generic kernel.
+COUT1_WGRAD = True
 
 
 class DShaper:
@@ -33,7 +42,11 @@ class DShaper:
             # trainable tensors (the d_vars of nsgan/GAN.py:136) with gradient and Adam slots
             self.slots = []        # (param, grad, m, v)
             for st in self.tape.stages:
-                names = ("w", "b") if isinstance(st, (_Conv, _Linear)) else ("gamma", "beta") if isinstance(st, _BnTrainLrelu) else ()
+                names = (("w", "b") if isinstance(st, (_Conv, _Linear)) else ("gamma", "beta") if isinstance(st, _BnTrainLrelu)
+                         else ("scale", "offset") if isinstance(st, _InstNormAct) else ())
+                if isinstance(st, _Conv):       # one output channel over a deep reduction (the PatchGAN logit head): the dot-product weight gradient
+                    kh, kw, _, cout = st.w.shape
+                    st.wgrad_cout1 = COUT1_WGRAD and cout == 1 and K.conv_wgrad_cout1_ok((self.B,) + tuple(st.dx.shape[1:]), kh, kw, st.s, st.s)
                 for n in names:
                     p = getattr(st, n)
                     g = torch.zeros_like(p)
@@ -52,6 +65,11 @@ class DShaper:
             elif isinstance(st, _BnTrainLrelu):
                 dy = st.bwd(dy)                                            # dx in place; statistics stay in the bn workspace
                 K.bn_train_param_grads(st.x, st.g_gamma, st.g_beta, accumulate)
+            elif isinstance(st, _InstNormAct):
+                if st.bstat is not None:
+                    raise L.CgsError("DShaper: the instance norm's parameter gradients need the separate-pass backward (its per-sample sums)")
+                dy = st.bwd(dy)                                            # dx in place; the per-sample sums stay in the instance norm's workspace
+                K.instnorm_param_grads(st.x, st.g_scale, st.g_offset, accumulate)
             elif isinstance(st, _Linear):
                 if st.epi == L.EPI_LRELU and not st.pre_folded:
                     dy = K.lrelu_bwd(dy, st.out, out=dy)
@@ -63,7 +81,10 @@ class DShaper:
                 if st.epi == L.EPI_LRELU and not st.pre_folded:
                     dy = K.lrelu_bwd(dy, st.out, out=dy)
                 kh, kw = st.w.shape[0], st.w.shape[1]
-                K.conv2d_bwd_weight(st.x_in, dy, kh, kw, st.s, st.s, out=st.g_w, accumulate=accumulate)
+                if st.wgrad_cout1:
+                    K.conv2d_bwd_weight_cout1(st.x_in, dy, kh, kw, st.s, st.s, out=st.g_w, accumulate=accumulate)
+                else:
+                    K.conv2d_bwd_weight(st.x_in, dy, kh, kw, st.s, st.s, out=st.g_w, accumulate=accumulate)
                 K.bias_grad(dy, out=st.g_b, accumulate=accumulate)
                 if not first:
                     e, a, aux = st.bwd_epi
@@ -104,6 +125,7 @@ class DShaper:
 def shape_step(engine, shaper, z, real, steps, rate, indices=None):
     """One iteration of the reference's D-shaping loop (nsgan/GAN.py:266-272):
     ``batch_refine = sess.run(g_refine_proba, {z, inputs}); sess.run([d_optim, d_loss], {inputs: real, G: batch_refine})``.
+    ``z``: what the generator's head consumes -- the noise batch, or the source images of an image-to-image net (``cyclegan*``).
     ``indices``: the probabilistic step draw; the reference bakes ONE draw into the graph for all batches
     (collaborator.py:54-56) -- pass the same array every call to reproduce that, or None to redraw per call."""
     import numpy as np
@@ -111,5 +133,14 @@ def shape_step(engine, shaper, z, real, steps, rate, indices=None):
         indices = np.random.randint(steps + 1, size=engine.B)
     refined = engine.refine_from_z(z, steps, rate, mode="probabilistic", indices=indices)[0]
     loss = shaper.step(real, refined)
+    engine.refresh_weights()
+    return loss
+
+
+def calibrate_step(engine, shaper, z, real):
+    """One iteration of the reference's ``calibrate`` branch (nsgan/GAN.py:273-275): the D step on the generator's UNREFINED samples,
+    ``sess.run([d_optim, d_loss], {z, inputs: real})`` with ``G = generator(z)``.  ``z`` as in ``shape_step``; every arch."""
+    fake = engine.generate(z)
+    loss = shaper.step(real, fake)
     engine.refresh_weights()
     return loss

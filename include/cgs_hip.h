@@ -465,6 +465,22 @@ int cgs_bias_grad(const float* dy, float* db, int M, int C, int accumulate, void
 /* dgamma, dbeta (+)= from the statistics the immediately preceding cgs_bn_train_lrelu_bwd_data call left in ITS
  * workspace `bwd_ws` (same M, C). */
 int cgs_bn_train_param_grads(const void* bwd_ws, int M, int C, float* dgamma, float* dbeta, int accumulate, void* stream);
+/* The D step of a PatchGAN discriminator (BASELINE config 5; the reference ships no code for it: the same step, nsgan/GAN.py:270-272,
+ * on a logit MAP -- shaping.DShaper._backward).
+ * dscale, doffset [C] (+)= the instance norm's parameter gradients from the per-sample sums {mean(d), mean(d * xhat)} the immediately
+ * preceding cgs_instnorm_lrelu_bwd_data call left in ITS workspace `bwd_ws` (same B, HW, C; either of its paths):
+ * doffset[c] = HW * sum_b mean_b(d), dscale[c] = HW * sum_b mean_b(d * xhat), the samples added in ascending order in double.
+ * Deterministic, no atomics. */
+int cgs_instnorm_param_grads(const void* bwd_ws, int B, int HW, int C, float* dscale, float* doffset, int accumulate, void* stream);
+/* dw[kh,kw,Cin] (+)= weight gradient of a 'SAME' convolution to ONE output channel over a deep reduction, dy [B,Ho,Wo] (the PatchGAN
+ * logit head 4x4 x 512 -> 1; the backward-weight twin of the forward's dot-product family, wgrad_dot.hip).  Takes what that family
+ * takes: Cin % 4 == 0, kh * kw * Cin >= 1024, sh == sw, x 16-byte aligned; anything else is CGS_EINVAL before any launch (the query
+ * then returns 0) -- cgs_conv2d_nhwc_bwd_weight serves every shape.  The B * Ho * Wo pixels are cut into slabs, one partial dw per slab
+ * in the workspace, added in slab order: no atomics, a function of the inputs alone.  Padding taps are not read.
+ * ws: cgs_conv_wgrad_cout1_ws_bytes of the same arguments, 16-byte aligned; CGS_EWORKSPACE if smaller. */
+size_t cgs_conv_wgrad_cout1_ws_bytes(int B, int H, int W, int Cin, int kh, int kw, int sh, int sw);
+int cgs_conv2d_nhwc_bwd_weight_cout1(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int kh, int kw,
+                                     int sh, int sw, int accumulate, void* ws, size_t ws_bytes, void* stream);
 /* dlogits[i] = scale*(sigmoid(logits[i]) - target); loss_sum[0] = scale * sum_i BCE(logits[i], target) (may be NULL).
  * tf.nn.sigmoid_cross_entropy_with_logits + reduce_mean (nsgan/GAN.py:126-131) with scale = 1/n. */
 int cgs_bce_logits_grad(const float* logits, float target, float scale, float* dlogits, float* loss_sum, int n, void* stream);
