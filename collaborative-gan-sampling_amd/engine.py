@@ -688,6 +688,47 @@ class RefineEngine:
         self._sync_weights()
         return K.sigmoid_rowmean(self.d.forward(images), out=out)
 
+    def _feature_stage(self):
+        """The stage of D whose output is the activation after the last nonlinearity in front of the logit layer."""
+        stages = self.d.stages
+        head = max(i for i, st in enumerate(stages) if isinstance(st, (_Linear, _Conv)))
+        i = head - 1
+        while i >= 0 and isinstance(stages[i], _View):
+            i -= 1
+        st = stages[i] if i >= 0 else None
+        # every stage type applies its activation in its own forward launch (conv / linear epilogues, norm + lrelu, unary), so the
+        # activation is already in the stage's buffer whatever the backward pass folded into a neighbour
+        active = (isinstance(st, (_Conv, _Linear)) and st.epi != L.EPI_NONE) or (isinstance(st, (_BnTrainLrelu, _InstNormAct)) and st.leak != 1.0) \
+            or isinstance(st, _Unary)
+        if not active:
+            raise L.CgsError("score_with_features: no nonlinearity in front of the discriminator's logit layer")
+        return st
+
+    def feature_width(self):
+        """d of ``score_with_features``: the channels (or units) of D's last activation in front of the logit layer."""
+        return int(self._feature_stage().out.shape[-1])
+
+    @_entry
+    def score_with_features(self, images, out=None, feat_out=None):
+        """``score`` plus D's features from the SAME forward pass: (sigmoids [B, 1], features [B, d]).  The features are D's activations
+        after the last nonlinearity in front of the logit layer, mean-pooled over space when that activation is a map (d = 512 for
+        dcgan32 / dcgan64 / cyclegan256, 1024 for mnist) -- batch statistics per logical batch under ``bn_groups``, as in ``score``.  The
+        sigmoids are those of ``score``.  Without ``feat_out`` the features are an engine-owned buffer, valid until the next call."""
+        self._sync_weights()
+        st = self._feature_stage()
+        sig = K.sigmoid_rowmean(self.d.forward(images), out=out)
+        act = st.out
+        if act.dim() == 2:
+            if feat_out is None:
+                return sig, act
+            feat_out.copy_(act)
+            return sig, feat_out
+        if feat_out is None:
+            if getattr(self, "_feat", None) is None:
+                self._feat = torch.empty((act.shape[0], act.shape[-1]), dtype=torch.float32, device=self.dev)
+            feat_out = self._feat
+        return sig, K.spatial_mean(act, out=feat_out)
+
     def forward_logits(self, theta, logit_out):
         x = self.g_tail.forward(theta)
         head = self.d.stages[-1]

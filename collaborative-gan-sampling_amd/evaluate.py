@@ -92,7 +92,7 @@ class FusedProposer:
     stream + pinned result buffers each)."""
 
     def __init__(self, gan, steps, rate, batch=None, groups=32, depth=2, method="momentum", mode="deterministic", contraction="f32",
-                 use_graph=True, indices=None):
+                 use_graph=True, indices=None, features=False):
         import torch
         from .engine import RefineEngine
         self.torch = torch
@@ -113,6 +113,12 @@ class FusedProposer:
         self.sig_host = [torch.empty((n, 1), dtype=torch.float32).pin_memory() for _ in range(depth)]
         self.sig_dev = [torch.empty((n, 1), dtype=torch.float32, device=self.dev) for _ in range(depth)]
         self.done = [torch.cuda.Event() for _ in range(depth)]
+        # features=True: every launch also keeps D's features of the round (engine.score_with_features) in a per-slot DEVICE buffer;
+        # nothing more is copied to the host -- ``accumulate`` adds chosen rows of it to a metrics.PoolMoments on the slot's stream
+        self.feat_dev = None
+        if features:
+            self.feat_width = self.engines[0].feature_width()
+            self.feat_dev = [torch.empty((n, self.feat_width), dtype=torch.float32, device=self.dev) for _ in range(depth)]
         self.depth, self.launched = depth, 0
         self.indices = None
         if mode == "probabilistic":      # the reference bakes ONE draw of size batch_size into the graph, for every batch (collaborator.py:54-56)
@@ -135,7 +141,10 @@ class FusedProposer:
             else:
                 img = e.generate(self.z_dev[k])
             self.img_host[k].copy_(img, non_blocking=True)        # (before score(): D's forward re-uses no G buffer, but keep the order plain)
-            e.score(img, out=self.sig_dev[k])
+            if self.feat_dev is not None:
+                e.score_with_features(img, out=self.sig_dev[k], feat_out=self.feat_dev[k])
+            else:
+                e.score(img, out=self.sig_dev[k])
             self.sig_host[k].copy_(self.sig_dev[k], non_blocking=True)
             self.done[k].record(st)
         return k
@@ -145,6 +154,33 @@ class FusedProposer:
         the slot is launched again)."""
         self.done[k].synchronize()
         return self.img_host[k].numpy(), self.sig_host[k].numpy()
+
+    def accumulate(self, k, rows, moments):
+        """Queue ``moments.update`` of rows ``rows`` (host integers into the slot's G*b samples) of slot k's features on the slot's
+        stream.  Valid from ``result(k)`` until the slot is launched again."""
+        if self.feat_dev is None:
+            raise ValueError("FusedProposer(features=True) keeps the features accumulate() reads")
+        with self.torch.cuda.stream(self.streams[k]):
+            moments.update(self.feat_dev[k], rows)
+
+    def real_moments(self, x, moments):
+        """Add D's features of a real evaluation set to ``moments``, ``batch`` samples per set of batch statistics like ``score_real``
+        (same padding of a last partial round; the padding batches are left out).  Returns ``moments``."""
+        torch = self.torch
+        n = self.b * self.G
+        N = x.shape[0]
+        if N % self.b:
+            raise ValueError(f"{N} real samples are not whole batches of {self.b}")
+        e = self.engines[0]
+        for i in range(0, N, n):
+            xb = np.asarray(x[i:i + n], dtype=np.float32)
+            m = xb.shape[0]
+            if m < n:
+                xb = np.concatenate([xb] + [xb[:self.b]] * ((n - m) // self.b))
+            with torch.cuda.stream(self.streams[0]):
+                _, f = e.score_with_features(torch.from_numpy(np.ascontiguousarray(xb)).to(self.dev))
+                moments.update(f, None if m == n else np.arange(m))
+        return moments
 
     def score_real(self, x, chunk=None):
         """np.mean-able sigmoids of a real evaluation set, scored ``batch`` samples at a time like nsgan/GAN.py:388-390
@@ -168,21 +204,38 @@ class FusedProposer:
         return out
 
 
-def collaborate_fused(proposer, mh_sampler, eval_size, real_sigmoid_mean, base=None, min_efficiency=None, max_rounds=100000, stats=None):
+def collaborate_fused(proposer, mh_sampler, eval_size, real_sigmoid_mean, base=None, min_efficiency=None, max_rounds=100000, stats=None,
+                      moments=None):
     """``collaborate`` (count_only_productive=False: the nsgan form, nsgan/GAN.py:398-426) over a ``FusedProposer``.
     ``stats`` (dict, optional) receives rounds / proposals / host-chain seconds / device-wait seconds.
     Returns (samples [eval_size, ...], efficiency) -- bit-identical to ``collaborate`` fed by one-batch-at-a-time proposals of the
-    same engine arithmetic, global numpy stream included."""
+    same engine arithmetic, global numpy stream included.
+    ``moments`` (a metrics.PoolMoments, optional; needs ``FusedProposer(features=True)``): D's features of exactly the rows copied
+    into the result are added to it on the device, one update per round; ``base`` must then be (images, sigmoids, features).  The
+    samples, the efficiency and every draw are those of the run without it."""
     import time
+    if moments is not None:
+        if proposer.feat_dev is None:
+            raise ValueError("collaborate_fused(moments=...) needs FusedProposer(features=True)")
+        if base is not None and len(base) != 3:
+            raise ValueError("collaborate_fused(moments=...): base must carry features too, as (images, sigmoids, features)")
     b, G = proposer.b, proposer.G
     out, cnt, cnt_propose = None, 0, eval_size
     mh_sampler.set_score_curr(real_sigmoid_mean)                                   # nsgan/GAN.py:401
     if base is not None:
-        acc = mh_sampler.sampling(base[0], base[1])
+        if moments is None:
+            acc = mh_sampler.sampling(base[0], base[1])
+        else:                                                                       # (sampling() spelled out: the accepted ROWS are needed)
+            base_rows = mh_sampler.walk(base[1])
+            acc = np.asarray([base[0][i] for i in base_rows], dtype=np.float32)
         if acc.shape[0] > 0:
             out = np.empty((eval_size,) + acc.shape[1:], dtype=acc.dtype)
             k = min(acc.shape[0], eval_size)
             out[:k] = acc[:k]
+            if moments is not None:
+                import torch
+                f = base[2] if isinstance(base[2], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(base[2], dtype=np.float32))
+                moments.update(f.to(proposer.dev), np.asarray(base_rows[:k], dtype=np.int64))
         cnt = acc.shape[0]
     max_propose = eval_size / min_efficiency if min_efficiency else float("inf")
     t_chain = t_wait = 0.0
@@ -215,6 +268,7 @@ def collaborate_fused(proposer, mh_sampler, eval_size, real_sigmoid_mean, base=N
         t_wait += t1 - t0
         if out is None:
             out = np.empty((eval_size,) + imgs.shape[1:], dtype=np.float32)
+        taken = []                                     # rows of this round's slot copied into ``out`` (moments)
         for j in range(G):
             batch = imgs[j * b:(j + 1) * b]
             if cnt_propose < max_propose:
@@ -225,15 +279,21 @@ def collaborate_fused(proposer, mh_sampler, eval_size, real_sigmoid_mean, base=N
                 if n > 0:
                     k = min(n, eval_size - cnt)
                     out[cnt:cnt + k] = batch[rows[:k]]
+                    if moments is not None:
+                        taken.extend(j * b + r for r in rows[:k])
                 cnt += n
             else:                                                                   # too inefficient: take the batch as is
                 k = min(b, eval_size - cnt)
                 out[cnt:cnt + k] = batch[:k]
+                if moments is not None:
+                    taken.extend(range(j * b, j * b + k))
                 cnt += b
             cnt_propose += b
             if cnt >= eval_size:
                 final_state = states[j]
                 break
+        if taken:                                      # (the slot is launched again at the top of the loop at the earliest)
+            proposer.accumulate(slot, np.asarray(taken, dtype=np.int64), moments)
         t_chain += time.perf_counter() - t1
     for slot, _, _ in pending:                         # rounds drawn ahead that the reference's loop never reaches: drained, discarded
         proposer.result(slot)

@@ -932,3 +932,65 @@ def bn_moving_update(mean, invstd, moving_mean, moving_var, decay, eps=BN_EPS):
     if invstd.numel() != C or moving_mean.numel() != C or moving_var.numel() != C:
         raise L.CgsError(f"bn_moving_update: {C} / {invstd.numel()} / {moving_mean.numel()} / {moving_var.numel()} channels")
     L.call("cgs_bn_moving_update", _ptr(mean), _ptr(invstd), _ptr(moving_mean), _ptr(moving_var), C, float(decay), float(eps), _stream())
+
+
+# ----------------------------------------------------------------------------- pool statistics (csrc/moments.hip)
+_mom_ws = {}
+
+
+def _moments_workspace(nbytes, device):
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)         # one scratch area per stream
+    ws = _mom_ws.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = torch.empty(max(nbytes, 8) // 8 + 1, dtype=torch.float64, device=device)
+        _mom_ws[key] = ws
+    return ws
+
+
+def pool_moments(x, sum, gram, shift=None, rows=None):
+    """sum[d] += sum_i a_i, gram[d,d] += sum_i a_i a_i^T with a_i = double(x[r_i]) - double(shift), in double on the device.
+    x: [n, d] contiguous fp32 on the GPU; sum / gram: float64 on the same device, updated in place; shift: [d] fp32 or None (= 0);
+    rows: None (every row of x) or a HOST integer array of row indices into x (checked here: the kernel trusts them), any order, repeats
+    allowed, empty = a no-op."""
+    _chk(x, "x")
+    if x.dim() != 2:
+        raise L.CgsError(f"pool_moments: x must be [n, d], got {tuple(x.shape)}")
+    n, d = x.shape
+    for t, name, shape in ((sum, "sum", (d,)), (gram, "gram", (d, d))):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
+                and t.device == x.device):
+            raise L.CgsError(f"pool_moments: {name} must be a contiguous float64 {shape} tensor on {x.device}")
+    if shift is not None:
+        _chk(shift, "shift")
+        if tuple(shift.shape) != (d,) or shift.device != x.device:
+            raise L.CgsError(f"pool_moments: shift must be [{d}] on {x.device}")
+    m, rows_dev = n, None
+    if rows is not None:
+        import numpy as np
+        r = np.asarray(rows)
+        if r.ndim != 1 or (r.size and r.dtype.kind not in "iu"):
+            raise L.CgsError("pool_moments: rows must be a 1-D host array of integers")
+        m = int(r.size)
+        if m == 0:
+            return
+        if int(r.min()) < 0 or int(r.max()) >= n:
+            raise L.CgsError(f"pool_moments: row index outside [0, {n})")
+        rows_dev = torch.from_numpy(np.ascontiguousarray(r, dtype=np.int32)).to(x.device)
+    if m == 0:
+        return
+    with torch.cuda.device(x.device):
+        need = int(L.load().cgs_pool_moments_ws_bytes(m, d))
+        if need == 0:
+            raise L.CgsError(f"pool_moments: unsupported shape (m={m}, d={d}): 1 <= d <= 2048")
+        ws = _moments_workspace(need, x.device)
+        L.call("cgs_pool_moments_accumulate", _ptr(x), n, d, _ptr(rows_dev), m, _ptr(shift), _ptr(sum), _ptr(gram), _ptr(ws), ws.numel() * 8,
+               _stream())
+
+
+def spatial_mean(x, out=None):
+    """[B, ..., C] -> [B, C]: the mean over every axis between the first and the last (a conv discriminator's feature map per sample)."""
+    _chk(x, "x")
+    B, C = x.shape[0], x.shape[-1]
+    o = out if out is not None else torch.empty((B, C), dtype=torch.float32, device=x.device)
+    L.call("cgs_spatial_mean", _ptr(x), _ptr(o), B, x.numel() // (B * C), C, _stream())
+    return o

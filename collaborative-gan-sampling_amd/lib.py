@@ -110,6 +110,9 @@ SIGNATURES = {
     "cgs_adam_step": (_i, [_p, _p, _p, _p, _f, _f, _f, _f, _z, _p]),
     "cgs_adam_multi": (_i, [_p, _i, _p, _i, _p, _f, _f, _f, _p]),
     "cgs_bn_moving_update": (_i, [_p, _p, _p, _p, _i, C.c_double, _f, _p]),
+    "cgs_pool_moments_ws_bytes": (_z, [_i, _i]),
+    "cgs_pool_moments_accumulate": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _p, _z, _p]),
+    "cgs_spatial_mean": (_i, [_p, _p, _i, _i, _i, _p]),
 }
 
 _lib = None

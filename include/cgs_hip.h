@@ -516,6 +516,23 @@ int cgs_adam_multi(const cgs_adam_slot* table, int n_slots, const cgs_adam_chunk
 int cgs_bn_moving_update(const float* mean, const float* invstd, float* moving_mean, float* moving_var, int C, double decay,
                          float eps, void* stream);
 
+/* Streaming Frechet statistics of a pool of feature vectors (metrics.PoolMoments; the FD row of the reference's evaluate loop,
+ * nsgan/GAN.py:306, without ever holding the pool): with a_i = (double)x[r_i] - (double)shift,
+ *   sum[j] += sum_i a_ij        gram[j][k] += sum_i a_ij * a_ik        (both ADDED to; double throughout, v_mfma_f64_16x16x4_f64)
+ * x: [n][d] fp32 row-major contiguous, below 2 GiB.  rows == NULL: the n rows of x (m is then only checked to be >= 0); else m row
+ * indices into x, which the kernel TRUSTS (0 <= rows[i] < n is the caller's duty; a row may repeat).  shift: [d] or NULL (= 0).
+ * 1 <= d <= 2048; anything else is CGS_EINVAL before any launch (the query then returns 0); no sample (m == 0 with rows, n == 0 without) is
+ * a no-op that launches nothing and dereferences nothing.  Only tile pairs on or above the diagonal are computed and the mirror is
+ * written from the same values: gram stays exactly symmetric if it was.  The samples are cut into slabs whose number depends on
+ * (m, d) alone, each slab leaves its partial tiles in the workspace, and a second launch adds them in ascending order: no atomics,
+ * reruns are bit-equal.  ws: cgs_pool_moments_ws_bytes(m, d) bytes for m samples, 8-byte aligned; CGS_EWORKSPACE if smaller. */
+size_t cgs_pool_moments_ws_bytes(int m, int d);
+int cgs_pool_moments_accumulate(const float* x, int n, int d, const int* rows, int m, const float* shift, double* sum, double* gram,
+                                void* ws, size_t ws_bytes, void* stream);
+/* out[b][c] = mean over the HW pixels of x[b][.][c] (x: [B][HW][C]), summed in double and rounded once: a conv discriminator's feature
+ * map as one vector per sample (engine.RefineEngine.score_with_features). */
+int cgs_spatial_mean(const float* x, float* out, int B, int HW, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
