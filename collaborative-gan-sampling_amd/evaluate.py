@@ -125,9 +125,12 @@ class FusedProposer:
             one = np.asarray(indices) if indices is not None else np.random.randint(steps + 1, size=self.b)
             self.indices = np.tile(one, self.G)
 
-    def launch(self, z, refine=True):
+    def launch(self, z, refine=True, calibration=None):
         """Queue one round on the next slot: z [G*b, z_dim] (host array) -> images + sigmoids in the slot's pinned buffers.
-        ``refine=False``: the standard samples instead (fake_images / fake_sigmoids, nsgan/GAN.py:153-155).  Returns the slot."""
+        ``refine=False``: the standard samples instead (fake_images / fake_sigmoids, nsgan/GAN.py:153-155).  Returns the slot.
+        ``calibration`` (a metrics.CalibrationStats, optional): the round's sigmoids are added to it with label 0 on the slot's stream,
+        from the device buffer the scoring pass wrote -- with ``refine=False`` the ``sigmoid_standard`` half of nsgan/GAN.py:287-301;
+        nothing more is copied to the host."""
         torch = self.torch
         k = self.launched % self.depth
         self.launched += 1
@@ -147,6 +150,8 @@ class FusedProposer:
                 e.score(img, out=self.sig_dev[k])
             self.sig_host[k].copy_(self.sig_dev[k], non_blocking=True)
             self.done[k].record(st)
+            if calibration is not None:                           # (behind ``done``: result(k) does not wait for it)
+                calibration.update(self.sig_dev[k], 0)
         return k
 
     def result(self, k):
@@ -182,10 +187,11 @@ class FusedProposer:
                 moments.update(f, None if m == n else np.arange(m))
         return moments
 
-    def score_real(self, x, chunk=None):
+    def score_real(self, x, chunk=None, calibration=None):
         """np.mean-able sigmoids of a real evaluation set, scored ``batch`` samples at a time like nsgan/GAN.py:388-390
         (``G`` batches per launch; x.shape[0] must be a multiple of ``batch``; a last partial round is padded with repeats
-        of whole batches, whose scores are dropped)."""
+        of whole batches, whose scores are dropped).  ``calibration`` (a metrics.CalibrationStats, optional): the same scores, padding
+        left out, are added to it with label 1 on the device (``sigmoid_real`` of nsgan/GAN.py:287-289)."""
         torch = self.torch
         n = self.b * self.G
         N = x.shape[0]
@@ -200,6 +206,8 @@ class FusedProposer:
                 xb = np.concatenate([xb] + [xb[:self.b]] * ((n - m) // self.b))
             with torch.cuda.stream(self.streams[0]):
                 s = e.score(torch.from_numpy(np.ascontiguousarray(xb)).to(self.dev))
+                if calibration is not None:
+                    calibration.update(s[:m], 1)
                 out[i:i + m] = s.cpu().numpy()[:m]
         return out
 
@@ -303,3 +311,18 @@ def collaborate_fused(proposer, mh_sampler, eval_size, real_sigmoid_mean, base=N
         stats.update(rounds=rounds, proposed=cnt_propose - eval_size, host_chain_s=t_chain, device_wait_s=t_wait,
                      discarded_batches=drawn - (cnt_propose - eval_size) // b)
     return out, cnt / cnt_propose
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The reference's log rows.  ``diag``: a dict with z_dawid / brier / ece / mce (metrics.calibration_diagnostics).
+def row_nsgan(ckpt, it, cs, fd, eff, diag):
+    """One line of GAN.write (nsgan/GAN.py:493-497): ckpt iter CS FD eff z_dawid brier ece mce."""
+    return "%d    %d    %.4f    %.4f    %.4f    %.4f    %.4f    %.4f    %.4f\r\n" % (
+        ckpt, it, cs, fd, eff, diag["z_dawid"], diag["brier"], diag["ece"], diag["mce"])
+
+
+def row_synthetic(ckpt, it, quality, eff, diag):
+    """One line of save_metrics (synthetic/main.py:106-110): ckpt iter mean_dist good kl js eff z_dawid brier ece mce.  ``quality``: a
+    dict with mean_dist / good / kl / js (metrics.mode_metrics, synthetic.evaluate_collaborative)."""
+    return "%d    %d    %.4f    %.4f    %.4f    %.4f    %.4f    %.4f    %.4f    %.4f    %.4f\r\n" % (
+        ckpt, it, quality["mean_dist"], quality["good"], quality["kl"], quality["js"], eff, diag["z_dawid"], diag["brier"], diag["ece"], diag["mce"])

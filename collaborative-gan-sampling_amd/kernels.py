@@ -6,6 +6,7 @@ layouts are the reference's (nsgan/ops.py:39,51,76).  Packed-weight workspaces a
 (weight storage, version, op): frozen weights are packed once.
 """
 import math
+import operator
 import weakref
 
 import torch
@@ -994,3 +995,69 @@ def spatial_mean(x, out=None):
     o = out if out is not None else torch.empty((B, C), dtype=torch.float32, device=x.device)
     L.call("cgs_spatial_mean", _ptr(x), _ptr(o), B, x.numel() // (B * C), C, _stream())
     return o
+
+
+# ----------------------------------------------------------------------------- calibration / mode statistics (csrc/diagnostics.hip)
+CAL_MAX_BINS, MODE_MAX_K = 64, 64
+
+
+def _f64_dev(t, name, shape, device, who):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
+            and t.device == device):
+        raise L.CgsError(f"{who}: {name} must be a contiguous float64 {shape} tensor on {device}")
+
+
+def calibration_accumulate(p, label, edges, state):
+    """Add the calibration statistics of the scores ``p`` (device fp32 [n] or [n, 1]), all of label ``label`` (0 fake, 1 real), to
+    ``state``: float64 [3 (n_bins + 1) + 11] on the same device, layout in include/cgs_hip.h.  ``edges``: float64 [n_bins + 1] on the
+    device (np.linspace(0., 1. + 1e-8, n_bins + 1)), 1 <= n_bins <= 64.  The host twin is metrics.calibration_state_of."""
+    _chk(p, "p")
+    if not (p.dim() == 1 or (p.dim() == 2 and p.shape[1] == 1)):
+        raise L.CgsError(f"calibration_accumulate: p must be [n] or [n, 1], got {tuple(p.shape)}")
+    try:
+        label = operator.index(label)
+    except TypeError:
+        label = None
+    if label not in (0, 1):
+        raise L.CgsError("calibration_accumulate: label must be the integer 0 (fake) or 1 (real)")
+    if not (isinstance(edges, torch.Tensor) and edges.dim() == 1):
+        raise L.CgsError("calibration_accumulate: edges must be a 1-D float64 device tensor")
+    n_bins = edges.shape[0] - 1
+    if not 1 <= n_bins <= CAL_MAX_BINS:
+        raise L.CgsError(f"calibration_accumulate: n_bins = {n_bins} outside 1..{CAL_MAX_BINS}")
+    _f64_dev(edges, "edges", (n_bins + 1,), p.device, "calibration_accumulate")
+    _f64_dev(state, "state", (3 * (n_bins + 1) + 11,), p.device, "calibration_accumulate")
+    n = p.shape[0]
+    if n == 0:
+        return
+    with torch.cuda.device(p.device):
+        need = int(L.load().cgs_calibration_ws_bytes(n, n_bins))
+        if need == 0:
+            raise L.CgsError(f"calibration_accumulate: unsupported size (n={n}, n_bins={n_bins})")
+        ws = _moments_workspace(need, p.device)
+        L.call("cgs_calibration_accumulate", _ptr(p), n, label, _ptr(edges), n_bins, _ptr(state), _ptr(ws), ws.numel() * 8, _stream())
+
+
+def mode_stats_accumulate(x, centeroids, thres, state):
+    """Add the mode statistics of the 2-D samples ``x`` (device fp32 [n, 2]) to ``state``: float64 [k + 3] on the same device (per-mode
+    hit counts | n | good | sum of the distance to the nearest mode).  ``centeroids``: float64 [k, 2] on the device, 1 <= k <= 64;
+    ``thres``: a host float.  The host twin is metrics.mode_state_of."""
+    _chk(x, "x")
+    if x.dim() != 2 or x.shape[1] != 2:
+        raise L.CgsError(f"mode_stats_accumulate: x must be [n, 2], got {tuple(x.shape)}")
+    if not (isinstance(centeroids, torch.Tensor) and centeroids.dim() == 2 and centeroids.shape[1] == 2):
+        raise L.CgsError("mode_stats_accumulate: centeroids must be a float64 [k, 2] device tensor")
+    k = centeroids.shape[0]
+    if not 1 <= k <= MODE_MAX_K:
+        raise L.CgsError(f"mode_stats_accumulate: k = {k} outside 1..{MODE_MAX_K}")
+    _f64_dev(centeroids, "centeroids", (k, 2), x.device, "mode_stats_accumulate")
+    _f64_dev(state, "state", (k + 3,), x.device, "mode_stats_accumulate")
+    n = x.shape[0]
+    if n == 0:
+        return
+    with torch.cuda.device(x.device):
+        need = int(L.load().cgs_mode_stats_ws_bytes(n, k))
+        if need == 0:
+            raise L.CgsError(f"mode_stats_accumulate: unsupported size (n={n}, k={k})")
+        ws = _moments_workspace(need, x.device)
+        L.call("cgs_mode_stats_accumulate", _ptr(x), n, _ptr(centeroids), k, float(thres), _ptr(state), _ptr(ws), ws.numel() * 8, _stream())

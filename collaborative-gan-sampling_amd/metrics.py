@@ -22,18 +22,28 @@ def metrics_distance(samples, centeroids, thres):
     return float(np.mean(dist_min)), float((dist_min < thres).sum() / dist_min.size)
 
 
+def _freqs_from_counts(counts, n):
+    """Per-mode hit counts of ``n`` samples -> (frequencies among the hits, frequencies incl. a last "no mode" bin): the tail of
+    ``freq_category``, shared with ``mode_metrics``."""
+    total = counts.sum()
+    freqs_valid = counts / total if total > 0 else np.ones(len(counts)) / len(counts)
+    return freqs_valid, np.append(counts, n - total) / n
+
+
 def freq_category(samples, centeroids, thres):
     """(per-mode frequencies among samples that hit a mode, frequencies incl. a last "no mode" bin).  :147-161."""
     hits = _mode_distances(samples, centeroids) < thres
-    counts = hits.sum(axis=0)
-    total, n = counts.sum(), hits.shape[0]
-    freqs_valid = counts / total if total > 0 else np.ones(len(counts)) / len(counts)
-    return freqs_valid, np.append(counts, n - total) / n
+    return _freqs_from_counts(hits.sum(axis=0), hits.shape[0])
 
 
 def kl_div(predictions, targets):
     """:169-177 (targets clipped away from 0/1; scipy entropy renormalises both)."""
     return float(stats.entropy(predictions, np.clip(targets, 1e-12, 1 - 1e-12)))
+
+
+def _js_from_freqs(fr, fm):
+    avg = 0.5 * (fr + fm)
+    return 0.5 * kl_div(fr, avg) + 0.5 * kl_div(fm, avg)
 
 
 def metrics_diversity(real_batch, model_batch, centeroids, thres):
@@ -43,9 +53,7 @@ def metrics_diversity(real_batch, model_batch, centeroids, thres):
 
 def metrics_distribution(real_batch, model_batch, centeroids, thres):
     """JS divergence of the frequencies including the "no mode" bin.  :179-184."""
-    fr, fm = freq_category(real_batch, centeroids, thres)[1], freq_category(model_batch, centeroids, thres)[1]
-    avg = 0.5 * (fr + fm)
-    return 0.5 * kl_div(fr, avg) + 0.5 * kl_div(fm, avg)
+    return _js_from_freqs(freq_category(real_batch, centeroids, thres)[1], freq_category(model_batch, centeroids, thres)[1])
 
 
 def frechet_distance(feat_real, feat_fake):
@@ -176,3 +184,231 @@ def all_reduce_moments(moments, group=None):
     dist.all_reduce(flat, group=group)
     h = flat.cpu().numpy()
     return _state(int(round(h[0])), st["shift"], h[1:1 + d], h[1 + d:].reshape(d, d))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# Calibration of D's scores and the 2-D mode statistics in the same streaming form: a STATE is a small dict of
+# host arrays that ADDS across batches, slots and ranks; the functions below are pure numpy on states, ``CalibrationStats`` /
+# ``ModeStats`` keep the state in double on the device (csrc/diagnostics.hip) and ``all_reduce_calibration`` / ``all_reduce_modes``
+# add the ranks' states.
+#
+# Calibration (the reference's calibration_diagnostic, utils_sampling.py:186-299).  edges = np.linspace(0., 1. + 1e-8, n_bins + 1); a
+# score p (fp32, widened to double exactly) of label y falls into slot np.digitize(p, edges) - 1 of n_bins + 1 slots -- the last one
+# catches p >= edges[-1] and NaN, as np.bincount(..., minlength=len(bins)) does; p < edges[0] (the reference's bincount raises) is
+# counted in ``under`` and nowhere else.
+def calibration_edges(n_bins=20):
+    return np.linspace(0., 1. + 1e-8, n_bins + 1)
+
+
+def _cal_state(n_bins, count, sum_p, sum_y, n, sum_ymp, sum_var, sum_sq, under, label_n, label_sum, label_max):
+    i64, f64 = (lambda a: np.asarray(a, dtype=np.int64)), (lambda a: np.asarray(a, dtype=np.float64))
+    return dict(n_bins=int(n_bins), count=i64(count), sum_p=f64(sum_p), sum_y=f64(sum_y), n=int(n), sum_ymp=float(sum_ymp),
+                sum_var=float(sum_var), sum_sq=float(sum_sq), under=int(under), label_n=i64(label_n), label_sum=f64(label_sum),
+                label_max=f64(label_max))
+
+
+def calibration_state_of(p, label, n_bins=20):
+    """The state of the scores ``p`` (any shape; fp32 values, possibly in a float64 holder), all of label ``label`` (0 fake, 1 real), in
+    float64 numpy.  {"n_bins", "count" [S], "sum_p" [S], "sum_y" [S], "n", "sum_ymp" = sum (y - p), "sum_var" = sum p (1 - p), "sum_sq" =
+    sum (y - p)^2, "under", "label_n" [2], "label_sum" [2], "label_max" [2]} with S = n_bins + 1."""
+    if label not in (0, 1):
+        raise ValueError(f"label must be 0 or 1, got {label!r}")
+    if not 1 <= n_bins <= 64:
+        raise ValueError(f"n_bins = {n_bins} outside 1..64")
+    p = np.asarray(p, dtype=np.float64).reshape(-1)
+    S = n_bins + 1
+    slot = np.digitize(p, calibration_edges(n_bins)) - 1
+    under = int((slot < 0).sum())
+    p, slot = p[slot >= 0], slot[slot >= 0]
+    y = float(label)
+    count = np.bincount(slot, minlength=S)
+    ln, ls, lm = np.zeros(2, np.int64), np.zeros(2), np.zeros(2)
+    ln[label], ls[label] = p.size, p.sum()
+    lm[label] = np.fmax.reduce(p, initial=0.0)                        # (a NaN never wins; every counted score is >= edges[0] = 0)
+    return _cal_state(n_bins, count, np.bincount(slot, weights=p, minlength=S), y * count, p.size, (y - p).sum(), (p * (1.0 - p)).sum(),
+                      ((y - p) ** 2).sum(), under, ln, ls, lm)
+
+
+def calibration_merge(a, b):
+    """The state of the union of two score sets."""
+    if a["n_bins"] != b["n_bins"]:
+        raise ValueError(f"calibration_merge: {a['n_bins']} and {b['n_bins']} bins do not add")
+    add = {k: a[k] + b[k] for k in ("count", "sum_p", "sum_y", "n", "sum_ymp", "sum_var", "sum_sq", "under", "label_n", "label_sum")}
+    return _cal_state(a["n_bins"], label_max=np.fmax(a["label_max"], b["label_max"]), **add)
+
+
+def calibration_diagnostics(state):
+    """{"z_dawid", "brier", "ece", "mce"} (calibration_diagnostic's four, utils_sampling.py:290-299), the bins behind them ("accuracy",
+    "confidence", "weights" over the non-empty slots: calibration_bins, :219-282) and the real scores' "real_mean" / "real_max" (what
+    mh_sampler.set_score_curr and rejector.set_score_max are seeded with).  Equals the reference on float64 holders of the fp32 scores
+    (the image path, nsgan/GAN.py:287-301); on fp32 arrays (the 2-D call site, synthetic/main.py:115-123) the reference computes z_dawid and
+    brier in fp32, so there the match is to fp32 rounding only."""
+    if state["under"] > 0:
+        raise ValueError(f"{state['under']} scores lie below the first bin edge (the reference's np.bincount raises on them)")
+    nz = state["count"] != 0
+    count = state["count"][nz]
+    accuracy, confidence, weights = state["sum_y"][nz] / count, state["sum_p"][nz] / count, count / state["n"]
+    gap = np.absolute(accuracy - confidence)
+    real_n = int(state["label_n"][1])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = np.float64(state["sum_ymp"]) / np.sqrt(np.float64(state["sum_var"]))
+        brier = np.float64(state["sum_sq"]) / state["n"]
+    return dict(z_dawid=float(z), brier=float(brier), ece=float(np.sum(gap * weights)), mce=float(np.max(gap)) if gap.size else float("nan"),
+                accuracy=accuracy, confidence=confidence, weights=weights,
+                real_mean=float(state["label_sum"][1] / real_n) if real_n else float("nan"), real_max=float(state["label_max"][1]))
+
+
+def _cal_flat(st):
+    """A state in the device layout of include/cgs_hip.h: 3 S + 11 doubles."""
+    lab = np.stack([st["label_n"].astype(np.float64), st["label_sum"], st["label_max"]], axis=1).reshape(-1)
+    return np.concatenate([st["count"].astype(np.float64), st["sum_p"], st["sum_y"],
+                           [float(st["n"]), st["sum_ymp"], st["sum_var"], st["sum_sq"], float(st["under"])], lab])
+
+
+def _cal_unflat(h, n_bins):
+    S = n_bins + 1
+    g, lab = h[3 * S:3 * S + 5], h[3 * S + 5:].reshape(2, 3)
+    return _cal_state(n_bins, np.rint(h[:S]), h[S:2 * S], h[2 * S:3 * S], round(g[0]), g[1], g[2], g[3], round(g[4]), np.rint(lab[:, 0]),
+                      lab[:, 1], lab[:, 2])
+
+
+# 2-D modes (utils_sampling.py:132-161): per sample and mode dist = sqrt(dx dx + dy dy) in double, products and sum rounded separately.
+def _mode_state(counts, n, good, sum_min):
+    return dict(counts=np.asarray(counts, dtype=np.int64), n=int(n), good=int(good), sum_min=float(sum_min))
+
+
+def mode_state_of(samples, centeroids, thres):
+    """The state of a [n, 2] sample pool in float64 numpy: {"counts" [k]: samples closer than ``thres`` to mode j (a sample may hit
+    several), "n", "good": samples whose nearest mode is closer than ``thres``, "sum_min": sum of the distance to the nearest mode}."""
+    dist = _mode_distances(np.asarray(samples, dtype=np.float64), np.asarray(centeroids, dtype=np.float64))
+    if dist.shape[0] == 0:
+        return _mode_state(np.zeros(dist.shape[1], np.int64), 0, 0, 0.0)
+    dist_min = dist.min(axis=1)
+    return _mode_state((dist < thres).sum(axis=0), dist.shape[0], (dist_min < thres).sum(), dist_min.sum())
+
+
+def mode_merge(a, b):
+    if a["counts"].shape != b["counts"].shape:
+        raise ValueError("mode_merge: the states count different numbers of modes")
+    return _mode_state(a["counts"] + b["counts"], a["n"] + b["n"], a["good"] + b["good"], a["sum_min"] + b["sum_min"])
+
+
+def mode_metrics(model_state, real_state):
+    """{"mean_dist", "good", "kl", "js"} of a model pool against a real pool from their states: metrics_distance, metrics_diversity and
+    metrics_distribution without the pools."""
+    fm, fr = _freqs_from_counts(model_state["counts"], model_state["n"]), _freqs_from_counts(real_state["counts"], real_state["n"])
+    return dict(mean_dist=float(model_state["sum_min"] / model_state["n"]), good=float(model_state["good"] / model_state["n"]),
+                kl=kl_div(fm[0], fr[0]), js=_js_from_freqs(fr[1], fm[1]))
+
+
+class _DeviceStats:
+    """A float64 state vector on the device that ``_accumulate`` adds to.  Updates may come from different HIP streams (the slots of a
+    ``FusedProposer``): each one waits for the one before it, as in ``PoolMoments``."""
+
+    def _init(self, device, size, who):
+        import torch
+        self.torch = torch
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"{who} accumulates on a GPU device (the host form is the *_state_of / *_merge functions)")
+        self.vec = torch.zeros(size, dtype=torch.float64, device=self.device)
+        self._last = None                      # event behind the latest update
+
+    def _chained(self, launch):
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream(self.device)
+            if self._last is not None:
+                st.wait_event(self._last)
+            launch()
+            self._last = torch.cuda.Event()
+            self._last.record(st)
+        return self
+
+    def _host(self):
+        if self._last is not None:
+            self._last.synchronize()
+        return self.vec.cpu().numpy()
+
+
+class CalibrationStats(_DeviceStats):
+    """The calibration state of every score handed to ``update``, as ONE float64 device tensor (layout: include/cgs_hip.h)."""
+
+    def __init__(self, device, n_bins=20):
+        if not 1 <= n_bins <= 64:
+            raise ValueError(f"n_bins = {n_bins} outside 1..64")
+        self.n_bins = int(n_bins)
+        self._init(device, 3 * (self.n_bins + 1) + 11, "CalibrationStats")
+        self.edges = self.torch.from_numpy(calibration_edges(self.n_bins)).to(self.device)
+
+    def update(self, p, label):
+        """Add the scores ``p`` (device fp32 [n] or [n, 1]), all of label ``label`` (0 fake, 1 real)."""
+        from . import kernels as K
+        return self._chained(lambda: K.calibration_accumulate(p, label, self.edges, self.vec))
+
+    def state(self):
+        """The state as host arrays (waits for the updates queued so far)."""
+        return _cal_unflat(self._host(), self.n_bins)
+
+    def diagnostics(self):
+        return calibration_diagnostics(self.state())
+
+
+class ModeStats(_DeviceStats):
+    """The mode state of every 2-D sample handed to ``update``: k + 3 doubles on the device."""
+
+    def __init__(self, centeroids, thres, device):
+        c = np.ascontiguousarray(centeroids, dtype=np.float64)
+        if c.ndim != 2 or c.shape[1] != 2 or not 1 <= c.shape[0] <= 64:
+            raise ValueError(f"centeroids {c.shape} are not [k, 2] with 1 <= k <= 64")
+        self.k, self.thres = c.shape[0], float(thres)
+        self._init(device, self.k + 3, "ModeStats")
+        self.centeroids = self.torch.from_numpy(c).to(self.device)
+
+    def update(self, x):
+        """Add the samples ``x`` (device fp32 [n, 2])."""
+        from . import kernels as K
+        return self._chained(lambda: K.mode_stats_accumulate(x, self.centeroids, self.thres, self.vec))
+
+    def state(self):
+        h = self._host()
+        return _mode_state(np.rint(h[:self.k]), round(h[self.k]), round(h[self.k + 1]), h[self.k + 2])
+
+
+def _all_reduce_flat(stats, flat_of, max_index, group):
+    """SUM all-reduce of a flat state (device tensor under "nccl", else staged through the host); the entries ``max_index`` travel in a
+    second, MAX all-reduce.  Returns the reduced flat host array, or None without a process group."""
+    import torch
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return None
+    on_dev = dist.get_backend(group) == "nccl"
+    if isinstance(stats, _DeviceStats):
+        stats._host()                                                   # (every queued update is behind us)
+        flat = stats.vec.clone() if on_dev else stats.vec.cpu()
+    else:
+        flat = torch.from_numpy(flat_of(stats))
+        flat = flat.to(torch.device("cuda", torch.cuda.current_device())) if on_dev else flat
+    mx = flat[max_index].clone() if max_index else None
+    dist.all_reduce(flat, group=group)
+    if mx is not None:
+        dist.all_reduce(mx, op=dist.ReduceOp.MAX, group=group)
+        flat[max_index] = mx
+    return flat.cpu().numpy()
+
+
+def all_reduce_calibration(stats, group=None):
+    """The calibration state of every rank's scores together: ONE SUM all-reduce of the 3 S + 11 doubles and one MAX all-reduce of the two
+    maxima.  ``stats``: a state or a ``CalibrationStats``.  Without a process group it is the identity."""
+    st = stats.state() if isinstance(stats, CalibrationStats) else stats
+    S = st["n_bins"] + 1
+    h = _all_reduce_flat(stats, _cal_flat, [3 * S + 7, 3 * S + 10], group)
+    return st if h is None else _cal_unflat(h, st["n_bins"])
+
+
+def all_reduce_modes(stats, group=None):
+    """The mode state of every rank's pool together: ONE SUM all-reduce of k + 3 doubles.  ``stats``: a state or a ``ModeStats``."""
+    st = stats.state() if isinstance(stats, ModeStats) else stats
+    k = st["counts"].shape[0]
+    h = _all_reduce_flat(stats, lambda s: np.concatenate([s["counts"].astype(np.float64), [float(s["n"]), float(s["good"]), s["sum_min"]]]), [], group)
+    return st if h is None else _mode_state(np.rint(h[:k]), round(h[k]), round(h[k + 1]), h[k + 2])

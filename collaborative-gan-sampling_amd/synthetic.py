@@ -283,19 +283,28 @@ def proposer(refiner, generate, discriminator):
     return propose, score
 
 
-def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_batch, centeroids, std, mh_sampler=None):
+def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_batch, centeroids, std, mh_sampler=None, diagnostics=False):
     """The "shape"-mode evaluation of synthetic/main.py:215-263 on the device refiner: refine the evaluation batch, report its
     quality, then D-score -> MH fill (thinning T = 20, chain seeded with mean(real_sigmoid)) until ``len(eval_batch)`` samples
     are accepted (proposal counter advancing only for productive batches, :251) and report the collaborative sample's
     quality.  Returns {"refinement": {...}, "collaborate": {..., "eff": accepted / proposed}} with the reference's four 2-D
     metrics (utils_sampling.py:132-184; ``thres`` = 4 std as in main.py:221).  ``generate``: a callable returning a generator batch,
-    or an ``MLPGenerator`` (then each proposal batch is G in training mode on ``NoiseDataset().next_batch(len(eval_batch))``)."""
+    or an ``MLPGenerator`` (then each proposal batch is G in training mode on ``NoiseDataset().next_batch(len(eval_batch))``).
+    ``diagnostics=True``: D's scores of ``eval_batch`` (label 0) and ``target_batch`` (label 1) go into a ``metrics.CalibrationStats``
+    as in synthetic/main.py:115-123 and the result gains "calibration" (``metrics.calibration_diagnostics``: the row's z_dawid brier ece
+    mce, computed in double where the reference's fp32 arrays give fp32 sums); the pools' quality then comes from ``metrics.ModeStats``
+    on the device, the pools taken as fp32.  Draws, samples and ``eff`` are those of ``diagnostics=False``."""
     from . import metrics as Mx
     from .evaluate import collaborate
     from .sampling import IndependenceSampler
     thres = std * 4
+    if diagnostics:
+        dev = discriminator.dev
+        real_modes = Mx.ModeStats(centeroids, thres, dev).update(_upload(target_batch, dev)).state()
 
     def quality(samples):
+        if diagnostics:
+            return Mx.mode_metrics(Mx.ModeStats(centeroids, thres, dev).update(_upload(samples, dev)).state(), real_modes)
         mean_dist, good = Mx.metrics_distance(samples, centeroids, thres)
         return {"mean_dist": float(mean_dist), "good": float(good),
                 "kl": float(Mx.metrics_diversity(target_batch, samples, centeroids, thres)),
@@ -306,6 +315,11 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
     _, score = proposer(refiner, generate, discriminator)
     real_sigmoid = score(target_batch)                                                 # main.py:116
     out = {"standard": quality(eval_batch)}
+    if diagnostics:                                                                    # :116-117,123: straight from D's device output
+        cal = Mx.CalibrationStats(dev)
+        cal.update(discriminator.sigmoid_and_saliency(eval_batch, want_saliency=False)[0], 0)
+        cal.update(discriminator.sigmoid_and_saliency(target_batch, want_saliency=False)[0], 1)
+        out["calibration"] = cal.diagnostics()
     refined = refiner.manipulate_sample(eval_batch)                                    # :217
     out["refinement"] = quality(refined)
     mh = mh_sampler if mh_sampler is not None else IndependenceSampler(T=20)           # main.py:80

@@ -533,6 +533,31 @@ int cgs_pool_moments_accumulate(const float* x, int n, int d, const int* rows, i
  * map as one vector per sample (engine.RefineEngine.score_with_features). */
 int cgs_spatial_mean(const float* x, float* out, int B, int HW, int C, void* stream);
 
+/* ---- calibration and 2-D mode statistics of a pool, additive, in double on the device (csrc/diagnostics.hip) ----
+ * Calibration of D's scores (the reference's calibration_diagnostic, sampling/utils_sampling.py:186-299).  p: n fp32 scores, widened to
+ * double exactly; label: 0 (fake) or 1 (real), one per call; edges: n_bins + 1 ascending doubles ON THE DEVICE
+ * (np.linspace(0., 1. + 1e-8, n_bins + 1) on the host); 1 <= n_bins <= 64.  The slot of a score is the number of edges <= p, minus one,
+ * compared in double (np.digitize(p, edges) - 1): S = n_bins + 1 slots, the last one catching p >= edges[n_bins] and NaN.  A score
+ * below edges[0] is counted in `under` and nowhere else.  The call ADDS to state, 3 S + 11 doubles:
+ *     [0, S)       count per slot            [S, 2S)  sum of p per slot            [2S, 3S)  sum of y per slot
+ *     3S + 0..4    n | sum (y - p) | sum p (1 - p) | sum (y - p)^2 | under
+ *     3S + 5 + 3y  n_y | sum of p | max of p   over the scores of label y (y = 0, 1; max: NaN ignored; the other label's three stay)
+ * Counts are doubles holding integers (exact below 2^53).  Every sum is a double sum in an order fixed by (n, n_bins): blocks over
+ * contiguous chunks leave one partial row each in ws, a one-block launch adds the rows in ascending order (max for the maximum) and
+ * then to state; no floating-point atomics, so two calls on the same inputs from the same state end bit-equal.
+ * Modes of a 2-D pool (utils_sampling.py:132-161).  x: [n][2] fp32; centeroids: [k][2] doubles ON THE DEVICE, 1 <= k <= 64.  Per sample and
+ * mode dist = sqrt(dx * dx + dy * dy) with dx = double(x0) - c0, dy = double(x1) - c1, products and sum rounded separately (numpy's
+ * linalg.norm).  The call ADDS to state, k + 3 doubles:
+ *     [0, k)  samples with dist_j < thres (a sample may hit several modes)     k: n | k + 1: samples with min_j dist_j < thres | k + 2: sum of min_j dist_j
+ * Errors: n_bins / k / label out of range or n < 0 or n > 2^30 is CGS_EINVAL before any launch (the query then returns 0); n == 0 is a
+ * no-op that dereferences nothing (query 0); ws: *_ws_bytes(n, .) bytes, 8-byte aligned, CGS_EWORKSPACE if smaller. */
+size_t cgs_calibration_ws_bytes(int n, int n_bins);
+int cgs_calibration_accumulate(const float* p, int n, int label, const double* edges, int n_bins, double* state, void* ws, size_t ws_bytes,
+                               void* stream);
+size_t cgs_mode_stats_ws_bytes(int n, int k);
+int cgs_mode_stats_accumulate(const float* x, int n, const double* centeroids, int k, double thres, double* state, void* ws, size_t ws_bytes,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
