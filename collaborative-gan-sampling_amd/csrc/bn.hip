@@ -350,7 +350,9 @@ __global__ __launch_bounds__(256) void norm_small_kernel(const float* __restrict
             for (int e = 0; e < 4; ++e) {
                 const double mean = a[e] / M;
                 double var = b[e] / M - mean * mean;
-                if (var < 0.0) var = 0.0;
+                // (one row: the variance IS 0; b - mean^2 is then only the float rounding of x*x, up to 6e-8 * x^2 -- against eps = 1e-5 that moved
+                // the saved invstd by up to 4 % at |x| ~ 2)
+                if (var < 0.0 || M == 1) var = 0.0;
                 o0[e] = (float)mean; o1[e] = (float)(1.0 / sqrt(var + (double)eps));
             }
             *(float4*)(mean_io + (size_t)grp * C + c) = make_float4(o0[0], o0[1], o0[2], o0[3]);
@@ -372,6 +374,9 @@ __global__ __launch_bounds__(256) void norm_small_kernel(const float* __restrict
         float4 scl, shf;
         scl.x = g.x * s1.x; scl.y = g.y * s1.y; scl.z = g.z * s1.z; scl.w = g.w * s1.w;
         shf.x = bt.x - s0.x * scl.x; shf.y = bt.y - s0.y * scl.y; shf.z = bt.z - s0.z * scl.z; shf.w = bt.w - s0.w * scl.w;
+        // (one row: x - mean IS 0 and y = lrelu(beta); with scale = gamma / sqrt(eps) the rounding of shift ~ -316 * gamma * x alone left
+        // y off by half an ulp of it, 3e-5 at |x| ~ 3, on values of ~0.1)
+        if (M == 1) { scl = make_float4(0.f, 0.f, 0.f, 0.f); shf = bt; }
 #pragma unroll
         for (int i = 0; i < NS_ROWS; ++i) {
             const int r = rl + 16 * i;
@@ -526,6 +531,7 @@ int cgs_bn_train_lrelu_fwd(const float* x, const float* gamma, const float* beta
     if (norm_small_ok(M)) {               // one launch: statistics + apply from registers
         hipLaunchKernelGGL(norm_small_kernel<false>, dim3(cgs_ceil_div(C, 64), 1), dim3(256), 0, s, x, nullptr, gamma, beta, eps, leak, y, mean, invstd, nullptr, M, C);
         CGS_CHECK_LAUNCH("bn_train_lrelu_fwd");
+        cgs_note_kernel("norm_small_fwd");
         return CGS_OK;
     }
     const BnGeom g = bn_geom(M, C);
@@ -536,6 +542,7 @@ int cgs_bn_train_lrelu_fwd(const float* x, const float* gamma, const float* beta
     const size_t n4 = (size_t)M * C / 4;
     hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, x, stat, leak, y, n4, C, n4);
     CGS_CHECK_LAUNCH("bn_train_lrelu_fwd");
+    cgs_note_kernel("norm_passes_fwd");
     return CGS_OK;
 }
 
@@ -549,10 +556,12 @@ int cgs_bn_train_lrelu_fwd_from_partials(const float* x, const float* part, int 
         hipLaunchKernelGGL(norm_fa_kernel<false>, dim3(cgs_ceil_div(C, 64), cgs_ceil_div(M, rpb), 1), dim3(256), 0, s, x, nullptr, part, G, 1, 0, gamma, beta, eps,
                            leak, y, mean, invstd, M, C, rpb);
         CGS_CHECK_LAUNCH("bn_train_lrelu_fwd_from_partials");
+        cgs_note_kernel("norm_fa_fwd");
         return CGS_OK;
     }
     float* stat = (float*)ws + (size_t)BN_MAX_BLOCKS * 2 * C;
-    if (G >= 1024 && !((uintptr_t)ws & 7)) {      // (the workspace's own partial area is unused on this path: BN_MAX_BLOCKS * 2 * C floats >= 16 * 2 * C doubles)
+    const bool sliced = G >= 1024 && !((uintptr_t)ws & 7);
+    if (sliced) {      // (the workspace's own partial area is unused on this path: BN_MAX_BLOCKS * 2 * C floats >= 16 * 2 * C doubles)
         double* slices = (double*)ws;
         hipLaunchKernelGGL(bn_slice_sums_kernel, dim3(cgs_ceil_div(C, BNF_CH), BNF_SLICES), dim3(256), 0, s, part, G, C, slices);
         hipLaunchKernelGGL(bn_finalize_slices_kernel, dim3(cgs_ceil_div(C, 64)), dim3(64), 0, s, slices, M, C, gamma, beta, eps, stat, mean, invstd);
@@ -562,6 +571,7 @@ int cgs_bn_train_lrelu_fwd_from_partials(const float* x, const float* part, int 
     const size_t n4 = (size_t)M * C / 4;
     hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, x, stat, leak, y, n4, C, n4);
     CGS_CHECK_LAUNCH("bn_train_lrelu_fwd_from_partials");
+    cgs_note_kernel(sliced ? "norm_sliced_fwd" : "norm_finalize_fwd");
     return CGS_OK;
 }
 
@@ -578,6 +588,7 @@ int cgs_bn_train_lrelu_bwd_data(const float* dy, const float* x, const float* ga
     if (norm_small_ok(M)) {               // one launch (stat2 is left where cgs_bn_train_param_grads reads it)
         hipLaunchKernelGGL(norm_small_kernel<true>, dim3(cgs_ceil_div(C, 64), 1), dim3(256), 0, s, x, dy, gamma, beta, 0.f, leak, dx, (float*)mean, (float*)invstd, stat2, M, C);
         CGS_CHECK_LAUNCH("bn_train_lrelu_bwd_data");
+        cgs_note_kernel("norm_small_bwd");
         return CGS_OK;
     }
     hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(g.G), dim3(256), 0, s, x, dy, mean, invstd, gamma, beta, leak, part, M, C, g.rows_per_block);
@@ -585,6 +596,7 @@ int cgs_bn_train_lrelu_bwd_data(const float* dy, const float* x, const float* ga
     const size_t n4 = (size_t)M * C / 4;
     hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, dy, x, mean, invstd, gamma, beta, stat2, leak, dx, n4, C, n4);
     CGS_CHECK_LAUNCH("bn_train_lrelu_bwd_data");
+    cgs_note_kernel("norm_passes_bwd");
     return CGS_OK;
 }
 
@@ -757,6 +769,7 @@ int cgs_instnorm_lrelu_fwd(const float* x, const float* scale, const float* offs
     if (norm_small_ok(HW)) {              // small groups: one launch (see norm_small_kernel)
         hipLaunchKernelGGL(norm_small_kernel<false>, dim3(cgs_ceil_div(C, 64), B), dim3(256), 0, s, x, nullptr, scale, offset, eps, leak, y, mean, invstd, nullptr, HW, C);
         CGS_CHECK_LAUNCH("instnorm_lrelu_fwd");
+        cgs_note_kernel("norm_small_fwd");
         return CGS_OK;
     }
     const BnGeom g = in_geom(B, HW);
@@ -767,6 +780,7 @@ int cgs_instnorm_lrelu_fwd(const float* x, const float* scale, const float* offs
     const size_t n4 = (size_t)B * HW * C / 4, gn4 = (size_t)HW * C / 4;
     hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, x, stat, leak, y, n4, C, gn4);
     CGS_CHECK_LAUNCH("instnorm_lrelu_fwd");
+    cgs_note_kernel("norm_passes_fwd");
     return CGS_OK;
 }
 
@@ -785,6 +799,7 @@ int cgs_groupnorm_lrelu_fwd_from_partials(const float* x, const float* part, int
         hipLaunchKernelGGL(norm_fa_kernel<false>, dim3(cgs_ceil_div(C, 64), cgs_ceil_div(M_group, rpb), groups), dim3(256), 0, s, x, nullptr, part, rows_per_seg, nseg,
                            seg_stride, gamma, beta, eps, leak, y, mean, invstd, M_group, C, rpb);
         CGS_CHECK_LAUNCH("groupnorm_lrelu_fwd_from_partials");
+        cgs_note_kernel("norm_fa_fwd");
         return CGS_OK;
     }
     float* stat = (float*)ws;                                          // [groups][4][C]
@@ -793,6 +808,7 @@ int cgs_groupnorm_lrelu_fwd_from_partials(const float* x, const float* part, int
     const size_t n4 = (size_t)groups * M_group * C / 4, gn4 = (size_t)M_group * C / 4;
     hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, x, stat, leak, y, n4, C, gn4);
     CGS_CHECK_LAUNCH("groupnorm_lrelu_fwd_from_partials");
+    cgs_note_kernel("norm_finalize_fwd");
     return CGS_OK;
 }
 
@@ -813,6 +829,7 @@ int cgs_norm_lrelu_bwd_from_partials(const float* dy, const float* x, const floa
         hipLaunchKernelGGL(norm_fa_kernel<true>, dim3(cgs_ceil_div(C, 64), cgs_ceil_div(M_group, rpb), groups), dim3(256), 0, s, x, dy, part, rows_per_seg, nseg,
                            seg_stride, gamma, beta, 0.f, leak, dx, (float*)mean, (float*)invstd, M_group, C, rpb);
         CGS_CHECK_LAUNCH("norm_lrelu_bwd_from_partials");
+        cgs_note_kernel("norm_fa_bwd");
         return CGS_OK;
     }
     float* stat2;
@@ -829,6 +846,7 @@ int cgs_norm_lrelu_bwd_from_partials(const float* dy, const float* x, const floa
     const size_t n4 = (size_t)groups * M_group * C / 4, gn4 = (size_t)M_group * C / 4;
     hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, dy, x, mean, invstd, gamma, beta, stat2, leak, dx, n4, C, gn4);
     CGS_CHECK_LAUNCH("norm_lrelu_bwd_from_partials");
+    cgs_note_kernel(sliced ? "norm_sliced_bwd" : "norm_finalize_bwd");
     return CGS_OK;
 }
 
@@ -844,6 +862,7 @@ int cgs_instnorm_lrelu_bwd_data(const float* dy, const float* x, const float* sc
     if (norm_small_ok(HW)) {
         hipLaunchKernelGGL(norm_small_kernel<true>, dim3(cgs_ceil_div(C, 64), B), dim3(256), 0, s, x, dy, scale, offset, 0.f, leak, dx, (float*)mean, (float*)invstd, stat2, HW, C);
         CGS_CHECK_LAUNCH("instnorm_lrelu_bwd_data");
+        cgs_note_kernel("norm_small_bwd");
         return CGS_OK;
     }
     hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(g.G, B), dim3(256), 0, s, x, dy, mean, invstd, scale, offset, leak, part, HW, C, g.rows_per_block);
@@ -851,5 +870,6 @@ int cgs_instnorm_lrelu_bwd_data(const float* dy, const float* x, const float* sc
     const size_t n4 = (size_t)B * HW * C / 4, gn4 = (size_t)HW * C / 4;
     hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, dy, x, mean, invstd, scale, offset, stat2, leak, dx, n4, C, gn4);
     CGS_CHECK_LAUNCH("instnorm_lrelu_bwd_data");
+    cgs_note_kernel("norm_passes_bwd");
     return CGS_OK;
 }

@@ -60,7 +60,16 @@ int cgs_version(void);
  * (cgs_amd/lib.py::load); bench.py reports this embedded value, so a measured number names the code that produced it. */
 const char* cgs_source_sha(void);
 const char* cgs_last_error(void);
-/* Name of the compute kernel the calling thread's most recent conv-family call launched (for profiling). */
+/* Name of the compute kernel the calling thread's most recent conv-family call launched (for profiling).
+ * The norm entry points (cgs_bn_train_lrelu_fwd / _fwd_from_partials / _bwd_data, cgs_instnorm_lrelu_fwd / _bwd_data,
+ * cgs_groupnorm_lrelu_fwd_from_partials, cgs_norm_lrelu_bwd_from_partials) leave the name of the FORM they launched, with
+ * "_fwd" or "_bwd" appended:
+ *   norm_small     one launch, statistics + apply from registers          (<= 128 rows per group)
+ *   norm_passes    partial sums -> finalize -> apply                      (from x, more rows)
+ *   norm_fa        one launch, finalize + apply from the partial rows     (<= 16 partial rows per group and a tensor of <= 2 MB)
+ *   norm_finalize  one-stage finalize -> apply                            (from partials otherwise)
+ *   norm_sliced    slice sums -> finalize of the slices -> apply          (>= 1024 partial rows, one group, one segment)
+ * so a test can pin the path a shape takes (tests/test_gpu_norm_paths.py). */
 const char* cgs_last_kernel(void);
 /* Floating-point operations that call really issued to the matrix cores: 2 x (algorithmic multiply-accumulates minus those
  * of zero-padding taps the kernel skipped).  0 = the kernel skips nothing (executed = algorithmic).  For rooflines. */
