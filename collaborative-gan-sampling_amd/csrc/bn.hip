@@ -6,6 +6,10 @@
 // Per-channel reductions are two-stage and deterministic (no float atomics): stage 1 writes one
 // (sum_a, sum_b) partial per block and channel, stage 2 adds the partials in a fixed order in
 // double and finishes the statistics.  Run-to-run results are bit-identical.
+//
+// Every formula is written once: the element arithmetic in cgs_internal.h (norm_fwd1, norm_d1, norm_d_acc1, norm_dx1) and its float4
+// forms below, the finish of the statistics in norm_stats_finish / norm_mean_finish / norm_write_stat.  The kernels differ in how they
+// walk memory and in the tree of their reductions, not in arithmetic.
 #include "cgs_internal.h"
 
 #define BN_MAX_BLOCKS CGS_BN_MAX_BLOCKS
@@ -26,16 +30,13 @@ static BnGeom bn_geom(int M, int C) {
     return g;
 }
 
-size_t cgs_bn_ws_bytes(int M, int C) {
-    (void)M;
-    return ((size_t)BN_MAX_BLOCKS * 2 * C + 6 * (size_t)C) * sizeof(float);   // partials | stat[4][C] | stat2[2][C]
-}
+// ------------------------------------------------------------------------------------------------
+// Element arithmetic on the four channels a thread owns
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
-// MODE 0: a = x, b = x*x.   MODE 1: a = dy', b = dy'*xhat  (dy' = dy * lrelu'(scale*x+shift))
-// 16-byte loads: a thread owns 4 consecutive channels and strides over the block's rows; the row groups of a
-// block are combined through LDS in a fixed order (deterministic).  C % 4 == 0.
-// scale = gamma * invstd, shift = beta - mean * scale of 4 channels, formed where they are used (a separate kernel that wrote them
-// to memory was one more dependent 4-us launch in front of every backward pass); the same expression in both backward kernels
+// The backward kernels' parameters from the SAVED mean / invstd, formed where they are used (a separate kernel that wrote them to memory
+// was one more dependent 4-us launch in front of every backward pass): mu = mean, inv = invstd, sc = gamma * invstd, sh = beta - mean * sc
 __device__ __forceinline__ void bn_affine4(const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma,
                                            const float* __restrict__ beta, int c, float4& mu, float4& inv, float4& sc, float4& sh) {
     mu = *(const float4*)(mean + c); inv = *(const float4*)(invstd + c);
@@ -44,6 +45,72 @@ __device__ __forceinline__ void bn_affine4(const float* __restrict__ mean, const
     sh.x = fmaf(-mu.x, sc.x, b.x); sh.y = fmaf(-mu.y, sc.y, b.y); sh.z = fmaf(-mu.z, sc.z, b.z); sh.w = fmaf(-mu.w, sc.w, b.w);
 }
 
+// The forward's affine from statistics just FINISHED: what norm_write_stat stores as stat[2], stat[3] and the one-launch forms apply
+__device__ __forceinline__ float norm_shift1(float mean, float scale, float beta) { return beta - mean * scale; }
+__device__ __forceinline__ void norm_affine4(const float4 mean, const float4 invstd, const float* gamma, const float* beta, int c,
+                                             float4& sc, float4& sh) {
+    const float4 g = *(const float4*)(gamma + c), b = *(const float4*)(beta + c);
+    sc.x = g.x * invstd.x; sc.y = g.y * invstd.y; sc.z = g.z * invstd.z; sc.w = g.w * invstd.w;
+    sh.x = norm_shift1(mean.x, sc.x, b.x); sh.y = norm_shift1(mean.y, sc.y, b.y); sh.z = norm_shift1(mean.z, sc.z, b.z); sh.w = norm_shift1(mean.w, sc.w, b.w);
+}
+
+__device__ __forceinline__ void add4(float4& t, const float4& v) { t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
+// sa += x, sb += x * x
+__device__ __forceinline__ void norm_sums4(const float4& v, float4& sa, float4& sb) {
+    sa.x += v.x; sa.y += v.y; sa.z += v.z; sa.w += v.w;
+    sb.x = fmaf(v.x, v.x, sb.x); sb.y = fmaf(v.y, v.y, sb.y); sb.z = fmaf(v.z, v.z, sb.z); sb.w = fmaf(v.w, v.w, sb.w);
+}
+// y = lrelu(scale * x + shift)
+__device__ __forceinline__ float4 norm_fwd4(const float4 v, const float4 sc, const float4 sh, float leak) {
+    return make_float4(norm_fwd1(v.x, sc.x, sh.x, leak), norm_fwd1(v.y, sc.y, sh.y, leak), norm_fwd1(v.z, sc.z, sh.z, leak), norm_fwd1(v.w, sc.w, sh.w, leak));
+}
+// d = dy * lrelu'(scale * x + shift)
+__device__ __forceinline__ float4 norm_d4(const float4 x, const float4 dy, const float4 sc, const float4 sh, float leak) {
+    return make_float4(norm_d1(x.x, dy.x, sc.x, sh.x, leak), norm_d1(x.y, dy.y, sc.y, sh.y, leak), norm_d1(x.z, dy.z, sc.z, sh.z, leak), norm_d1(x.w, dy.w, sc.w, sh.w, leak));
+}
+// ... with sa += d, sb += d * xhat
+__device__ __forceinline__ float4 norm_d_acc4(const float4 x, const float4 dy, const float4 mu, const float4 inv, const float4 sc, const float4 sh, float leak,
+                                              float4& sa, float4& sb) {
+    float4 d;
+    d.x = norm_d_acc1(x.x, dy.x, mu.x, inv.x, sc.x, sh.x, leak, sa.x, sb.x); d.y = norm_d_acc1(x.y, dy.y, mu.y, inv.y, sc.y, sh.y, leak, sa.y, sb.y);
+    d.z = norm_d_acc1(x.z, dy.z, mu.z, inv.z, sc.z, sh.z, leak, sa.z, sb.z); d.w = norm_d_acc1(x.w, dy.w, mu.w, inv.w, sc.w, sh.w, leak, sa.w, sb.w);
+    return d;
+}
+// dx = gamma * invstd * (d - m1 - xhat * m2)
+__device__ __forceinline__ float4 norm_dx4(const float4 x, const float4 d, const float4 mu, const float4 inv, const float4 sc, const float4 m1, const float4 m2) {
+    return make_float4(norm_dx1(x.x, d.x, mu.x, inv.x, sc.x, m1.x, m2.x), norm_dx1(x.y, d.y, mu.y, inv.y, sc.y, m1.y, m2.y),
+                       norm_dx1(x.z, d.z, mu.z, inv.z, sc.z, m1.z, m2.z), norm_dx1(x.w, d.w, mu.w, inv.w, sc.w, m1.w, m2.w));
+}
+// ... straight from dy
+__device__ __forceinline__ float4 norm_bwd4(const float4 x, const float4 dy, const float4 mu, const float4 inv, const float4 sc, const float4 sh, const float4 m1,
+                                            const float4 m2, float leak) {
+    return norm_dx4(x, norm_d4(x, dy, sc, sh, leak), mu, inv, sc, m1, m2);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The finish of a channel's statistics from its two sums over M rows, in double
+// ------------------------------------------------------------------------------------------------
+// forward (a = sum x, b = sum x * x): mean (in double: the callers round it) and invstd = 1 / sqrt(var + eps), var = E[x^2] - mean^2 clamped at 0 (zero_var: var IS 0)
+struct MeanInvstd { double mean; float invstd; };
+__device__ __forceinline__ MeanInvstd norm_stats_finish(double a, double b, double M, float eps, bool zero_var = false) {
+    const double mean = a / M;
+    double var = b / M - mean * mean;
+    if (var < 0.0 || zero_var) var = 0.0;
+    return MeanInvstd{mean, (float)(1.0 / sqrt(var + (double)eps))};
+}
+// backward: stat2 = {m1, m2} = {norm_mean_finish(sum d), norm_mean_finish(sum d * xhat)}
+__device__ __forceinline__ float norm_mean_finish(double sum, double M) { return (float)(sum / M); }
+// stat[4][C] = {mean, invstd, scale, shift} of channel c, which bn_apply_fwd_kernel reads, and the saved mean / invstd
+__device__ __forceinline__ void norm_write_stat(const MeanInvstd t, const float* gamma, const float* beta, int c, int C, float* stat, float* mean_out,
+                                                float* invstd_out) {
+    const float invstd = t.invstd, scale = gamma[c] * invstd, mean = (float)t.mean;
+    stat[c] = mean; stat[C + c] = invstd; stat[2 * C + c] = scale; stat[3 * C + c] = norm_shift1(mean, scale, beta[c]);
+    mean_out[c] = mean; invstd_out[c] = invstd;
+}
+
+// MODE 0: a = x, b = x*x.   MODE 1: a = dy', b = dy'*xhat  (dy' = dy * lrelu'(scale*x+shift))
+// 16-byte loads: a thread owns 4 consecutive channels and strides over the block's rows; the row groups of a
+// block are combined through LDS in a fixed order (deterministic).  C % 4 == 0.
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                          const float* __restrict__ mean_p, const float* __restrict__ invstd_p /* [groups][C] */,
@@ -65,36 +132,23 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
     const int rg = tid / tpr, RG = 256 / tpr, tc = tid - rg * tpr;
     for (int q0 = 0; q0 < CQ; q0 += tpr) {
         const int cq = q0 + tc;
-        float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = sa;
+        float4 sa = zero4(), sb = sa;
         if (cq < CQ) {
             float4 mean = sa, invstd = sa, scale = sa, shift = sa;
             if (MODE == 1) bn_affine4(mean_p, invstd_p, gamma, beta, 4 * cq, mean, invstd, scale, shift);
             for (int r = r0 + rg; r < r1; r += RG) {
                 const float4 xv = ((const float4*)(x + (size_t)r * C))[cq];
-                if (MODE == 0) {
-                    sa.x += xv.x; sa.y += xv.y; sa.z += xv.z; sa.w += xv.w;
-                    sb.x = fmaf(xv.x, xv.x, sb.x); sb.y = fmaf(xv.y, xv.y, sb.y); sb.z = fmaf(xv.z, xv.z, sb.z); sb.w = fmaf(xv.w, xv.w, sb.w);
-                } else {
-                    const float4 dv = ((const float4*)(dy + (size_t)r * C))[cq];
-#define P1(f)                                                                   \
-                    {                                                           \
-                        const float u = fmaf(xv.f, scale.f, shift.f);           \
-                        const float d = dv.f * (u > 0.f ? 1.f : leak);          \
-                        sa.f += d; sb.f = fmaf(d, (xv.f - mean.f) * invstd.f, sb.f); \
-                    }
-                    P1(x) P1(y) P1(z) P1(w)
-#undef P1
-                }
+                if (MODE == 0) norm_sums4(xv, sa, sb);
+                else norm_d_acc4(xv, ((const float4*)(dy + (size_t)r * C))[cq], mean, invstd, scale, shift, leak, sa, sb);
             }
         }
         red[0][tid] = sa; red[1][tid] = sb;
         __syncthreads();
         if (rg == 0 && cq < CQ) {
-            float4 ta = make_float4(0.f, 0.f, 0.f, 0.f), tb = ta;
+            float4 ta = zero4(), tb = ta;
             for (int gq = 0; gq < RG; ++gq) {
                 const float4 a = red[0][gq * tpr + tc], b = red[1][gq * tpr + tc];
-                ta.x += a.x; ta.y += a.y; ta.z += a.z; ta.w += a.w;
-                tb.x += b.x; tb.y += b.y; tb.z += b.z; tb.w += b.w;
+                add4(ta, a); add4(tb, b);
             }
             ((float4*)(part + ((size_t)blockIdx.x * 2 + 0) * C))[cq] = ta;
             ((float4*)(part + ((size_t)blockIdx.x * 2 + 1) * C))[cq] = tb;
@@ -135,19 +189,13 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
     a = 0.0; b = 0.0;
     for (int i = 0; i < BNF_SL; ++i) { a += red[0][i][cl]; b += red[1][i][cl]; }
     if (MODE == 0) {
-        const double mean = a / M;
-        double var = b / M - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-        const float scale = gamma[c] * invstd;
-        stat[c] = (float)mean; stat[C + c] = invstd; stat[2 * C + c] = scale; stat[3 * C + c] = beta[c] - (float)mean * scale;
-        mean_out[c] = (float)mean; invstd_out[c] = invstd;
+        norm_write_stat(norm_stats_finish(a, b, M, eps), gamma, beta, c, C, stat, mean_out, invstd_out);
     } else {
-        stat[c] = (float)(a / M); stat[C + c] = (float)(b / M);
+        stat[c] = norm_mean_finish(a, M); stat[C + c] = norm_mean_finish(b, M);
     }
 }
 
-// Two-stage form of bn_finalize_kernel<0> for the many partial rows a fused convolution leaves (two per 128-row m-tile: G = 4096
+// Two-stage form of bn_finalize_kernel for the many partial rows a fused convolution leaves (two per 128-row m-tile: G = 4096
 // for the 16x16x128 layer at batch 1024; the one-stage kernel has C/8 = 16 blocks walk them in 128 dependent steps: 23 us).
 // Stage A: block (channel group, slice) sums its slice of the rows in double; stage B: one thread per channel adds the slices
 // in a fixed order and finishes the statistics.  No atomics: deterministic.
@@ -169,39 +217,43 @@ __global__ __launch_bounds__(256) void bn_slice_sums_kernel(const float* __restr
     slices[((size_t)blockIdx.y * 2 + 0) * C + c] = a; slices[((size_t)blockIdx.y * 2 + 1) * C + c] = b;
 }
 
-__global__ void bn_finalize_slices_kernel(const double* __restrict__ slices, int M, int C, const float* __restrict__ gamma,
+// Stage B, forward and backward (stat2, when the producing backward-data launch left the two column sums as partial rows:
+// cgs_norm_lrelu_bwd_from_partials): slices is [nslices][2][C] double.  With ONE slice these are the second halves of the synchronised
+// form below, whose caller all-reduced the [2][C] sums over the ranks; M is then the global row count (0.0 + s == s: the same statistics).
+__device__ __forceinline__ void add_slices(const double* slices, int nslices, int C, int c, double& a, double& b) {
+    a = 0.0; b = 0.0;
+    for (int i = 0; i < nslices; ++i) { a += slices[((size_t)i * 2 + 0) * C + c]; b += slices[((size_t)i * 2 + 1) * C + c]; }
+}
+
+__global__ void bn_finalize_slices_kernel(const double* __restrict__ slices, int nslices, double M, int C, const float* __restrict__ gamma,
                                           const float* __restrict__ beta, float eps, float* __restrict__ stat,
                                           float* __restrict__ mean_out, float* __restrict__ invstd_out) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    double a = 0.0, b = 0.0;
-    for (int i = 0; i < BNF_SLICES; ++i) { a += slices[((size_t)i * 2 + 0) * C + c]; b += slices[((size_t)i * 2 + 1) * C + c]; }
-    const double mean = a / M;
-    double var = b / M - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float scale = gamma[c] * invstd;
-    stat[c] = (float)mean; stat[C + c] = invstd; stat[2 * C + c] = scale; stat[3 * C + c] = beta[c] - (float)mean * scale;
-    mean_out[c] = (float)mean; invstd_out[c] = invstd;
+    double a, b;
+    add_slices(slices, nslices, C, c, a, b);
+    norm_write_stat(norm_stats_finish(a, b, M, eps), gamma, beta, c, C, stat, mean_out, invstd_out);
 }
 
-// ... and for the two backward column sums (stat2 = {mean(dy'), mean(dy' * xhat)}) when the producing backward-data launch left them
-// as partial rows (cgs_norm_lrelu_bwd_from_partials).
-__global__ void bn_finalize2_slices_kernel(const double* __restrict__ slices, int M, int C, float* __restrict__ stat2) {
+__global__ void bn_finalize2_slices_kernel(const double* __restrict__ slices, int nslices, double M, int C, float* __restrict__ stat2) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    double a = 0.0, b = 0.0;
-    for (int i = 0; i < BNF_SLICES; ++i) { a += slices[((size_t)i * 2 + 0) * C + c]; b += slices[((size_t)i * 2 + 1) * C + c]; }
-    stat2[c] = (float)(a / M); stat2[C + c] = (float)(b / M);
+    double a, b;
+    add_slices(slices, nslices, C, c, a, b);
+    stat2[c] = norm_mean_finish(a, M); stat2[C + c] = norm_mean_finish(b, M);
 }
 
 // The two streaming passes of a norm.  A thread walks the tensor with a stride of gridDim.x * 256 float4; whenever that stride is a
 // whole number of channel rows (C | 1024 * gridDim.x: every power-of-two channel count), its four channels never change, so the
 // per-channel parameters are loaded ONCE per thread (and group) instead of with every element -- the element loop then issues one
 // 16-byte load per 16 bytes streamed (round 3's form: 3 loads forward, 8 backward, all through the same vector-memory path: 4.5-4.8 TB/s).
-// Same arithmetic, same order: bit-identical results.
+// Both loops run the same body (norm_fwd4 / norm_bwd4) on the same parameters: bit-identical results.
 
 // y = lrelu(scale*x + shift)
+__device__ __forceinline__ void apply_fwd_params(const float* stat /* [4][C] of the group */, int C, int c, float4& sc, float4& sh) {
+    sc = *(const float4*)(stat + 2 * C + c); sh = *(const float4*)(stat + 3 * C + c);
+}
+
 __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const float* __restrict__ x, const float* __restrict__ stat0,
                                                            float leak, float* __restrict__ y, size_t n4, int C, size_t group_n4) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -210,18 +262,14 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const float* __restri
     if (((stride * 4) % (size_t)C) == 0) {                     // (wave-uniform)
         const int c = (int)((i * 4) % C);
         size_t grp = i / group_n4, grp_end = (grp + 1) * group_n4;
-        float4 sc = *(const float4*)(stat0 + grp * 4 * C + 2 * C + c), sh = *(const float4*)(stat0 + grp * 4 * C + 3 * C + c);
+        float4 sc, sh;
+        apply_fwd_params(stat0 + grp * 4 * C, C, c, sc, sh);
         for (; i < n4; i += stride) {
             if (i >= grp_end) {                                // next group of images (instance norm / fused logical batches)
                 grp = i / group_n4; grp_end = (grp + 1) * group_n4;
-                sc = *(const float4*)(stat0 + grp * 4 * C + 2 * C + c); sh = *(const float4*)(stat0 + grp * 4 * C + 3 * C + c);
+                apply_fwd_params(stat0 + grp * 4 * C, C, c, sc, sh);
             }
-            const float4 v = ((const float4*)x)[i];
-            float4 o;
-            o.x = fmaf(v.x, sc.x, sh.x); o.y = fmaf(v.y, sc.y, sh.y); o.z = fmaf(v.z, sc.z, sh.z); o.w = fmaf(v.w, sc.w, sh.w);
-            o.x = o.x > 0.f ? o.x : leak * o.x; o.y = o.y > 0.f ? o.y : leak * o.y;
-            o.z = o.z > 0.f ? o.z : leak * o.z; o.w = o.w > 0.f ? o.w : leak * o.w;
-            ((float4*)y)[i] = o;
+            ((float4*)y)[i] = norm_fwd4(((const float4*)x)[i], sc, sh, leak);
         }
         return;
     }
@@ -232,22 +280,17 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const float* __restri
         const int c = (int)((i * 4) % C);
         const float4 v = ((const float4*)x)[i];
         const float4 sc = *(const float4*)(scale + c), sh = *(const float4*)(shift + c);
-        float4 o;
-        o.x = fmaf(v.x, sc.x, sh.x); o.y = fmaf(v.y, sc.y, sh.y); o.z = fmaf(v.z, sc.z, sh.z); o.w = fmaf(v.w, sc.w, sh.w);
-        o.x = o.x > 0.f ? o.x : leak * o.x; o.y = o.y > 0.f ? o.y : leak * o.y;
-        o.z = o.z > 0.f ? o.z : leak * o.z; o.w = o.w > 0.f ? o.w : leak * o.w;
-        ((float4*)y)[i] = o;
+        ((float4*)y)[i] = norm_fwd4(v, sc, sh, leak);
     }
 }
 
 // dx = gamma*invstd*(dy' - m1 - xhat*m2)
-#define BWD1(f)                                                       \
-        {                                                             \
-            const float u = fmaf(xv.f, sc.f, sh.f);                   \
-            const float d = dv.f * (u > 0.f ? 1.f : leak);            \
-            const float xh = (xv.f - mean.f) * inv.f;                 \
-            o.f = sc.f * (d - m1.f - xh * m2.f);                      \
-        }
+__device__ __forceinline__ void apply_bwd_params(const float* mean0, const float* invstd0, const float* gamma, const float* beta, const float* stat20, size_t grp,
+                                                 int C, int c, float4& mean, float4& inv, float4& sc, float4& sh, float4& m1, float4& m2) {
+    bn_affine4(mean0 + grp * C, invstd0 + grp * C, gamma, beta, c, mean, inv, sc, sh);
+    m1 = *(const float4*)(stat20 + grp * 2 * C + c); m2 = *(const float4*)(stat20 + grp * 2 * C + C + c);
+}
+
 __global__ __launch_bounds__(256) void bn_apply_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                            const float* __restrict__ mean0, const float* __restrict__ invstd0,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -256,36 +299,24 @@ __global__ __launch_bounds__(256) void bn_apply_bwd_kernel(const float* __restri
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
+    float4 mean, inv, sc, sh, m1, m2;
     if (((stride * 4) % (size_t)C) == 0) {                     // (wave-uniform) the thread's four channels are fixed: parameters once per group
         const int c = (int)((i * 4) % C);
         size_t grp = i / group_n4, grp_end = (grp + 1) * group_n4;
-        float4 mean, inv, sc, sh, m1, m2;
-        bn_affine4(mean0 + grp * C, invstd0 + grp * C, gamma, beta, c, mean, inv, sc, sh);
-        m1 = *(const float4*)(stat20 + grp * 2 * C + c); m2 = *(const float4*)(stat20 + grp * 2 * C + C + c);
+        apply_bwd_params(mean0, invstd0, gamma, beta, stat20, grp, C, c, mean, inv, sc, sh, m1, m2);
         for (; i < n4; i += stride) {
             if (i >= grp_end) {
                 grp = i / group_n4; grp_end = (grp + 1) * group_n4;
-                bn_affine4(mean0 + grp * C, invstd0 + grp * C, gamma, beta, c, mean, inv, sc, sh);
-                m1 = *(const float4*)(stat20 + grp * 2 * C + c); m2 = *(const float4*)(stat20 + grp * 2 * C + C + c);
+                apply_bwd_params(mean0, invstd0, gamma, beta, stat20, grp, C, c, mean, inv, sc, sh, m1, m2);
             }
-            const float4 xv = ((const float4*)x)[i], dv = ((const float4*)dy)[i];
-            float4 o;
-            BWD1(x) BWD1(y) BWD1(z) BWD1(w)
-            ((float4*)dx)[i] = o;
+            ((float4*)dx)[i] = norm_bwd4(((const float4*)x)[i], ((const float4*)dy)[i], mean, inv, sc, sh, m1, m2, leak);
         }
         return;
     }
     for (; i < n4; i += stride) {
-        const size_t grp = i / group_n4;
-        const float* stat2 = stat20 + grp * 2 * C;
-        const int c = (int)((i * 4) % C);
         const float4 xv = ((const float4*)x)[i], dv = ((const float4*)dy)[i];
-        float4 mean, inv, sc, sh;
-        bn_affine4(mean0 + grp * C, invstd0 + grp * C, gamma, beta, c, mean, inv, sc, sh);
-        const float4 m1 = *(const float4*)(stat2 + c), m2 = *(const float4*)(stat2 + C + c);
-        float4 o;
-        BWD1(x) BWD1(y) BWD1(z) BWD1(w)
-        ((float4*)dx)[i] = o;
+        apply_bwd_params(mean0, invstd0, gamma, beta, stat20, i / group_n4, C, (int)((i * 4) % C), mean, inv, sc, sh, m1, m2);
+        ((float4*)dx)[i] = norm_bwd4(xv, dv, mean, inv, sc, sh, m1, m2, leak);
     }
 }
 
@@ -310,30 +341,18 @@ __global__ __launch_bounds__(256) void norm_small_kernel(const float* __restrict
     const bool live = c < C;
     const size_t base = (size_t)grp * M * C;
     float4 xv[NS_ROWS], dv[NS_ROWS];
-    float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = sa;
+    float4 sa = zero4(), sb = sa;
     float4 mu = sa, inv = sa, sc = sa, sh = sa;
     if (BWD && live) bn_affine4(mean_io + (size_t)grp * C, invstd_io + (size_t)grp * C, gamma, beta, c, mu, inv, sc, sh);
 #pragma unroll
     for (int i = 0; i < NS_ROWS; ++i) {
         const int r = rl + 16 * i;
-        xv[i] = make_float4(0.f, 0.f, 0.f, 0.f); dv[i] = xv[i];
+        xv[i] = zero4(); dv[i] = xv[i];
         if (live && r < M) {
             xv[i] = *(const float4*)(x + base + (size_t)r * C + c);
             if (BWD) dv[i] = *(const float4*)(dy + base + (size_t)r * C + c);
-            if (!BWD) {
-                sa.x += xv[i].x; sa.y += xv[i].y; sa.z += xv[i].z; sa.w += xv[i].w;
-                sb.x = fmaf(xv[i].x, xv[i].x, sb.x); sb.y = fmaf(xv[i].y, xv[i].y, sb.y); sb.z = fmaf(xv[i].z, xv[i].z, sb.z); sb.w = fmaf(xv[i].w, xv[i].w, sb.w);
-            } else {
-#define NS1(f)                                                                          \
-                {                                                                       \
-                    const float u = fmaf(xv[i].f, sc.f, sh.f);                          \
-                    const float d = dv[i].f * (u > 0.f ? 1.f : leak);                   \
-                    dv[i].f = d;                                                        \
-                    sa.f += d; sb.f = fmaf(d, (xv[i].f - mu.f) * inv.f, sb.f);          \
-                }
-                NS1(x) NS1(y) NS1(z) NS1(w)
-#undef NS1
-            }
+            if (!BWD) norm_sums4(xv[i], sa, sb);
+            else dv[i] = norm_d_acc4(xv[i], dv[i], mu, inv, sc, sh, leak, sa, sb);        // (dv holds d from here on)
         }
     }
     red[0][rl][q] = sa; red[1][rl][q] = sb;
@@ -347,18 +366,16 @@ __global__ __launch_bounds__(256) void norm_small_kernel(const float* __restrict
         }
         float o0[4], o1[4];
         if (!BWD) {
+            // (one row: the variance IS 0; b - mean^2 is then only the float rounding of x*x, up to 6e-8 * x^2 -- against eps = 1e-5 that moved
+            // the saved invstd by up to 4 % at |x| ~ 2)
             for (int e = 0; e < 4; ++e) {
-                const double mean = a[e] / M;
-                double var = b[e] / M - mean * mean;
-                // (one row: the variance IS 0; b - mean^2 is then only the float rounding of x*x, up to 6e-8 * x^2 -- against eps = 1e-5 that moved
-                // the saved invstd by up to 4 % at |x| ~ 2)
-                if (var < 0.0 || M == 1) var = 0.0;
-                o0[e] = (float)mean; o1[e] = (float)(1.0 / sqrt(var + (double)eps));
+                const MeanInvstd t = norm_stats_finish(a[e], b[e], M, eps, M == 1);
+                o0[e] = (float)t.mean; o1[e] = t.invstd;
             }
             *(float4*)(mean_io + (size_t)grp * C + c) = make_float4(o0[0], o0[1], o0[2], o0[3]);
             *(float4*)(invstd_io + (size_t)grp * C + c) = make_float4(o1[0], o1[1], o1[2], o1[3]);
         } else {
-            for (int e = 0; e < 4; ++e) { o0[e] = (float)(a[e] / M); o1[e] = (float)(b[e] / M); }
+            for (int e = 0; e < 4; ++e) { o0[e] = norm_mean_finish(a[e], M); o1[e] = norm_mean_finish(b[e], M); }
             if (stat2) {
                 *(float4*)(stat2 + (size_t)grp * 2 * C + c) = make_float4(o0[0], o0[1], o0[2], o0[3]);
                 *(float4*)(stat2 + (size_t)grp * 2 * C + C + c) = make_float4(o1[0], o1[1], o1[2], o1[3]);
@@ -368,36 +385,25 @@ __global__ __launch_bounds__(256) void norm_small_kernel(const float* __restrict
     }
     __syncthreads();
     if (!live) return;
-    const float4 s0 = bc[0][q], s1 = bc[1][q];
-    if (!BWD) {      // y = lrelu(scale * x + shift): the affine exactly as bn_finalize_kernel<0> forms it
-        const float4 g = *(const float4*)(gamma + c), bt = *(const float4*)(beta + c);
+    const float4 s0 = bc[0][q], s1 = bc[1][q];       // forward: mean, invstd; backward: m1, m2
+    if (!BWD) {
         float4 scl, shf;
-        scl.x = g.x * s1.x; scl.y = g.y * s1.y; scl.z = g.z * s1.z; scl.w = g.w * s1.w;
-        shf.x = bt.x - s0.x * scl.x; shf.y = bt.y - s0.y * scl.y; shf.z = bt.z - s0.z * scl.z; shf.w = bt.w - s0.w * scl.w;
+        norm_affine4(s0, s1, gamma, beta, c, scl, shf);
         // (one row: x - mean IS 0 and y = lrelu(beta); with scale = gamma / sqrt(eps) the rounding of shift ~ -316 * gamma * x alone left
         // y off by half an ulp of it, 3e-5 at |x| ~ 3, on values of ~0.1)
-        if (M == 1) { scl = make_float4(0.f, 0.f, 0.f, 0.f); shf = bt; }
+        if (M == 1) { scl = zero4(); shf = *(const float4*)(beta + c); }
 #pragma unroll
         for (int i = 0; i < NS_ROWS; ++i) {
             const int r = rl + 16 * i;
             if (r >= M) break;
-            float4 o;
-            o.x = fmaf(xv[i].x, scl.x, shf.x); o.y = fmaf(xv[i].y, scl.y, shf.y); o.z = fmaf(xv[i].z, scl.z, shf.z); o.w = fmaf(xv[i].w, scl.w, shf.w);
-            o.x = o.x > 0.f ? o.x : leak * o.x; o.y = o.y > 0.f ? o.y : leak * o.y;
-            o.z = o.z > 0.f ? o.z : leak * o.z; o.w = o.w > 0.f ? o.w : leak * o.w;
-            *(float4*)(out + base + (size_t)r * C + c) = o;
+            *(float4*)(out + base + (size_t)r * C + c) = norm_fwd4(xv[i], scl, shf, leak);
         }
-    } else {         // dx = gamma * invstd * (dy' - m1 - xhat * m2)
+    } else {
 #pragma unroll
         for (int i = 0; i < NS_ROWS; ++i) {
             const int r = rl + 16 * i;
             if (r >= M) break;
-            float4 o;
-            o.x = sc.x * (dv[i].x - s0.x - (xv[i].x - mu.x) * inv.x * s1.x);
-            o.y = sc.y * (dv[i].y - s0.y - (xv[i].y - mu.y) * inv.y * s1.y);
-            o.z = sc.z * (dv[i].z - s0.z - (xv[i].z - mu.z) * inv.z * s1.z);
-            o.w = sc.w * (dv[i].w - s0.w - (xv[i].w - mu.w) * inv.w * s1.w);
-            *(float4*)(out + base + (size_t)r * C + c) = o;
+            *(float4*)(out + base + (size_t)r * C + c) = norm_dx4(xv[i], dv[i], mu, inv, sc, s0, s1);
         }
     }
 }
@@ -419,7 +425,7 @@ static unsigned ew_blocks(size_t n) {
 // the finalize kernel and the apply kernel are two dependent launches of ~5 us each whatever they do -- 6 of the ~40 launches of a refinement
 // step on the DCGAN nets.  Here every block re-derives the statistics of its 64 channels from the partial rows (<= 256 rows x 2 x 64 floats out
 // of L2: 16 row lanes sum their rows in double in index order, the 16 lane sums are added in index order -- deterministic) and applies them to its
-// chunk of rows; the block of the first chunk also writes the saved mean / invstd (forward).  Same formulas as bn_finalize_kernel + bn_apply_*.
+// chunk of rows; the block of the first chunk also writes the saved mean / invstd (forward).
 // Taken for groups of <= 16 partial rows and tensors of <= 2 MB (norm_fa_rows_per_block): beyond, the per-block re-derivation costs what the launch saved.
 // Layout of the partial rows as in bn_finalize_kernel: group g owns, for every segment sg < nseg, the rows sg * seg_stride + g * R ... + R - 1.
 // ------------------------------------------------------------------------------------------------
@@ -455,14 +461,8 @@ __global__ __launch_bounds__(256) void norm_fa_kernel(const float* __restrict__ 
         for (int e = 0; e < 4; ++e) {
             double sa = 0.0, sb = 0.0;
             for (int i = 0; i < 16; ++i) { sa += red[0][i][q][e]; sb += red[1][i][q][e]; }
-            if (!BWD) {
-                const double mean = sa / M;
-                double var = sb / M - mean * mean;
-                if (var < 0.0) var = 0.0;
-                o0[e] = (float)mean; o1[e] = (float)(1.0 / sqrt(var + (double)eps));
-            } else {
-                o0[e] = (float)(sa / M); o1[e] = (float)(sb / M);
-            }
+            if (!BWD) { const MeanInvstd t = norm_stats_finish(sa, sb, M, eps); o0[e] = (float)t.mean; o1[e] = t.invstd; }
+            else { o0[e] = norm_mean_finish(sa, M); o1[e] = norm_mean_finish(sb, M); }
         }
         bc[0][q] = make_float4(o0[0], o0[1], o0[2], o0[3]); bc[1][q] = make_float4(o1[0], o1[1], o1[2], o1[3]);
         if (!BWD && blockIdx.y == 0) {
@@ -472,36 +472,23 @@ __global__ __launch_bounds__(256) void norm_fa_kernel(const float* __restrict__ 
     }
     __syncthreads();
     if (!live) return;
-    const float4 s0 = bc[0][q], s1 = bc[1][q];
+    const float4 s0 = bc[0][q], s1 = bc[1][q];       // forward: mean, invstd; backward: m1, m2
     const int r0 = blockIdx.y * rows_per_block, r1 = min(M, r0 + rows_per_block);
     const size_t base = (size_t)grp * M * C + c;
-    if (!BWD) {      // y = lrelu(scale * x + shift): the affine exactly as bn_finalize_kernel<0> forms it
-        const float4 g = *(const float4*)(gamma + c), bt = *(const float4*)(beta + c);
+    if (!BWD) {
         float4 sc, sh;
-        sc.x = g.x * s1.x; sc.y = g.y * s1.y; sc.z = g.z * s1.z; sc.w = g.w * s1.w;
-        sh.x = bt.x - s0.x * sc.x; sh.y = bt.y - s0.y * sc.y; sh.z = bt.z - s0.z * sc.z; sh.w = bt.w - s0.w * sc.w;
-        for (int r = r0 + rl; r < r1; r += 16) {
-            const float4 v = *(const float4*)(x + base + (size_t)r * C);
-            float4 o;
-            o.x = fmaf(v.x, sc.x, sh.x); o.y = fmaf(v.y, sc.y, sh.y); o.z = fmaf(v.z, sc.z, sh.z); o.w = fmaf(v.w, sc.w, sh.w);
-            o.x = o.x > 0.f ? o.x : leak * o.x; o.y = o.y > 0.f ? o.y : leak * o.y;
-            o.z = o.z > 0.f ? o.z : leak * o.z; o.w = o.w > 0.f ? o.w : leak * o.w;
-            *(float4*)(out + base + (size_t)r * C) = o;
-        }
-    } else {         // dx = gamma * invstd * (dy' - m1 - xhat * m2)   (dy / dx may be the same buffer: every thread reads its element before it writes it)
+        norm_affine4(s0, s1, gamma, beta, c, sc, sh);
+        for (int r = r0 + rl; r < r1; r += 16)
+            *(float4*)(out + base + (size_t)r * C) = norm_fwd4(*(const float4*)(x + base + (size_t)r * C), sc, sh, leak);
+    } else {         // (dy / dx may be the same buffer: every thread reads its element before it writes it)
         float4 mean, inv, sc, sh;
         bn_affine4(mean_io + (size_t)grp * C, invstd_io + (size_t)grp * C, gamma, beta, c, mean, inv, sc, sh);
-        const float4 m1 = s0, m2 = s1;
         for (int r = r0 + rl; r < r1; r += 16) {
             const float4 xv = *(const float4*)(x + base + (size_t)r * C), dv = *(const float4*)(dy + base + (size_t)r * C);
-            float4 o;
-            BWD1(x) BWD1(y) BWD1(z) BWD1(w)
-            *(float4*)(out + base + (size_t)r * C) = o;
+            *(float4*)(out + base + (size_t)r * C) = norm_bwd4(xv, dv, mean, inv, sc, sh, s0, s1, leak);
         }
     }
 }
-
-#undef BWD1
 
 // rows per block of norm_fa_kernel for a call, 0 = the two-launch form serves it (too many partial rows, or a tensor large enough that the
 // statistics' re-derivation per block and the plain row loop would cost more than the launch they save)
@@ -523,27 +510,103 @@ static int norm_fa_rows_per_block(int groups, int rows_per_seg, int nseg, int M_
     return (int)rpb;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Host side.  A norm's workspace is part | stat[groups][4][C] | stat2[groups][2][C]: the stage-1 partial rows, what bn_apply_fwd_kernel
+// reads, and {mean(d), mean(d * xhat)}, which the backward leaves for the parameter gradients (wgrad.hip, wgrad_dot.hip: through the
+// offset functions).  Batch norm: one group, room for BN_MAX_BLOCKS partial rows.  Instance norm: a group per sample, in_geom rows each.
+// ------------------------------------------------------------------------------------------------
+struct NormWs { float *part, *stat, *stat2; };
+
+static NormWs carve_ws(void* ws, int groups, int C, size_t stat2_offset) {
+    float* part = (float*)ws;
+    return NormWs{part, part + stat2_offset - (size_t)groups * 4 * C, part + stat2_offset};
+}
+
+size_t cgs_bn_stat2_offset(int C) { return (size_t)BN_MAX_BLOCKS * 2 * C + 4 * (size_t)C; }
+size_t cgs_bn_ws_bytes(int M, int C) {
+    (void)M;
+    return (cgs_bn_stat2_offset(C) + 2 * (size_t)C) * sizeof(float);
+}
+static NormWs bn_ws(void* ws, int C) { return carve_ws(ws, 1, C, cgs_bn_stat2_offset(C)); }
+
+// the launches are done: a failed one is the entry point's error, else the path taken is left for cgs_last_kernel
+static int norm_launched(const char* who, const char* path = nullptr) {
+    CGS_CHECK_LAUNCH(who);
+    if (path) cgs_note_kernel(path);
+    return CGS_OK;
+}
+
+static void launch_apply_fwd(const float* x, const float* stat, float leak, float* y, int groups, int M, int C, hipStream_t s) {
+    const size_t n4 = (size_t)groups * M * C / 4, gn4 = (size_t)M * C / 4;
+    hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, x, stat, leak, y, n4, C, gn4);
+}
+
+static void launch_apply_bwd(const float* dy, const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                             const float* stat2, float leak, float* dx, int groups, int M, int C, hipStream_t s) {
+    const size_t n4 = (size_t)groups * M * C / 4, gn4 = (size_t)M * C / 4;
+    hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, dy, x, mean, invstd, gamma, beta, stat2, leak, dx, n4, C, gn4);
+}
+
+// stage 1 of the statistics: part[groups][g.G][2][C]; dy == null: sums of x and x * x, else of d and d * xhat
+static void launch_partial(const float* x, const float* dy, const float* mean, const float* invstd, const float* gamma, const float* beta, float leak,
+                           float* part, int groups, int M, int C, BnGeom g, hipStream_t s) {
+    if (!dy) hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(g.G, groups), dim3(256), 0, s, x, nullptr, nullptr, nullptr, nullptr, nullptr, leak, part, M, C, g.rows_per_block);
+    else hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(g.G, groups), dim3(256), 0, s, x, dy, mean, invstd, gamma, beta, leak, part, M, C, g.rows_per_block);
+}
+
+// Norm of x [groups][M][C] from x itself (batch norm: one group; instance norm: a group per sample): small groups in one launch from
+// registers, else partial sums -> finalize -> apply.
+static int norm_fwd_from_x(const char* who, const float* x, const float* gamma, const float* beta, float eps, float leak, float* y, float* mean,
+                           float* invstd, int groups, int M, int C, BnGeom g, NormWs w, hipStream_t s) {
+    if (norm_small_ok(M)) {
+        hipLaunchKernelGGL(norm_small_kernel<false>, dim3(cgs_ceil_div(C, 64), groups), dim3(256), 0, s, x, nullptr, gamma, beta, eps, leak, y, mean, invstd, nullptr, M, C);
+        return norm_launched(who, "norm_small_fwd");
+    }
+    launch_partial(x, nullptr, nullptr, nullptr, nullptr, nullptr, leak, w.part, groups, M, C, g, s);
+    hipLaunchKernelGGL(bn_finalize_kernel<0>, dim3(cgs_ceil_div(C, BNF_CH), groups), dim3(256), 0, s, w.part, g.G, M, C, gamma, beta, eps, w.stat, mean, invstd);
+    launch_apply_fwd(x, w.stat, leak, y, groups, M, C, s);
+    return norm_launched(who, "norm_passes_fwd");
+}
+
+// ... and its backward-data; both paths leave stat2 where the parameter-gradient calls read it
+static int norm_bwd_from_x(const char* who, const float* dy, const float* x, const float* gamma, const float* beta, const float* mean,
+                           const float* invstd, float leak, float* dx, int groups, int M, int C, BnGeom g, NormWs w, hipStream_t s) {
+    if (norm_small_ok(M)) {
+        hipLaunchKernelGGL(norm_small_kernel<true>, dim3(cgs_ceil_div(C, 64), groups), dim3(256), 0, s, x, dy, gamma, beta, 0.f, leak, dx, (float*)mean, (float*)invstd, w.stat2, M, C);
+        return norm_launched(who, "norm_small_bwd");
+    }
+    launch_partial(x, dy, mean, invstd, gamma, beta, leak, w.part, groups, M, C, g, s);
+    hipLaunchKernelGGL(bn_finalize_kernel<1>, dim3(cgs_ceil_div(C, BNF_CH), groups), dim3(256), 0, s, w.part, g.G, M, C, nullptr, nullptr, 0.f, w.stat2, nullptr, nullptr);
+    launch_apply_bwd(dy, x, mean, invstd, gamma, beta, w.stat2, leak, dx, groups, M, C, s);
+    return norm_launched(who, "norm_passes_bwd");
+}
+
+// Norm of x [groups][M][C] whose statistics the producing convolution left as partial rows (cgs_conv_stat_layout): few rows and a small
+// tensor in one launch, else finalize -> apply.  slices != null: the caller chose the two-stage finalize and this is its [BNF_SLICES][2][C].
+static int norm_fwd_from_partials(const char* who, const float* x, const float* part, int groups, int rows_per_seg, int nseg, int seg_stride,
+                                  const float* gamma, const float* beta, float eps, float leak, float* y, float* mean, float* invstd, int M, int C,
+                                  float* stat, double* slices, hipStream_t s) {
+    if (const int rpb = norm_fa_rows_per_block(groups, rows_per_seg, nseg, M, C)) {
+        hipLaunchKernelGGL(norm_fa_kernel<false>, dim3(cgs_ceil_div(C, 64), cgs_ceil_div(M, rpb), groups), dim3(256), 0, s, x, nullptr, part, rows_per_seg, nseg,
+                           seg_stride, gamma, beta, eps, leak, y, mean, invstd, M, C, rpb);
+        return norm_launched(who, "norm_fa_fwd");
+    }
+    if (slices) {
+        hipLaunchKernelGGL(bn_slice_sums_kernel, dim3(cgs_ceil_div(C, BNF_CH), BNF_SLICES), dim3(256), 0, s, part, rows_per_seg, C, slices);
+        hipLaunchKernelGGL(bn_finalize_slices_kernel, dim3(cgs_ceil_div(C, 64)), dim3(64), 0, s, slices, BNF_SLICES, (double)M, C, gamma, beta, eps, stat, mean, invstd);
+    } else {
+        hipLaunchKernelGGL(bn_finalize_kernel<0>, dim3(cgs_ceil_div(C, BNF_CH), groups), dim3(256), 0, s, part, rows_per_seg, M, C, gamma, beta, eps, stat,
+                           mean, invstd, nseg, seg_stride);
+    }
+    launch_apply_fwd(x, stat, leak, y, groups, M, C, s);
+    return norm_launched(who, slices ? "norm_sliced_fwd" : "norm_finalize_fwd");
+}
+
 int cgs_bn_train_lrelu_fwd(const float* x, const float* gamma, const float* beta, float eps, float leak, float* y,
                            float* mean, float* invstd, int M, int C, void* ws, size_t ws_bytes, void* stream) {
     if (M <= 0 || C <= 0 || (C & 3)) return cgs_set_error(CGS_EINVAL, "bn fwd: M=%d C=%d (C must be a multiple of 4)", M, C);
     if (ws_bytes < cgs_bn_ws_bytes(M, C)) return cgs_set_error(CGS_EWORKSPACE, "bn fwd: workspace %zu < %zu", ws_bytes, cgs_bn_ws_bytes(M, C));
-    hipStream_t s = (hipStream_t)stream;
-    if (norm_small_ok(M)) {               // one launch: statistics + apply from registers
-        hipLaunchKernelGGL(norm_small_kernel<false>, dim3(cgs_ceil_div(C, 64), 1), dim3(256), 0, s, x, nullptr, gamma, beta, eps, leak, y, mean, invstd, nullptr, M, C);
-        CGS_CHECK_LAUNCH("bn_train_lrelu_fwd");
-        cgs_note_kernel("norm_small_fwd");
-        return CGS_OK;
-    }
-    const BnGeom g = bn_geom(M, C);
-    float* part = (float*)ws;
-    float* stat = part + (size_t)BN_MAX_BLOCKS * 2 * C;
-    hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(g.G), dim3(256), 0, s, x, nullptr, nullptr, nullptr, nullptr, nullptr, leak, part, M, C, g.rows_per_block);
-    hipLaunchKernelGGL(bn_finalize_kernel<0>, dim3(cgs_ceil_div(C, BNF_CH)), dim3(256), 0, s, part, g.G, M, C, gamma, beta, eps, stat, mean, invstd);
-    const size_t n4 = (size_t)M * C / 4;
-    hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, x, stat, leak, y, n4, C, n4);
-    CGS_CHECK_LAUNCH("bn_train_lrelu_fwd");
-    cgs_note_kernel("norm_passes_fwd");
-    return CGS_OK;
+    return norm_fwd_from_x("bn_train_lrelu_fwd", x, gamma, beta, eps, leak, y, mean, invstd, 1, M, C, bn_geom(M, C), bn_ws(ws, C), (hipStream_t)stream);
 }
 
 int cgs_bn_train_lrelu_fwd_from_partials(const float* x, const float* part, int G, const float* gamma, const float* beta, float eps,
@@ -551,28 +614,10 @@ int cgs_bn_train_lrelu_fwd_from_partials(const float* x, const float* part, int 
                                          void* stream) {
     if (M <= 0 || C <= 0 || (C & 3) || G <= 0 || !part) return cgs_set_error(CGS_EINVAL, "bn fwd from partials: M=%d C=%d G=%d", M, C, G);
     if (ws_bytes < cgs_bn_ws_bytes(M, C)) return cgs_set_error(CGS_EWORKSPACE, "bn fwd: workspace %zu < %zu", ws_bytes, cgs_bn_ws_bytes(M, C));
-    hipStream_t s = (hipStream_t)stream;
-    if (const int rpb = norm_fa_rows_per_block(1, G, 1, M, C)) {          // few partial rows, small tensor: finalize + apply in one launch
-        hipLaunchKernelGGL(norm_fa_kernel<false>, dim3(cgs_ceil_div(C, 64), cgs_ceil_div(M, rpb), 1), dim3(256), 0, s, x, nullptr, part, G, 1, 0, gamma, beta, eps,
-                           leak, y, mean, invstd, M, C, rpb);
-        CGS_CHECK_LAUNCH("bn_train_lrelu_fwd_from_partials");
-        cgs_note_kernel("norm_fa_fwd");
-        return CGS_OK;
-    }
-    float* stat = (float*)ws + (size_t)BN_MAX_BLOCKS * 2 * C;
+    // (the workspace's own partial area is unused here and holds the slices: BN_MAX_BLOCKS * 2 * C floats >= 16 * 2 * C doubles)
     const bool sliced = G >= 1024 && !((uintptr_t)ws & 7);
-    if (sliced) {      // (the workspace's own partial area is unused on this path: BN_MAX_BLOCKS * 2 * C floats >= 16 * 2 * C doubles)
-        double* slices = (double*)ws;
-        hipLaunchKernelGGL(bn_slice_sums_kernel, dim3(cgs_ceil_div(C, BNF_CH), BNF_SLICES), dim3(256), 0, s, part, G, C, slices);
-        hipLaunchKernelGGL(bn_finalize_slices_kernel, dim3(cgs_ceil_div(C, 64)), dim3(64), 0, s, slices, M, C, gamma, beta, eps, stat, mean, invstd);
-    } else {
-        hipLaunchKernelGGL(bn_finalize_kernel<0>, dim3(cgs_ceil_div(C, BNF_CH)), dim3(256), 0, s, part, G, M, C, gamma, beta, eps, stat, mean, invstd);
-    }
-    const size_t n4 = (size_t)M * C / 4;
-    hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, x, stat, leak, y, n4, C, n4);
-    CGS_CHECK_LAUNCH("bn_train_lrelu_fwd_from_partials");
-    cgs_note_kernel(sliced ? "norm_sliced_fwd" : "norm_finalize_fwd");
-    return CGS_OK;
+    return norm_fwd_from_partials("bn_train_lrelu_fwd_from_partials", x, part, 1, G, 1, 0, gamma, beta, eps, leak, y, mean, invstd, M, C, bn_ws(ws, C).stat,
+                                  sliced ? (double*)ws : nullptr, (hipStream_t)stream);
 }
 
 int cgs_bn_train_lrelu_bwd_data(const float* dy, const float* x, const float* gamma, const float* beta, const float* mean,
@@ -580,32 +625,13 @@ int cgs_bn_train_lrelu_bwd_data(const float* dy, const float* x, const float* ga
                                 void* stream) {
     if (M <= 0 || C <= 0 || (C & 3)) return cgs_set_error(CGS_EINVAL, "bn bwd: M=%d C=%d (C must be a multiple of 4)", M, C);
     if (ws_bytes < cgs_bn_ws_bytes(M, C)) return cgs_set_error(CGS_EWORKSPACE, "bn bwd: workspace %zu < %zu", ws_bytes, cgs_bn_ws_bytes(M, C));
-    hipStream_t s = (hipStream_t)stream;
-    const BnGeom g = bn_geom(M, C);
-    float* part = (float*)ws;
-    float* stat = part + (size_t)BN_MAX_BLOCKS * 2 * C;           // [4][C]
-    float* stat2 = stat + 4 * (size_t)C;                          // [2][C]
-    if (norm_small_ok(M)) {               // one launch (stat2 is left where cgs_bn_train_param_grads reads it)
-        hipLaunchKernelGGL(norm_small_kernel<true>, dim3(cgs_ceil_div(C, 64), 1), dim3(256), 0, s, x, dy, gamma, beta, 0.f, leak, dx, (float*)mean, (float*)invstd, stat2, M, C);
-        CGS_CHECK_LAUNCH("bn_train_lrelu_bwd_data");
-        cgs_note_kernel("norm_small_bwd");
-        return CGS_OK;
-    }
-    hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(g.G), dim3(256), 0, s, x, dy, mean, invstd, gamma, beta, leak, part, M, C, g.rows_per_block);
-    hipLaunchKernelGGL(bn_finalize_kernel<1>, dim3(cgs_ceil_div(C, BNF_CH)), dim3(256), 0, s, part, g.G, M, C, nullptr, nullptr, 0.f, stat2, nullptr, nullptr);
-    const size_t n4 = (size_t)M * C / 4;
-    hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, dy, x, mean, invstd, gamma, beta, stat2, leak, dx, n4, C, n4);
-    CGS_CHECK_LAUNCH("bn_train_lrelu_bwd_data");
-    cgs_note_kernel("norm_passes_bwd");
-    return CGS_OK;
+    return norm_bwd_from_x("bn_train_lrelu_bwd_data", dy, x, gamma, beta, mean, invstd, leak, dx, 1, M, C, bn_geom(M, C), bn_ws(ws, C), (hipStream_t)stream);
 }
-
-
 
 // ------------------------------------------------------------------------------------------------
 // Synchronised batch statistics (one logical batch split over several GPUs; SURVEY.md 8e caveat).
 // The local reduction stops at per-channel SUMS in double; the caller all-reduces the 2*C doubles over the ranks
-// (RCCL) and the second half finishes the statistics from the global sums and the global row count.
+// (RCCL) and the second half finishes the statistics from the global sums and the global row count: the stage-B kernels above on one slice.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bn_sums_kernel(const float* __restrict__ part, int G, int C, double* __restrict__ sums) {
     __shared__ double red[2][16][17];
@@ -622,83 +648,53 @@ __global__ __launch_bounds__(256) void bn_sums_kernel(const float* __restrict__ 
     sums[c] = a; sums[C + c] = b;
 }
 
-__global__ void bn_stats_from_sums_kernel(const double* __restrict__ sums, double Mtot, int C, const float* __restrict__ gamma,
-                                          const float* __restrict__ beta, float eps, float* __restrict__ stat,
-                                          float* __restrict__ mean_out, float* __restrict__ invstd_out) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const double mean = sums[c] / Mtot;
-    double var = sums[C + c] / Mtot - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float scale = gamma[c] * invstd;
-    stat[c] = (float)mean; stat[C + c] = invstd; stat[2 * C + c] = scale; stat[3 * C + c] = beta[c] - (float)mean * scale;
-    mean_out[c] = (float)mean; invstd_out[c] = invstd;
-}
-
-__global__ void bn_stat2_from_sums_kernel(const double* __restrict__ sums, double Mtot, int C, float* __restrict__ stat2) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    stat2[c] = (float)(sums[c] / Mtot); stat2[C + c] = (float)(sums[C + c] / Mtot);
-}
-
-static int bn_sync_check(const char* who, int M, int C, size_t ws_bytes, const void* sums) {
+static int bn_sync_check(const char* who, int M, int C, size_t ws_bytes, const void* sums, long long M_total) {
     if (M <= 0 || C <= 0 || (C & 3)) return cgs_set_error(CGS_EINVAL, "%s: M=%d C=%d (C must be a multiple of 4)", who, M, C);
     if (ws_bytes < cgs_bn_ws_bytes(M, C)) return cgs_set_error(CGS_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, cgs_bn_ws_bytes(M, C));
     if (!sums || ((uintptr_t)sums & 7)) return cgs_set_error(CGS_EINVAL, "%s: sums must be an 8-byte aligned [2][C] double buffer", who);
+    if (M_total < M) return cgs_set_error(CGS_EINVAL, "%s: M_total %lld < local M %d", who, M_total, M);
     return CGS_OK;
 }
 
 int cgs_bn_sync_fwd_sums(const float* x, double* sums, int M, int C, void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = bn_sync_check("bn sync fwd sums", M, C, ws_bytes, sums)) return rc;
+    if (int rc = bn_sync_check("bn sync fwd sums", M, C, ws_bytes, sums, M)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const BnGeom g = bn_geom(M, C);
-    float* part = (float*)ws;
-    hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(g.G), dim3(256), 0, s, x, nullptr, nullptr, nullptr, nullptr, nullptr, 1.f, part, M, C, g.rows_per_block);
-    hipLaunchKernelGGL(bn_sums_kernel, dim3(cgs_ceil_div(C, 16)), dim3(256), 0, s, part, g.G, C, sums);
-    CGS_CHECK_LAUNCH("bn_sync_fwd_sums");
-    return CGS_OK;
+    launch_partial(x, nullptr, nullptr, nullptr, nullptr, nullptr, 1.f, (float*)ws, 1, M, C, g, s);
+    hipLaunchKernelGGL(bn_sums_kernel, dim3(cgs_ceil_div(C, 16)), dim3(256), 0, s, (const float*)ws, g.G, C, sums);
+    return norm_launched("bn_sync_fwd_sums");
 }
 
 int cgs_bn_sync_fwd_apply(const float* x, const float* gamma, const float* beta, float eps, float leak, const double* sums,
                           long long M_total, float* y, float* mean, float* invstd, int M, int C, void* ws, size_t ws_bytes,
                           void* stream) {
-    if (int rc = bn_sync_check("bn sync fwd apply", M, C, ws_bytes, sums)) return rc;
-    if (M_total < M) return cgs_set_error(CGS_EINVAL, "bn sync fwd apply: M_total %lld < local M %d", M_total, M);
+    if (int rc = bn_sync_check("bn sync fwd apply", M, C, ws_bytes, sums, M_total)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    float* stat = (float*)ws + (size_t)BN_MAX_BLOCKS * 2 * C;
-    hipLaunchKernelGGL(bn_stats_from_sums_kernel, dim3(cgs_ceil_div(C, 128)), dim3(128), 0, s, sums, (double)M_total, C, gamma, beta, eps, stat, mean, invstd);
-    const size_t n4 = (size_t)M * C / 4;
-    hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, x, stat, leak, y, n4, C, n4);
-    CGS_CHECK_LAUNCH("bn_sync_fwd_apply");
-    return CGS_OK;
+    float* stat = bn_ws(ws, C).stat;
+    hipLaunchKernelGGL(bn_finalize_slices_kernel, dim3(cgs_ceil_div(C, 128)), dim3(128), 0, s, sums, 1, (double)M_total, C, gamma, beta, eps, stat, mean, invstd);
+    launch_apply_fwd(x, stat, leak, y, 1, M, C, s);
+    return norm_launched("bn_sync_fwd_apply");
 }
 
 int cgs_bn_sync_bwd_sums(const float* dy, const float* x, const float* gamma, const float* beta, const float* mean,
                          const float* invstd, float leak, double* sums, int M, int C, void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = bn_sync_check("bn sync bwd sums", M, C, ws_bytes, sums)) return rc;
+    if (int rc = bn_sync_check("bn sync bwd sums", M, C, ws_bytes, sums, M)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const BnGeom g = bn_geom(M, C);
-    float* part = (float*)ws;
-    hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(g.G), dim3(256), 0, s, x, dy, mean, invstd, gamma, beta, leak, part, M, C, g.rows_per_block);
-    hipLaunchKernelGGL(bn_sums_kernel, dim3(cgs_ceil_div(C, 16)), dim3(256), 0, s, part, g.G, C, sums);
-    CGS_CHECK_LAUNCH("bn_sync_bwd_sums");
-    return CGS_OK;
+    launch_partial(x, dy, mean, invstd, gamma, beta, leak, (float*)ws, 1, M, C, g, s);
+    hipLaunchKernelGGL(bn_sums_kernel, dim3(cgs_ceil_div(C, 16)), dim3(256), 0, s, (const float*)ws, g.G, C, sums);
+    return norm_launched("bn_sync_bwd_sums");
 }
 
 int cgs_bn_sync_bwd_apply(const float* dy, const float* x, const float* gamma, const float* beta, const float* mean,
                           const float* invstd, float leak, const double* sums, long long M_total, float* dx, int M, int C,
                           void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = bn_sync_check("bn sync bwd apply", M, C, ws_bytes, sums)) return rc;
-    if (M_total < M) return cgs_set_error(CGS_EINVAL, "bn sync bwd apply: M_total %lld < local M %d", M_total, M);
+    if (int rc = bn_sync_check("bn sync bwd apply", M, C, ws_bytes, sums, M_total)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    float* stat = (float*)ws + (size_t)BN_MAX_BLOCKS * 2 * C;
-    float* stat2 = stat + 4 * (size_t)C;
-    hipLaunchKernelGGL(bn_stat2_from_sums_kernel, dim3(cgs_ceil_div(C, 128)), dim3(128), 0, s, sums, (double)M_total, C, stat2);
-    const size_t n4 = (size_t)M * C / 4;
-    hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, dy, x, mean, invstd, gamma, beta, stat2, leak, dx, n4, C, n4);
-    CGS_CHECK_LAUNCH("bn_sync_bwd_apply");
-    return CGS_OK;
+    float* stat2 = bn_ws(ws, C).stat2;
+    hipLaunchKernelGGL(bn_finalize2_slices_kernel, dim3(cgs_ceil_div(C, 128)), dim3(128), 0, s, sums, 1, (double)M_total, C, stat2);
+    launch_apply_bwd(dy, x, mean, invstd, gamma, beta, stat2, leak, dx, 1, M, C, s);
+    return norm_launched("bn_sync_bwd_apply");
 }
 
 
@@ -725,10 +721,9 @@ int cgs_bias_grad(const float* dy, float* db, int M, int C, int accumulate, void
     if (ws_bytes < cgs_bn_ws_bytes(M, C)) return cgs_set_error(CGS_EWORKSPACE, "bias_grad: workspace %zu < %zu", ws_bytes, cgs_bn_ws_bytes(M, C));
     hipStream_t s = (hipStream_t)stream;
     const BnGeom g = bn_geom(M, C);
-    hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(g.G), dim3(256), 0, s, dy, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, (float*)ws, M, C, g.rows_per_block);
+    launch_partial(dy, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, (float*)ws, 1, M, C, g, s);
     hipLaunchKernelGGL(colsum_finalize_kernel, dim3(cgs_ceil_div(C, BNF_CH)), dim3(256), 0, s, (const float*)ws, g.G, C, db, accumulate);
-    CGS_CHECK_LAUNCH("bias_grad");
-    return CGS_OK;
+    return norm_launched("bias_grad");
 }
 
 
@@ -749,39 +744,36 @@ static BnGeom in_geom(int B, int HW) {
     return g;
 }
 
-size_t cgs_instnorm_ws_bytes(int B, int HW, int C) {
-    if (B <= 0 || HW <= 0 || C <= 0) return 0;
-    const BnGeom g = in_geom(B, HW);
-    return ((size_t)B * g.G * 2 * C + (size_t)B * 6 * C) * sizeof(float);   // partials | stat[B][4][C] | stat2[B][2][C]
-}
-
 // floats in front of stat2[B][2][C] in that workspace: where cgs_instnorm_lrelu_bwd_data leaves {mean(d), mean(d * xhat)} of every
 // sample (on both of its paths) and cgs_instnorm_param_grads (wgrad_dot.hip) reads them
 size_t cgs_instnorm_stat2_offset(int B, int HW, int C) {
     return (size_t)B * in_geom(B, HW).G * 2 * C + (size_t)B * 4 * C;
 }
 
+size_t cgs_instnorm_ws_bytes(int B, int HW, int C) {
+    if (B <= 0 || HW <= 0 || C <= 0) return 0;
+    return (cgs_instnorm_stat2_offset(B, HW, C) + (size_t)B * 2 * C) * sizeof(float);
+}
+
+static int instnorm_check(const char* who, int B, int HW, int C, size_t ws_bytes) {
+    if (B <= 0 || HW <= 0 || C <= 0 || (C & 3) || B > 65535) return cgs_set_error(CGS_EINVAL, "%s: B=%d HW=%d C=%d", who, B, HW, C);
+    if (ws_bytes < cgs_instnorm_ws_bytes(B, HW, C)) return cgs_set_error(CGS_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, cgs_instnorm_ws_bytes(B, HW, C));
+    return CGS_OK;
+}
+
 int cgs_instnorm_lrelu_fwd(const float* x, const float* scale, const float* offset, float eps, float leak, float* y,
                            float* mean, float* invstd, int B, int HW, int C, void* ws, size_t ws_bytes, void* stream) {
-    if (B <= 0 || HW <= 0 || C <= 0 || (C & 3) || B > 65535) return cgs_set_error(CGS_EINVAL, "instnorm fwd: B=%d HW=%d C=%d", B, HW, C);
-    if (ws_bytes < cgs_instnorm_ws_bytes(B, HW, C)) return cgs_set_error(CGS_EWORKSPACE, "instnorm fwd: workspace %zu < %zu", ws_bytes, cgs_instnorm_ws_bytes(B, HW, C));
-    hipStream_t s = (hipStream_t)stream;
-    if (norm_small_ok(HW)) {              // small groups: one launch (see norm_small_kernel)
-        hipLaunchKernelGGL(norm_small_kernel<false>, dim3(cgs_ceil_div(C, 64), B), dim3(256), 0, s, x, nullptr, scale, offset, eps, leak, y, mean, invstd, nullptr, HW, C);
-        CGS_CHECK_LAUNCH("instnorm_lrelu_fwd");
-        cgs_note_kernel("norm_small_fwd");
-        return CGS_OK;
-    }
-    const BnGeom g = in_geom(B, HW);
-    float* part = (float*)ws;
-    float* stat = part + (size_t)B * g.G * 2 * C;
-    hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(g.G, B), dim3(256), 0, s, x, nullptr, nullptr, nullptr, nullptr, nullptr, leak, part, HW, C, g.rows_per_block);
-    hipLaunchKernelGGL(bn_finalize_kernel<0>, dim3(cgs_ceil_div(C, BNF_CH), B), dim3(256), 0, s, part, g.G, HW, C, scale, offset, eps, stat, mean, invstd);
-    const size_t n4 = (size_t)B * HW * C / 4, gn4 = (size_t)HW * C / 4;
-    hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, x, stat, leak, y, n4, C, gn4);
-    CGS_CHECK_LAUNCH("instnorm_lrelu_fwd");
-    cgs_note_kernel("norm_passes_fwd");
-    return CGS_OK;
+    if (int rc = instnorm_check("instnorm fwd", B, HW, C, ws_bytes)) return rc;
+    return norm_fwd_from_x("instnorm_lrelu_fwd", x, scale, offset, eps, leak, y, mean, invstd, B, HW, C, in_geom(B, HW),
+                           carve_ws(ws, B, C, cgs_instnorm_stat2_offset(B, HW, C)), (hipStream_t)stream);
+}
+
+int cgs_instnorm_lrelu_bwd_data(const float* dy, const float* x, const float* scale, const float* offset, const float* mean,
+                                const float* invstd, float leak, float* dx, int B, int HW, int C, void* ws, size_t ws_bytes,
+                                void* stream) {
+    if (int rc = instnorm_check("instnorm bwd", B, HW, C, ws_bytes)) return rc;
+    return norm_bwd_from_x("instnorm_lrelu_bwd_data", dy, x, scale, offset, mean, invstd, leak, dx, B, HW, C, in_geom(B, HW),
+                           carve_ws(ws, B, C, cgs_instnorm_stat2_offset(B, HW, C)), (hipStream_t)stream);
 }
 
 // Norm over GROUPS of rows whose statistics the producing convolution left as partial rows (cgs_conv_stat_layout): instance norm
@@ -794,22 +786,8 @@ int cgs_groupnorm_lrelu_fwd_from_partials(const float* x, const float* part, int
         return cgs_set_error(CGS_EINVAL, "groupnorm fwd from partials: groups=%d M=%d C=%d rows=%d x %d", groups, M_group, C, rows_per_seg, nseg);
     if (ws_bytes < (size_t)groups * 4 * C * sizeof(float))
         return cgs_set_error(CGS_EWORKSPACE, "groupnorm fwd from partials: workspace %zu < %zu", ws_bytes, (size_t)groups * 4 * C * sizeof(float));
-    hipStream_t s = (hipStream_t)stream;
-    if (const int rpb = norm_fa_rows_per_block(groups, rows_per_seg, nseg, M_group, C)) {
-        hipLaunchKernelGGL(norm_fa_kernel<false>, dim3(cgs_ceil_div(C, 64), cgs_ceil_div(M_group, rpb), groups), dim3(256), 0, s, x, nullptr, part, rows_per_seg, nseg,
-                           seg_stride, gamma, beta, eps, leak, y, mean, invstd, M_group, C, rpb);
-        CGS_CHECK_LAUNCH("groupnorm_lrelu_fwd_from_partials");
-        cgs_note_kernel("norm_fa_fwd");
-        return CGS_OK;
-    }
-    float* stat = (float*)ws;                                          // [groups][4][C]
-    hipLaunchKernelGGL(bn_finalize_kernel<0>, dim3(cgs_ceil_div(C, BNF_CH), groups), dim3(256), 0, s, part, rows_per_seg, M_group, C, gamma, beta, eps, stat,
-                       mean, invstd, nseg, seg_stride);
-    const size_t n4 = (size_t)groups * M_group * C / 4, gn4 = (size_t)M_group * C / 4;
-    hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, x, stat, leak, y, n4, C, gn4);
-    CGS_CHECK_LAUNCH("groupnorm_lrelu_fwd_from_partials");
-    cgs_note_kernel("norm_finalize_fwd");
-    return CGS_OK;
+    return norm_fwd_from_partials("groupnorm_lrelu_fwd_from_partials", x, part, groups, rows_per_seg, nseg, seg_stride, gamma, beta, eps, leak, y, mean, invstd,
+                                  M_group, C, (float*)ws /* stat[groups][4][C] */, nullptr, (hipStream_t)stream);
 }
 
 // Backward-data of a norm (+ lrelu) over groups of rows whose two column sums the PRODUCING backward-data launch left as partial rows
@@ -819,6 +797,7 @@ int cgs_groupnorm_lrelu_fwd_from_partials(const float* x, const float* part, int
 int cgs_norm_lrelu_bwd_from_partials(const float* dy, const float* x, const float* part, int groups, int rows_per_seg, int nseg, int seg_stride,
                                      const float* gamma, const float* beta, const float* mean, const float* invstd, float leak, float* dx,
                                      int M_group, int C, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "norm_lrelu_bwd_from_partials";
     if (groups <= 0 || groups > 65535 || M_group <= 0 || C <= 0 || (C & 3) || rows_per_seg <= 0 || nseg <= 0 || seg_stride < 0 || !part || !dy || !x || !dx)
         return cgs_set_error(CGS_EINVAL, "norm bwd from partials: groups=%d M=%d C=%d rows=%d x %d", groups, M_group, C, rows_per_seg, nseg);
     const bool sliced = groups == 1 && nseg == 1 && rows_per_seg >= 1024 && !((uintptr_t)ws & 7);
@@ -828,48 +807,18 @@ int cgs_norm_lrelu_bwd_from_partials(const float* dy, const float* x, const floa
     if (const int rpb = norm_fa_rows_per_block(groups, rows_per_seg, nseg, M_group, C)) {
         hipLaunchKernelGGL(norm_fa_kernel<true>, dim3(cgs_ceil_div(C, 64), cgs_ceil_div(M_group, rpb), groups), dim3(256), 0, s, x, dy, part, rows_per_seg, nseg,
                            seg_stride, gamma, beta, 0.f, leak, dx, (float*)mean, (float*)invstd, M_group, C, rpb);
-        CGS_CHECK_LAUNCH("norm_lrelu_bwd_from_partials");
-        cgs_note_kernel("norm_fa_bwd");
-        return CGS_OK;
+        return norm_launched(who, "norm_fa_bwd");
     }
-    float* stat2;
+    float* stat2 = (float*)ws;                                                    // [groups][2][C]
     if (sliced) {
         double* slices = (double*)ws;
         stat2 = (float*)(slices + (size_t)BNF_SLICES * 2 * C);
         hipLaunchKernelGGL(bn_slice_sums_kernel, dim3(cgs_ceil_div(C, BNF_CH), BNF_SLICES), dim3(256), 0, s, part, rows_per_seg, C, slices);
-        hipLaunchKernelGGL(bn_finalize2_slices_kernel, dim3(cgs_ceil_div(C, 64)), dim3(64), 0, s, slices, M_group, C, stat2);
+        hipLaunchKernelGGL(bn_finalize2_slices_kernel, dim3(cgs_ceil_div(C, 64)), dim3(64), 0, s, slices, BNF_SLICES, (double)M_group, C, stat2);
     } else {
-        stat2 = (float*)ws;                                                   // [groups][2][C]
         hipLaunchKernelGGL(bn_finalize_kernel<1>, dim3(cgs_ceil_div(C, BNF_CH), groups), dim3(256), 0, s, part, rows_per_seg, M_group, C, nullptr, nullptr, 0.f,
                            stat2, nullptr, nullptr, nseg, seg_stride);
     }
-    const size_t n4 = (size_t)groups * M_group * C / 4, gn4 = (size_t)M_group * C / 4;
-    hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, dy, x, mean, invstd, gamma, beta, stat2, leak, dx, n4, C, gn4);
-    CGS_CHECK_LAUNCH("norm_lrelu_bwd_from_partials");
-    cgs_note_kernel(sliced ? "norm_sliced_bwd" : "norm_finalize_bwd");
-    return CGS_OK;
-}
-
-int cgs_instnorm_lrelu_bwd_data(const float* dy, const float* x, const float* scale, const float* offset, const float* mean,
-                                const float* invstd, float leak, float* dx, int B, int HW, int C, void* ws, size_t ws_bytes,
-                                void* stream) {
-    if (B <= 0 || HW <= 0 || C <= 0 || (C & 3) || B > 65535) return cgs_set_error(CGS_EINVAL, "instnorm bwd: B=%d HW=%d C=%d", B, HW, C);
-    if (ws_bytes < cgs_instnorm_ws_bytes(B, HW, C)) return cgs_set_error(CGS_EWORKSPACE, "instnorm bwd: workspace %zu < %zu", ws_bytes, cgs_instnorm_ws_bytes(B, HW, C));
-    hipStream_t s = (hipStream_t)stream;
-    const BnGeom g = in_geom(B, HW);
-    float* part = (float*)ws;
-    float* stat2 = part + cgs_instnorm_stat2_offset(B, HW, C);
-    if (norm_small_ok(HW)) {
-        hipLaunchKernelGGL(norm_small_kernel<true>, dim3(cgs_ceil_div(C, 64), B), dim3(256), 0, s, x, dy, scale, offset, 0.f, leak, dx, (float*)mean, (float*)invstd, stat2, HW, C);
-        CGS_CHECK_LAUNCH("instnorm_lrelu_bwd_data");
-        cgs_note_kernel("norm_small_bwd");
-        return CGS_OK;
-    }
-    hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(g.G, B), dim3(256), 0, s, x, dy, mean, invstd, scale, offset, leak, part, HW, C, g.rows_per_block);
-    hipLaunchKernelGGL(bn_finalize_kernel<1>, dim3(cgs_ceil_div(C, BNF_CH), B), dim3(256), 0, s, part, g.G, HW, C, nullptr, nullptr, 0.f, stat2, nullptr, nullptr);
-    const size_t n4 = (size_t)B * HW * C / 4, gn4 = (size_t)HW * C / 4;
-    hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, dy, x, mean, invstd, scale, offset, stat2, leak, dx, n4, C, gn4);
-    CGS_CHECK_LAUNCH("instnorm_lrelu_bwd_data");
-    cgs_note_kernel("norm_passes_bwd");
-    return CGS_OK;
+    launch_apply_bwd(dy, x, mean, invstd, gamma, beta, stat2, leak, dx, groups, M_group, C, s);
+    return norm_launched(who, sliced ? "norm_sliced_bwd" : "norm_finalize_bwd");
 }

@@ -43,6 +43,7 @@ struct CgsLayer {
 };
 
 #define CGS_BN_MAX_BLOCKS 512   // stage-1 partial blocks of the per-channel reductions (bn.hip workspace layout)
+size_t cgs_bn_stat2_offset(int C);                        // floats in front of stat2[2][C] in a batch norm's workspace (bn.hip)
 size_t cgs_instnorm_stat2_offset(int B, int HW, int C);   // floats in front of stat2[B][2][C] in an instance norm's workspace (bn.hip)
 #define CGS_BK 32           // K-tile of the implicit GEMM
 #define CGS_MAX_CLASSES 4   // stride <= 2 for the T direction
@@ -159,6 +160,29 @@ __device__ __forceinline__ float epilogue_apply(float v, int mode, float a, floa
         case CGS_EPI_TANH_BWD: return v * (1.f - aux * aux);
         default: return v;
     }
+}
+
+// The element arithmetic of norm + lrelu (bn.hip; the norm-backward statistics of igemm_epilogue.h), each formula once:
+//   y  = lrelu(fma(x, scale, shift))                     scale = gamma * invstd, shift = beta - mean * scale
+//   d  = dy * lrelu'(fma(x, scale, shift)),              xhat = (x - mean) * invstd
+//   dx = scale * (d - m1 - xhat * m2)                    m1 = mean(d), m2 = mean(d * xhat)
+__device__ __forceinline__ float norm_fwd1(float x, float sc, float sh, float leak) {
+    const float o = fmaf(x, sc, sh);
+    return o > 0.f ? o : leak * o;
+}
+__device__ __forceinline__ float norm_d1(float x, float dy, float sc, float sh, float leak) {
+    const float u = fmaf(x, sc, sh);
+    return dy * (u > 0.f ? 1.f : leak);
+}
+// ... d with the two column sums it feeds: sa += d, sb += d * xhat
+__device__ __forceinline__ float norm_d_acc1(float x, float dy, float mu, float inv, float sc, float sh, float leak, float& sa, float& sb) {
+    const float d = norm_d1(x, dy, sc, sh, leak);
+    sa += d; sb = fmaf(d, (x - mu) * inv, sb);
+    return d;
+}
+__device__ __forceinline__ float norm_dx1(float x, float d, float mu, float inv, float sc, float m1, float m2) {
+    const float xh = (x - mu) * inv;
+    return sc * (d - m1 - xh * m2);
 }
 #endif
 

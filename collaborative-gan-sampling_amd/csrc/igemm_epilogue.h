@@ -52,6 +52,14 @@ __device__ __forceinline__ NsLane ns_lane_params(const IgemmParams& p, int group
     return L;
 }
 
+// channel e of a lane's norm-backward sums: sa[e] += d, sb[e] += d * xhat (norm_d_acc1, cgs_internal.h: the arithmetic of bn.hip's backward sums;
+// through locals, because an element of a vector cannot be bound to a reference)
+__device__ __forceinline__ void ns_acc(const NsLane& L, float x, float dy, int e, f32x4& sa, f32x4& sb) {
+    float a = sa[e], b = sb[e];
+    norm_d_acc1(x, dy, L.mu[e], L.inv[e], L.sc[e], L.sh[e], L.leak, a, b);
+    sa[e] = a; sb[e] = b;
+}
+
 // ST: 0 = no statistics; 1 = fused norm statistics of the stored values (sum, sum of squares); 2 = norm-BACKWARD statistics: the stored
 // value y is a gradient w.r.t. the output of norm + lrelu over x = ep_aux (same shape): sums of d = y * lrelu'(sc * x + sh) and d * xhat.
 template <int EPI, int ROWS, int RPP, int LDE, int ST = 0, int NSU = 1>
@@ -85,11 +93,7 @@ __device__ __forceinline__ void epilogue_rows(const IgemmParams& p, const float*
                 for (int e = 0; e < 4; ++e) y[e] = v[e] + bias[e];
                 *(f32x4*)(p.out + (size_t)pixs[u] * p.N + n) = y;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {          // the arithmetic of bn_partial_kernel<1>, element by element
-                    const float uu = fmaf(xs[u][e], ns->sc[e], ns->sh[e]);
-                    const float d = y[e] * (uu > 0.f ? 1.f : ns->leak);
-                    (*sa)[e] += d; (*sb)[e] = fmaf(d, (xs[u][e] - ns->mu[e]) * ns->inv[e], (*sb)[e]);
-                }
+                for (int e = 0; e < 4; ++e) ns_acc(*ns, xs[u][e], y[e], e, *sa, *sb);
             }
         }
         return;
@@ -111,13 +115,9 @@ __device__ __forceinline__ void epilogue_rows(const IgemmParams& p, const float*
 #pragma unroll
             for (int e = 0; e < 4; ++e) { (*sa)[e] += y[e]; (*sb)[e] = fmaf(y[e], y[e], (*sb)[e]); }
         }
-        if (ST == 2) {   // (NSU == 1: row by row) the arithmetic of bn_partial_kernel<1>, element by element
+        if (ST == 2) {   // (NSU == 1: row by row)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float u = fmaf(aux[e], ns->sc[e], ns->sh[e]);
-                const float d = y[e] * (u > 0.f ? 1.f : ns->leak);
-                (*sa)[e] += d; (*sb)[e] = fmaf(d, (aux[e] - ns->mu[e]) * ns->inv[e], (*sb)[e]);
-            }
+            for (int e = 0; e < 4; ++e) ns_acc(*ns, aux[e], y[e], e, *sa, *sb);
         }
     }
 }

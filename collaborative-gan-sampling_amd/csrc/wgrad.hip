@@ -374,8 +374,7 @@ int cgs_bn_moving_update(const float* mean, const float* invstd, float* moving_m
 
 int cgs_bn_train_param_grads(const void* bwd_ws, int M, int C, float* dgamma, float* dbeta, int accumulate, void* stream) {
     if (M <= 0 || C <= 0 || !bwd_ws) return cgs_set_error(CGS_EINVAL, "bn_train_param_grads: bad argument");
-    // workspace layout of bn.hip: partials [CGS_BN_MAX_BLOCKS][2][C] | stat [4][C] | stat2 [2][C] = {mean(dy'), mean(dy'*xhat)}
-    const float* stat2 = (const float*)bwd_ws + (size_t)CGS_BN_MAX_BLOCKS * 2 * C + 4 * (size_t)C;
+    const float* stat2 = (const float*)bwd_ws + cgs_bn_stat2_offset(C);          // [2][C] = {mean(dy'), mean(dy'*xhat)}
     hipLaunchKernelGGL(bn_param_grad_kernel, dim3(cgs_ceil_div(C, 128)), dim3(128), 0, (hipStream_t)stream, stat2, (float)M, dgamma, dbeta, C, accumulate);
     CGS_CHECK_LAUNCH("bn_train_param_grads");
     return CGS_OK;

@@ -54,6 +54,31 @@ def test_split_sums_equal_whole_batch(M, C, leak):
     assert (got - dx).abs().max().item() <= 2e-5 * dx.abs().max().item()
 
 
+@pytest.mark.parametrize("M,C", [(129, 4), (129, 40)])
+def test_one_rank_equals_the_unsynchronised_norm(M, C):
+    """One rank: the second halves finish the statistics from ONE slice of sums (bn_finalize_slices_kernel /
+    bn_finalize2_slices_kernel with nslices = 1) and must give what bn_train_lrelu_fwd / _bwd_data give, within the bars above.
+    129 rows: the smallest M past the one-launch small path; C = 40: one tail channel group."""
+    from cgs_amd import kernels as K
+    d, leak = dev(), 0.2
+    x, dy = (rnd((M, C), 1) * 1.7 + 0.3).to(d), rnd((M, C), 2).to(d)
+    gamma, beta = (rnd((C,), 3).abs() + 0.5).to(d), rnd((C,), 4, 0.3).to(d)
+    y, mean, invstd = K.bn_train_lrelu_fwd(x, gamma, beta, leak)
+    dx = K.bn_train_lrelu_bwd_data(dy.clone(), x, gamma, beta, mean, invstd, leak)
+
+    def run():
+        sums = K.bn_sync_fwd_sums(x, torch.empty((2, C), dtype=torch.float64, device=d))
+        ys, m, iv = K.bn_sync_fwd_apply(x, gamma, beta, sums, M, leak)
+        bsums = K.bn_sync_bwd_sums(dy, x, gamma, beta, m, iv, torch.empty((2, C), dtype=torch.float64, device=d), leak)
+        return ys, m, iv, K.bn_sync_bwd_apply(dy.clone(), x, gamma, beta, m, iv, bsums, M, leak)
+
+    ys, m, iv, dxs = run()
+    assert torch.allclose(m, mean, rtol=0, atol=1e-6) and torch.allclose(iv, invstd, rtol=1e-6, atol=0)
+    assert torch.allclose(ys, y, rtol=1e-5, atol=1e-5)
+    assert (dxs - dx).abs().max().item() <= 2e-5 * dx.abs().max().item()
+    assert all(torch.equal(a, b) for a, b in zip((ys, m, iv, dxs), run()))          # bit-equal over two runs
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
