@@ -28,7 +28,7 @@ int cgs_set_error(int code, const char* fmt, ...) {
 
 extern "C" {
 
-int cgs_version(void) { return 111; }
+int cgs_version(void) { return 112; }
 const char* cgs_last_error(void) { return g_err; }
 const char* cgs_last_kernel(void) { return g_last_kernel; }
 double cgs_last_executed_flops(void) { return g_last_flops; }
@@ -481,9 +481,12 @@ __global__ __launch_bounds__(256) void linear_out1_fwd_kernel(const float* __res
 }
 
 // the logit head and the loss seed in one launch (the last launches of every D forward of the refinement loop, both a few microseconds of
-// latency): y[b] = x[b] . w + bias; dl[b] = sigmoid(y[b]) - 1 (d softplus(-y) / dy, the stable form of bce_rowmean_kernel); lm[b] = y[b]
-__global__ __launch_bounds__(256) void linear_out1_bce_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                              float* __restrict__ y, float* __restrict__ dl, float* __restrict__ lm, int B, int K) {
+// latency): y[b] = x[b] . w + bias; dl[b] = d loss(KIND) / dy (BCE: sigmoid(y[b]) - 1, the stable form of the seed kernels); lm[b] = y[b];
+// with LADAM the sample's ladam state from sigmoid(y[b]) (cgs_refine_loss_seed at P = 1)
+template <int KIND, bool LADAM>
+__device__ __forceinline__ void linear_out1_seed_body(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                      float* __restrict__ y, float* __restrict__ dl, float* __restrict__ lm, int B, int K,
+                                                      const cgs_ladam_seed& la) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (b >= B) return;
@@ -502,9 +505,22 @@ __global__ __launch_bounds__(256) void linear_out1_bce_kernel(const float* __res
     if (lane == 0) {
         const float v = s + (bias ? bias[0] : 0.f);
         y[b] = v;
-        dl[b] = v >= 0.f ? -expf(-v) / (1.f + expf(-v)) : -1.f / (1.f + expf(v));
+        dl[b] = loss_seed1<KIND>(v);
         lm[b] = v;
+        if (LADAM) ladam_seed1(la, b, sigmoid_stable(v));
     }
+}
+
+__global__ __launch_bounds__(256) void linear_out1_bce_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                              float* __restrict__ y, float* __restrict__ dl, float* __restrict__ lm, int B, int K) {
+    linear_out1_seed_body<CGS_LOSS_BCE, false>(x, w, bias, y, dl, lm, B, K, cgs_ladam_seed{});
+}
+
+template <int KIND, bool LADAM>
+__global__ __launch_bounds__(256) void linear_out1_seed_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                               float* __restrict__ y, float* __restrict__ dl, float* __restrict__ lm, int B, int K,
+                                                               cgs_ladam_seed la) {
+    linear_out1_seed_body<KIND, LADAM>(x, w, bias, y, dl, lm, B, K, la);
 }
 
 __global__ __launch_bounds__(256) void linear_out1_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ w,
@@ -537,6 +553,24 @@ int cgs_linear_out1_bce(const float* x, const float* w, const float* bias, float
     if (B <= 0 || in <= 0 || !x || !w || !logits || !dlogits || !logit_mean) return cgs_set_error(CGS_EINVAL, "linear_out1_bce: bad argument");
     hipLaunchKernelGGL(linear_out1_bce_kernel, dim3(cgs_ceil_div(B, 4)), dim3(256), 0, (hipStream_t)stream, x, w, bias, logits, dlogits, logit_mean, B, in);
     CGS_CHECK_LAUNCH("linear_out1_bce");
+    return CGS_OK;
+}
+
+int cgs_linear_out1_seed(const float* x, const float* w, const float* bias, float* logits, float* dlogits, float* logit_mean, int B, int in,
+                         int kind, const cgs_ladam_seed* ladam, void* stream) {
+    if (B <= 0 || in <= 0 || !x || !w || !logits || !dlogits || !logit_mean) return cgs_set_error(CGS_EINVAL, "linear_out1_seed: bad argument");
+    if (kind != CGS_LOSS_BCE && kind != CGS_LOSS_LSQ && kind != CGS_LOSS_LINEAR) return cgs_set_error(CGS_EINVAL, "linear_out1_seed: kind %d", kind);
+    if (ladam && (!ladam->s_real || !ladam->loss_avg || !ladam->gain)) return cgs_set_error(CGS_EINVAL, "linear_out1_seed: ladam state with a null pointer");
+    if (kind == CGS_LOSS_BCE && !ladam) return cgs_linear_out1_bce(x, w, bias, logits, dlogits, logit_mean, B, in, stream);
+    const dim3 grid(cgs_ceil_div(B, 4)), block(256);
+    const hipStream_t st = (hipStream_t)stream;
+    const cgs_ladam_seed la = ladam ? *ladam : cgs_ladam_seed{};
+#define OUT1_SEED(KIND, LADAM) hipLaunchKernelGGL((linear_out1_seed_kernel<KIND, LADAM>), grid, block, 0, st, x, w, bias, logits, dlogits, logit_mean, B, in, la)
+    if (kind == CGS_LOSS_BCE) OUT1_SEED(CGS_LOSS_BCE, true);
+    else if (kind == CGS_LOSS_LSQ) { if (ladam) OUT1_SEED(CGS_LOSS_LSQ, true); else OUT1_SEED(CGS_LOSS_LSQ, false); }
+    else { if (ladam) OUT1_SEED(CGS_LOSS_LINEAR, true); else OUT1_SEED(CGS_LOSS_LINEAR, false); }
+#undef OUT1_SEED
+    CGS_CHECK_LAUNCH("linear_out1_seed");
     return CGS_OK;
 }
 

@@ -184,6 +184,25 @@ __device__ __forceinline__ float norm_dx1(float x, float d, float mu, float inv,
     const float xh = (x - mu) * inv;
     return sc * (d - m1 - xh * m2);
 }
+
+// The loss seed of the refinement loop, each formula once (elementwise.hip; the one-logit head of api.hip).
+__device__ __forceinline__ float sigmoid_stable(float v) { return v >= 0.f ? 1.f / (1.f + expf(-v)) : expf(v) / (1.f + expf(v)); }
+//   d loss / d logit of the unreduced loss (cgs_hip.h, CGS_LOSS_*).  BCE: sigmoid(v) - 1 = -1/(1+exp(v)), written to stay accurate for large |v|
+template <int KIND>
+__device__ __forceinline__ float loss_seed1(float v) {
+    if (KIND == CGS_LOSS_BCE) return v >= 0.f ? -expf(-v) / (1.f + expf(-v)) : -1.f / (1.f + expf(v));
+    if (KIND == CGS_LOSS_LSQ) return 2.f * (v - 1.f);
+    return -1.f;
+}
+//   the ladam rule's per-sample state from the sample's score sig = mean_p sigmoid(logit) (cgs_ladam_seed): one thread per sample
+__device__ __forceinline__ void ladam_seed1(const cgs_ladam_seed& la, int b, float sig, const float* loss_in = nullptr) {
+#pragma clang fp contract(off)   // separately rounded mul / add (policy.py:50,56)
+    const float loss = loss_in ? loss_in[b] : la.s_real[0] - sig;
+    const float avg = la.first ? loss : 0.5f * la.loss_avg[b] + 0.5f * loss;
+    la.loss_avg[b] = avg;
+    const float c = fminf(fmaxf(avg + 0.5f, 0.f), 10000.f);
+    la.gain[b] = c * c;
+}
 #endif
 
 

@@ -113,33 +113,56 @@ int cgs_lrelu_bwd(const float* dy, const float* y, float leak, float* out, size_
 int cgs_tanh_fwd(const float* x, float* out, size_t n, void* stream) { UNARY_ENTRY("tanh_fwd", 2, x, nullptr, 0.f) }
 int cgs_tanh_bwd(const float* dy, const float* y, float* out, size_t n, void* stream) { UNARY_ENTRY("tanh_bwd", 3, dy, y, 0.f) }
 
-__global__ void bce_rowmean_kernel(const float* __restrict__ l, float* __restrict__ dl, float* __restrict__ lm, int B, int P) {
+// The loss seed (cgs_refine_loss_seed; KIND = CGS_LOSS_*) of one sample's P logits, with the ladam rule's per-sample state when LADAM:
+// one thread per sample (P < 64) ...
+template <int KIND, bool LADAM>
+__device__ __forceinline__ void seed_row_thread(const float* __restrict__ l, float* __restrict__ dl, float* __restrict__ lm, int B, int P,
+                                                const cgs_ladam_seed& la) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    float s = 0.f;
+    float s = 0.f, sg = 0.f;
     for (int i = 0; i < P; ++i) {
         const float v = l[(size_t)b * P + i];
         s += v;
-        // sigmoid(v) - 1 = -1/(1+exp(v)), written to stay accurate for large |v|
-        dl[(size_t)b * P + i] = v >= 0.f ? -expf(-v) / (1.f + expf(-v)) : -1.f / (1.f + expf(v));
+        if (LADAM) sg += sigmoid_stable(v);
+        dl[(size_t)b * P + i] = loss_seed1<KIND>(v);
     }
     lm[b] = s / (float)P;
+    if (LADAM) ladam_seed1(la, b, P == 1 ? sg : sg / (float)P);     // (the score of sigmoid_rowmean_kernel, bit for bit)
 }
 
-// PatchGAN logit maps (P = hundreds of logits per sample): one wave per sample, lanes stride over the row, fixed shuffle tree
-__global__ __launch_bounds__(256) void bce_rowmean_wave_kernel(const float* __restrict__ l, float* __restrict__ dl, float* __restrict__ lm,
-                                                               int B, int P) {
+// ... or, for PatchGAN logit maps (P = hundreds of logits per sample), one wave per sample: lanes stride over the row, fixed shuffle tree
+template <int KIND, bool LADAM>
+__device__ __forceinline__ void seed_row_wave(const float* __restrict__ l, float* __restrict__ dl, float* __restrict__ lm, int B, int P,
+                                              const cgs_ladam_seed& la) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= B) return;
-    float s = 0.f;
+    float s = 0.f, sg = 0.f;
     for (int i = lane; i < P; i += 64) {
         const float v = l[(size_t)b * P + i];
         s += v;
-        dl[(size_t)b * P + i] = v >= 0.f ? -expf(-v) / (1.f + expf(-v)) : -1.f / (1.f + expf(v));
+        if (LADAM) sg += sigmoid_stable(v);
+        dl[(size_t)b * P + i] = loss_seed1<KIND>(v);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) lm[b] = s / (float)P;
+    if (LADAM) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sg += __shfl_xor(sg, o);
+    }
+    if (lane == 0) {
+        lm[b] = s / (float)P;
+        if (LADAM) ladam_seed1(la, b, sg / (float)P);               // (sigmoid_rowmean_wave_kernel's)
+    }
+}
+
+__global__ void bce_rowmean_kernel(const float* __restrict__ l, float* __restrict__ dl, float* __restrict__ lm, int B, int P) {
+    seed_row_thread<CGS_LOSS_BCE, false>(l, dl, lm, B, P, cgs_ladam_seed{});
+}
+
+__global__ __launch_bounds__(256) void bce_rowmean_wave_kernel(const float* __restrict__ l, float* __restrict__ dl, float* __restrict__ lm,
+                                                               int B, int P) {
+    seed_row_wave<CGS_LOSS_BCE, false>(l, dl, lm, B, P, cgs_ladam_seed{});
 }
 
 int cgs_bce_ones_grad_rowmean(const float* logits, float* dlogits, float* logit_mean, int B, int P, void* stream) {
@@ -152,10 +175,44 @@ int cgs_bce_ones_grad_rowmean(const float* logits, float* dlogits, float* logit_
     return CGS_OK;
 }
 
+template <int KIND, bool LADAM>
+__global__ void loss_seed_kernel(const float* __restrict__ l, float* __restrict__ dl, float* __restrict__ lm, int B, int P, cgs_ladam_seed la) {
+    seed_row_thread<KIND, LADAM>(l, dl, lm, B, P, la);
+}
+
+template <int KIND, bool LADAM>
+__global__ __launch_bounds__(256) void loss_seed_wave_kernel(const float* __restrict__ l, float* __restrict__ dl, float* __restrict__ lm,
+                                                             int B, int P, cgs_ladam_seed la) {
+    seed_row_wave<KIND, LADAM>(l, dl, lm, B, P, la);
+}
+
+template <int KIND, bool LADAM>
+static void loss_seed_launch(const float* logits, float* dlogits, float* logit_mean, int B, int P, const cgs_ladam_seed& la, hipStream_t st) {
+    if (P >= 64)
+        hipLaunchKernelGGL((loss_seed_wave_kernel<KIND, LADAM>), dim3(cgs_ceil_div(B, 4)), dim3(256), 0, st, logits, dlogits, logit_mean, B, P, la);
+    else
+        hipLaunchKernelGGL((loss_seed_kernel<KIND, LADAM>), dim3(cgs_ceil_div(B, 128)), dim3(128), 0, st, logits, dlogits, logit_mean, B, P, la);
+}
+
+int cgs_refine_loss_seed(const float* logits, int kind, float* dlogits, float* logit_mean, int B, int P, const cgs_ladam_seed* ladam,
+                         void* stream) {
+    if (B <= 0 || P <= 0 || !logits || !dlogits || !logit_mean) return cgs_set_error(CGS_EINVAL, "refine_loss_seed: B=%d P=%d or a null pointer", B, P);
+    if (kind != CGS_LOSS_BCE && kind != CGS_LOSS_LSQ && kind != CGS_LOSS_LINEAR) return cgs_set_error(CGS_EINVAL, "refine_loss_seed: kind %d", kind);
+    if (ladam && (!ladam->s_real || !ladam->loss_avg || !ladam->gain)) return cgs_set_error(CGS_EINVAL, "refine_loss_seed: ladam state with a null pointer");
+    if (kind == CGS_LOSS_BCE && !ladam) return cgs_bce_ones_grad_rowmean(logits, dlogits, logit_mean, B, P, stream);
+    const hipStream_t st = (hipStream_t)stream;
+    const cgs_ladam_seed la = ladam ? *ladam : cgs_ladam_seed{};
+    if (kind == CGS_LOSS_BCE) loss_seed_launch<CGS_LOSS_BCE, true>(logits, dlogits, logit_mean, B, P, la, st);
+    else if (kind == CGS_LOSS_LSQ) ladam ? loss_seed_launch<CGS_LOSS_LSQ, true>(logits, dlogits, logit_mean, B, P, la, st)
+                                         : loss_seed_launch<CGS_LOSS_LSQ, false>(logits, dlogits, logit_mean, B, P, la, st);
+    else ladam ? loss_seed_launch<CGS_LOSS_LINEAR, true>(logits, dlogits, logit_mean, B, P, la, st)
+               : loss_seed_launch<CGS_LOSS_LINEAR, false>(logits, dlogits, logit_mean, B, P, la, st);
+    CGS_CHECK_LAUNCH("refine_loss_seed");
+    return CGS_OK;
+}
+
 // sig[b] = mean_p sigmoid(l[b, p]): fake_sigmoids = tf.nn.sigmoid(fake_logits) (nsgan/GAN.py:154-155; P = 1 there), the score the
 // accept / reject step reads (nsgan/GAN.py:409, sampling/idpsampler.py:18).  One thread per sample (P < 64) or one wave (P >= 64).
-__device__ __forceinline__ float sigmoid_stable(float v) { return v >= 0.f ? 1.f / (1.f + expf(-v)) : expf(v) / (1.f + expf(v)); }
-
 __global__ void sigmoid_rowmean_kernel(const float* __restrict__ l, float* __restrict__ sig, int B, int P) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
@@ -211,6 +268,38 @@ int cgs_bce_ones_bwd(const float* dloss, const float* logits, float* dlogits, si
     return CGS_OK;
 }
 
+// The GAN training losses of cgs_gan_logits_grad, unreduced (the operator API's least_squares_loss / hinge_loss): without dloss the loss
+// per logit, with it dloss * d loss / d logit
+template <int KIND>
+__global__ __launch_bounds__(256) void gan_loss_kernel(const float* __restrict__ l, float target, const float* __restrict__ dloss,
+                                                       float* __restrict__ o, size_t n) {
+#pragma clang fp contract(off)
+    GRID_STRIDE(i, n) {
+        const float v = l[i];
+        float e, d;
+        if (KIND == CGS_LOSS_LSQ) { const float r = v - target; e = r * r; d = 2.f * r; }
+        else if (KIND == CGS_LOSS_HINGE) {
+            const float u = target > 0.5f ? 1.f - v : 1.f + v;
+            e = fmaxf(u, 0.f);
+            d = u > 0.f ? (target > 0.5f ? -1.f : 1.f) : 0.f;
+        } else { e = -v; d = -1.f; }
+        o[i] = dloss ? dloss[i] * d : e;
+    }
+}
+
+int cgs_gan_loss(const float* logits, int kind, float target, const float* dloss, float* out, size_t n, void* stream) {
+    if (n == 0) return CGS_OK;
+    if (!logits || !out) return cgs_set_error(CGS_EINVAL, "gan_loss: null pointer");
+    const hipStream_t st = (hipStream_t)stream;
+    if (kind == CGS_LOSS_LSQ) hipLaunchKernelGGL(gan_loss_kernel<CGS_LOSS_LSQ>, dim3(ew_blocks(n)), dim3(256), 0, st, logits, target, dloss, out, n);
+    else if (kind == CGS_LOSS_HINGE && (target == 0.f || target == 1.f))
+        hipLaunchKernelGGL(gan_loss_kernel<CGS_LOSS_HINGE>, dim3(ew_blocks(n)), dim3(256), 0, st, logits, target, dloss, out, n);
+    else if (kind == CGS_LOSS_LINEAR) hipLaunchKernelGGL(gan_loss_kernel<CGS_LOSS_LINEAR>, dim3(ew_blocks(n)), dim3(256), 0, st, logits, target, dloss, out, n);
+    else return cgs_set_error(CGS_EINVAL, "gan_loss: kind %d target %g", kind, (double)target);
+    CGS_CHECK_LAUNCH("gan_loss");
+    return CGS_OK;
+}
+
 int cgs_clip(const float* x, float vmin, float vmax, float* y, size_t n, void* stream) {
     if (n == 0) return CGS_OK;
     hipLaunchKernelGGL(loss_unary_kernel<2>, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, nullptr, vmin, vmax, y, n);
@@ -238,6 +327,78 @@ int cgs_refine_update(float* theta, float* m, const float* g, float rate, float 
     if (n == 0) return CGS_OK;
     hipLaunchKernelGGL(refine_update_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, theta, m, g, rate, alpha, first, use_clip, vmin, vmax, n);
     CGS_CHECK_LAUNCH("refine_update");
+    return CGS_OK;
+}
+
+// the ladam state from a per-sample loss the caller already has (PolicyAdaptive.apply_gradient(theta, grad, loss) on device tensors)
+__global__ void ladam_gain_kernel(const float* __restrict__ loss, cgs_ladam_seed la, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) ladam_seed1(la, b, 0.f, loss);
+}
+
+int cgs_ladam_gain(const float* loss, float* loss_avg, float* gain, int first, int B, void* stream) {
+    if (B <= 0 || !loss || !loss_avg || !gain) return cgs_set_error(CGS_EINVAL, "ladam_gain: B=%d or a null pointer", B);
+    hipLaunchKernelGGL(ladam_gain_kernel, dim3(cgs_ceil_div(B, 128)), dim3(128), 0, (hipStream_t)stream, loss, cgs_ladam_seed{nullptr, loss_avg, gain, first}, B);
+    CGS_CHECK_LAUNCH("ladam_gain");
+    return CGS_OK;
+}
+
+// The ladam rule on an activation map (policy.py:53-59; the per-sample gain comes from the seed launch of the step, ladam_seed1): one
+// element, every operation rounded on its own in the reference's order.  HBM-bound, 4 reads and 3 writes per element.
+__device__ __forceinline__ void ladam_update1(float& th, float& m, float& v, float g, float gain, float rate, float c1, float c2, int first,
+                                              int use_clip, float vmin, float vmax) {
+#pragma clang fp contract(off)
+    const float sq = g * g;
+    const float mm = first ? g : 0.9f * m + c1 * g;
+    const float vv = first ? sq : 0.5f * v + c2 * sq;
+    m = mm; v = vv;
+    const float dir = rate * mm / (sqrtf(vv) + 1e-8f);
+    float t = th - dir * gain;
+    if (use_clip) t = fminf(fmaxf(t, vmin), vmax);              // collaborator.py:69-70
+    th = t;
+}
+
+// VEC: F % 4 == 0 and 16-byte aligned bases, so a float4 never straddles two samples
+template <bool VEC>
+__global__ __launch_bounds__(256) void refine_update_ladam_kernel(float* __restrict__ theta, float* __restrict__ m, float* __restrict__ v,
+                                                                  const float* __restrict__ g, const float* __restrict__ gain, float rate,
+                                                                  float c1, float c2, int first, int use_clip, float vmin, float vmax,
+                                                                  size_t n, int F) {
+    if (VEC) {
+        float4* t4 = (float4*)theta; float4* m4 = (float4*)m; float4* v4 = (float4*)v;
+        const float4* g4 = (const float4*)g;
+        GRID_STRIDE(i, n >> 2) {
+            const float gn = gain[(i << 2) / (size_t)F];
+            float4 t = t4[i], mm = first ? float4{0.f, 0.f, 0.f, 0.f} : m4[i], vv = first ? float4{0.f, 0.f, 0.f, 0.f} : v4[i];
+            const float4 gg = g4[i];
+            ladam_update1(t.x, mm.x, vv.x, gg.x, gn, rate, c1, c2, first, use_clip, vmin, vmax);
+            ladam_update1(t.y, mm.y, vv.y, gg.y, gn, rate, c1, c2, first, use_clip, vmin, vmax);
+            ladam_update1(t.z, mm.z, vv.z, gg.z, gn, rate, c1, c2, first, use_clip, vmin, vmax);
+            ladam_update1(t.w, mm.w, vv.w, gg.w, gn, rate, c1, c2, first, use_clip, vmin, vmax);
+            t4[i] = t; m4[i] = mm; v4[i] = vv;
+        }
+    } else {
+        GRID_STRIDE(i, n) {
+            float t = theta[i], mm = first ? 0.f : m[i], vv = first ? 0.f : v[i];
+            ladam_update1(t, mm, vv, g[i], gain[i / (size_t)F], rate, c1, c2, first, use_clip, vmin, vmax);
+            theta[i] = t; m[i] = mm; v[i] = vv;
+        }
+    }
+}
+
+int cgs_refine_update_ladam(float* theta, float* m, float* v, const float* g, const float* gain, float rate, int first, int use_clip,
+                            float vmin, float vmax, int B, int F, void* stream) {
+    if (B <= 0 || F <= 0 || !theta || !m || !v || !g || !gain) return cgs_set_error(CGS_EINVAL, "refine_update_ladam: B=%d F=%d or a null pointer", B, F);
+    const size_t n = (size_t)B * F;
+    const float c1 = (float)(1.0 - 0.9), c2 = (float)(1.0 - 0.5);      // policy.py:42,44: the double difference, rounded once
+    const bool vec = (F & 3) == 0 && (((uintptr_t)theta | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(refine_update_ladam_kernel<true>, dim3(ew_blocks(n >> 2)), dim3(256), 0, (hipStream_t)stream, theta, m, v, g, gain, rate, c1, c2,
+                           first, use_clip, vmin, vmax, n, F);
+    else
+        hipLaunchKernelGGL(refine_update_ladam_kernel<false>, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, theta, m, v, g, gain, rate, c1, c2,
+                           first, use_clip, vmin, vmax, n, F);
+    CGS_CHECK_LAUNCH("refine_update_ladam");
     return CGS_OK;
 }
 

@@ -227,6 +227,35 @@ __global__ void bce_grad_kernel(const float* __restrict__ l, float target, float
     if (loss_sum && threadIdx.x == 0) loss_sum[blockIdx.x] = red[0] * scale;
 }
 
+// The other GAN training losses with the same one-block fixed-order sum (cgs_gan_logits_grad): KIND = CGS_LOSS_LSQ, _HINGE, _LINEAR
+template <int KIND>
+__global__ void gan_grad_kernel(const float* __restrict__ l, float target, float scale, float* __restrict__ dl,
+                                float* __restrict__ loss_sum, int n) {
+#pragma clang fp contract(off)
+    __shared__ float red[256];
+    float acc = 0.f;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float v = l[i];
+        float d, e;
+        if (KIND == CGS_LOSS_LSQ) { const float r = v - target; d = 2.f * r; e = r * r; }
+        else if (KIND == CGS_LOSS_HINGE) {
+            // real: relu(1 - v), fake: relu(1 + v)
+            const float u = target > 0.5f ? 1.f - v : 1.f + v;
+            e = fmaxf(u, 0.f);
+            d = u > 0.f ? (target > 0.5f ? -1.f : 1.f) : 0.f;
+        } else { d = -1.f; e = -v; }
+        dl[i] = scale * d;
+        acc += e;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (loss_sum && threadIdx.x == 0) loss_sum[blockIdx.x] = red[0] * scale;
+}
+
 // One element of the Adam update: shared by adam_kernel and adam_multi_kernel, so both round every element the same way.
 __device__ __forceinline__ void adam_update(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                                             float* __restrict__ v, float lr_t, float b1, float b2, float eps, size_t i) {
@@ -339,6 +368,23 @@ int cgs_bce_logits_grad(const float* logits, float target, float scale, float* d
     if (n <= 0) return cgs_set_error(CGS_EINVAL, "bce_logits_grad: n=%d", n);
     hipLaunchKernelGGL(bce_grad_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, scale, dlogits, loss_sum, n);
     CGS_CHECK_LAUNCH("bce_logits_grad");
+    return CGS_OK;
+}
+
+int cgs_gan_logits_grad(const float* logits, int kind, float target, float scale, float* dlogits, float* loss_sum, int n, void* stream) {
+    if (n <= 0 || !logits || !dlogits) return cgs_set_error(CGS_EINVAL, "gan_logits_grad: n=%d or a null pointer", n);
+    const hipStream_t st = (hipStream_t)stream;
+    switch (kind) {
+        case CGS_LOSS_BCE: return cgs_bce_logits_grad(logits, target, scale, dlogits, loss_sum, n, stream);
+        case CGS_LOSS_LSQ: hipLaunchKernelGGL(gan_grad_kernel<CGS_LOSS_LSQ>, dim3(1), dim3(256), 0, st, logits, target, scale, dlogits, loss_sum, n); break;
+        case CGS_LOSS_HINGE:
+            if (target != 0.f && target != 1.f) return cgs_set_error(CGS_EINVAL, "gan_logits_grad: hinge target %g is neither 0 nor 1", (double)target);
+            hipLaunchKernelGGL(gan_grad_kernel<CGS_LOSS_HINGE>, dim3(1), dim3(256), 0, st, logits, target, scale, dlogits, loss_sum, n);
+            break;
+        case CGS_LOSS_LINEAR: hipLaunchKernelGGL(gan_grad_kernel<CGS_LOSS_LINEAR>, dim3(1), dim3(256), 0, st, logits, target, scale, dlogits, loss_sum, n); break;
+        default: return cgs_set_error(CGS_EINVAL, "gan_logits_grad: kind %d", kind);
+    }
+    CGS_CHECK_LAUNCH("gan_logits_grad");
     return CGS_OK;
 }
 

@@ -578,6 +578,7 @@ class RefineEngine:
             self.images = torch.empty((B,) + tuple(A["img"]), **f32)
         self.use_graph = use_graph
         self._graphs = {}
+        self._ladam, self.mean_square = None, None     # the ladam rule's state (K.LadamState, v): allocated at its first use
         self._gstream = None                 # the side stream hipGraphs are warmed up and captured on
         self._ws_epoch = K.WS.epoch          # the parameter state the folded affines / graph workspaces were derived from
         # sync_bn = True (default process group) or a process group: this engine's batch is one shard of a logical batch of
@@ -729,34 +730,45 @@ class RefineEngine:
             feat_out = self._feat
         return sig, K.spatial_mean(act, out=feat_out)
 
-    def forward_logits(self, theta, logit_out):
+    def forward_logits(self, theta, logit_out, loss="bce", ladam=None, first=False):
+        """G tail + D + the loss seed: ``self.dlogits`` = d sum loss / d logits for ``loss`` ("bce": softplus(-l), nsgan/GAN.py:176-177;
+        "lsq": (l - 1)^2; "linear": -l), ``logit_out`` = the per-sample mean logit.  ``ladam``: the rule's per-sample state
+        (``K.LadamState``), advanced by the seed launch (``first``: its running loss starts here)."""
         x = self.g_tail.forward(theta)
         head = self.d.stages[-1]
+        plain = loss == "bce" and ladam is None
         if isinstance(head, _Linear) and head.w.shape[1] == 1 and head.epi == L.EPI_NONE:
             # D ends in the one-logit linear head (nsgan/GAN.py:68): head + loss seed + per-sample mean logit in ONE launch
             for st in self.d.stages[:-1]:
                 x = st.fwd(x)
             head.x_in = x
-            return K.linear_out1_bce(x, head.w, head.b, head.out, self.dlogits, logit_out)
+            if plain:
+                return K.linear_out1_bce(x, head.w, head.b, head.out, self.dlogits, logit_out)
+            return K.linear_out1_seed(x, head.w, head.b, head.out, self.dlogits, logit_out, loss, ladam, first)
         logits = self.d.forward(x)
-        K.bce_ones_grad_rowmean(logits, self.dlogits, logit_out)
+        if plain:
+            K.bce_ones_grad_rowmean(logits, self.dlogits, logit_out)
+        else:
+            K.refine_loss_seed(logits, loss, self.dlogits, logit_out, ladam, first)
         return logits
 
     def backward_to_feature(self):
-        """d sum_b softplus(-logit_b) / d theta, through D then the G tail (collaborator.py:31)."""
+        """d sum_b loss(logit_b) / d theta for the loss of the last ``forward_logits``, through D then the G tail (collaborator.py:31)."""
         return self.g_tail.backward(self.d.backward(self.dlogits))
 
     @_entry
-    def compute_forward_logits_and_grad(self, feature):
+    def compute_forward_logits_and_grad(self, feature, loss="bce"):
+        if loss not in ("bce", "lsq", "linear"):
+            raise L.CgsError(f"loss {loss!r}: the engine differentiates 'bce', 'lsq' and 'linear'")
         self._sync_weights()
-        self.forward_logits(feature, self.logit)
+        self.forward_logits(feature, self.logit, loss)
         return self.logit, self.backward_to_feature()
 
     # -- the K-step program -------------------------------------------------------------------
-    def _program(self, steps, rate, alpha, probabilistic, vmin, vmax):
+    def _program(self, steps, rate, alpha, probabilistic, vmin, vmax, loss="bce", ladam=None):
         th = self.theta
         render = self.g_tail.stages[-1].out                         # x = G_tail(theta) of the current step
-        self.forward_logits(th, self.logit)
+        self.forward_logits(th, self.logit, loss, ladam, True)
         self.default_logit.copy_(self.logit)
         self.best_logit.copy_(self.logit)
         self.best_theta.copy_(th)
@@ -766,26 +778,37 @@ class RefineEngine:
         forced = self.forced if probabilistic else None
         for i in range(steps):
             g = self.backward_to_feature()
-            K.refine_update(th, self.mom, g, rate, alpha, first=(i == 0), vmin=vmin, vmax=vmax)
-            self.forward_logits(th, self.logit)                     # the K-th gradient is never formed (Q4)
+            if ladam is None:
+                K.refine_update(th, self.mom, g, rate, alpha, first=(i == 0), vmin=vmin, vmax=vmax)
+            else:                                                   # (the gain of this step: left by the seed launch of the forward above it)
+                K.refine_update_ladam(th, self.mom, self.mean_square, g, ladam.gain, rate, first=(i == 0), vmin=vmin, vmax=vmax)
+            self.forward_logits(th, self.logit, loss, ladam, False)  # the K-th gradient is never formed (Q4)
             # collaborator.py:88 renders G_tail(best_theta) once more at the end; the very same image was already
             # rendered in the step that selected it, so it is kept by the same row-select instead (bit-identical)
             K.refine_select2(render, self.images, th, self.best_theta, self.logit, forced, i, self.best_logit, self.best_step, self.tickets)
 
     @_entry
     def refine(self, feature0, steps, rate, method="momentum", mode="deterministic", indices=None,
-               vmin=None, vmax=None):
+               vmin=None, vmax=None, loss="bce", real_sigmoid_mean=None):
         """collaborator.py:41-88 on device.  Returns (images, default_logit, optimal_logit, optimal_step,
-        optimal_feature) -- engine-owned buffers, valid until the next call."""
+        optimal_feature) -- engine-owned buffers, valid until the next call.
+        ``loss``: the unreduced per-logit loss the steps descend -- "bce" softplus(-l) (nsgan/GAN.py:176-177), "lsq" (l - 1)^2,
+        "linear" -l.  ``method="ladam"`` needs ``real_sigmoid_mean``, D's mean score on real data (a float or a device scalar): the
+        per-sample loss of policy.py:48-51 is then real_sigmoid_mean - sigmoid score of the sample (sampling/refiner_cpu.py:28,55)."""
+        ladam = None
         if method == "momentum":
             alpha = 0.9                                             # policy.py:10
         elif method == "sgd":
             alpha = 0.0
         elif method == "ladam":
-            raise L.CgsError("ladam needs a loss argument the map-space refiner never passes "
-                             "(sampling/collaborator.py:66 vs policy.py:48-51); use momentum or sgd")
+            if real_sigmoid_mean is None:
+                raise L.CgsError("ladam needs a loss argument the map-space refiner never passes "
+                                 "(sampling/collaborator.py:66 vs policy.py:48-51); use momentum or sgd, or pass real_sigmoid_mean")
+            alpha = None
         else:
             raise NotImplementedError(method)
+        if loss not in ("bce", "lsq", "linear"):
+            raise L.CgsError(f"loss {loss!r}: the engine differentiates 'bce', 'lsq' and 'linear'")
         if mode not in ("deterministic", "probabilistic"):
             raise NotImplementedError(mode)
         prob = mode == "probabilistic"
@@ -798,9 +821,15 @@ class RefineEngine:
         self._sync_weights()
         with torch.cuda.device(self.dev):
             self.theta.copy_(feature0)
-            key = (steps, float(rate), alpha, prob, vmin, vmax)
+            if method == "ladam":
+                if self._ladam is None:                             # (first ladam use: v, loss_avg, gain)
+                    self._ladam = K.LadamState(self.B, self.dev)
+                    self.mean_square = torch.empty_like(self.mom)
+                ladam = self._ladam
+                ladam.set_real(real_sigmoid_mean)                   # a device scalar the seed launches read: a new value replays the same graph
+            key = (steps, float(rate), alpha, prob, vmin, vmax, loss, method)
             if not self.use_graph:
-                self._program(steps, rate, alpha, prob, vmin, vmax)
+                self._program(steps, rate, alpha, prob, vmin, vmax, loss, ladam)
             else:
                 g = self._graphs.get(key)
                 if g is None:
@@ -812,7 +841,7 @@ class RefineEngine:
                     cur = torch.cuda.current_stream(self.dev)
                     self._gstream.wait_stream(cur)
                     with torch.cuda.stream(self._gstream):
-                        self._program(steps, rate, alpha, prob, vmin, vmax)
+                        self._program(steps, rate, alpha, prob, vmin, vmax, loss, ladam)
                         self.theta.copy_(feature0)
                     torch.cuda.synchronize(self.dev)
                     # (thread-local capture: other threads of the process -- RCCL proxies, the distributed watchdog, a second engine's
@@ -826,7 +855,7 @@ class RefineEngine:
                     try:
                         g = torch.cuda.CUDAGraph()
                         with torch.cuda.graph(g, stream=self._gstream, capture_error_mode="thread_local"):
-                            self._program(steps, rate, alpha, prob, vmin, vmax)
+                            self._program(steps, rate, alpha, prob, vmin, vmax, loss, ladam)
                     except L.CgsError:
                         raise
                     except Exception as ex:                          # noqa: BLE001 (HIP / allocator / another thread's HIP call refused the capture)

@@ -736,6 +736,85 @@ def linear_out1_bce(x, w, bias, logits, dlogits, logit_mean):
     return logits
 
 
+def _loss_kind(kind, allowed):
+    code = L.LOSSES.get(kind) if isinstance(kind, str) else kind
+    if code not in [L.LOSSES[k] for k in allowed]:
+        raise L.CgsError(f"loss {kind!r}: expected one of {allowed}")
+    return code
+
+
+class LadamState:
+    """The ladam rule's per-sample state on the device (include/cgs_hip.h, cgs_ladam_seed): ``s_real`` [1] the mean score of real data the
+    per-sample loss is measured against, ``loss_avg`` [B] its running average, ``gain`` [B] the step's per-sample factor.  ``s_real`` is read
+    by the launch, so a captured program replays with whatever ``set_real`` wrote last."""
+
+    def __init__(self, B, device):
+        self.s_real = torch.zeros(1, dtype=torch.float32, device=device)
+        self.loss_avg = torch.empty(B, dtype=torch.float32, device=device)
+        self.gain = torch.empty(B, dtype=torch.float32, device=device)
+
+    def set_real(self, value):
+        """A float, or a device scalar (copied in stream order: no host synchronisation either way)."""
+        if isinstance(value, torch.Tensor):
+            self.s_real.copy_(value.reshape(1))
+        else:
+            self.s_real.fill_(float(value))
+
+    def arg(self, first):
+        import ctypes
+        return ctypes.byref(L.LadamSeed(_ptr(self.s_real), _ptr(self.loss_avg), _ptr(self.gain), 1 if first else 0))
+
+
+def refine_loss_seed(logits, kind, dlogits=None, logit_mean=None, ladam=None, first=False):
+    """d loss / d logit of the unreduced refinement loss ``kind`` ("bce": softplus(-l), "lsq": (l - 1)^2, "linear": -l) and the per-sample
+    mean logit, which is that of ``bce_ones_grad_rowmean`` bit for bit.  ``ladam``: a ``LadamState`` this launch advances by one step."""
+    _chk(logits, "logits")
+    B = logits.shape[0]
+    dl = dlogits if dlogits is not None else torch.empty_like(logits)
+    lm = logit_mean if logit_mean is not None else torch.empty(B, dtype=torch.float32, device=logits.device)
+    L.call("cgs_refine_loss_seed", _ptr(logits), _loss_kind(kind, ("bce", "lsq", "linear")), _ptr(dl), _ptr(lm), B, logits.numel() // B,
+           None if ladam is None else ladam.arg(first), _stream())
+    return dl, lm
+
+
+def linear_out1_seed(x, w, bias, logits, dlogits, logit_mean, kind, ladam=None, first=False):
+    """``linear_out1_bce`` for any refinement loss: linear_fwd(N = 1) then ``refine_loss_seed`` in one launch."""
+    _chk(x, "x"); _chk(w, "w")
+    B, K = x.shape
+    pr = _Prof(2.0 * B * K, "", _nb(x, w, logits), op="linear_out1_fwd") if PROFILE is not None else None
+    L.call("cgs_linear_out1_seed", _ptr(x), _ptr(w), _ptr(bias), _ptr(logits), _ptr(dlogits), _ptr(logit_mean), B, K,
+           _loss_kind(kind, ("bce", "lsq", "linear")), None if ladam is None else ladam.arg(first), _stream())
+    if pr is not None:
+        pr.done()
+    return logits
+
+
+def ladam_gain(loss, loss_avg, gain, first):
+    """The ladam rule's running loss and per-sample gain from a per-sample ``loss`` [B] on the device (policy.py:48-51,56)."""
+    for t, name in ((loss, "loss"), (loss_avg, "loss_avg"), (gain, "gain")):
+        _chk(t, name)
+    B = loss.numel()
+    if loss_avg.numel() != B or gain.numel() != B:
+        raise L.CgsError("ladam_gain: loss, loss_avg and gain must have one size")
+    L.call("cgs_ladam_gain", _ptr(loss), _ptr(loss_avg), _ptr(gain), 1 if first else 0, B, _stream())
+    return gain
+
+
+def refine_update_ladam(theta, m, v, g, gain, rate, first, vmin=None, vmax=None):
+    """In-place ladam step on the map ``theta`` [B, ...] (+ optional clip) with the per-sample ``gain`` a seed launch left.  policy.py:39-59."""
+    for t, name in ((theta, "theta"), (m, "m"), (v, "v"), (g, "g"), (gain, "gain")):
+        _chk(t, name)
+    B = theta.shape[0]
+    if m.numel() != theta.numel() or v.numel() != theta.numel() or g.numel() != theta.numel() or gain.numel() < B:
+        raise L.CgsError("refine_update_ladam: theta, m, v and g must have one size, gain at least B elements")
+    use_clip = 1 if (vmin and vmax) else 0          # the reference's truthiness test (quirk Q5)
+    pr = _Prof(0.0, "", _nb(theta, theta, m, v, g) + (0.0 if first else _nb(m, v)), op="refine_update_ladam") if PROFILE is not None else None
+    L.call("cgs_refine_update_ladam", _ptr(theta), _ptr(m), _ptr(v), _ptr(g), _ptr(gain), float(rate), 1 if first else 0, use_clip,
+           float(vmin or 0.0), float(vmax or 0.0), B, theta.numel() // B, _stream())
+    if pr is not None:
+        pr.done()
+
+
 def refine_select_rows(src, logit, forced, step_index, dst, best_logit):
     """Copy the rows of ``src`` whose sample is selected at this step into ``dst`` (predicate of refine_select;
     call before it, which updates best_logit)."""
@@ -864,6 +943,27 @@ def bce_logits_grad(logits, target, scale, dlogits=None, loss=None):
     dl = dlogits if dlogits is not None else torch.empty_like(logits)
     L.call("cgs_bce_logits_grad", _ptr(logits), float(target), float(scale), _ptr(dl), _ptr(loss), logits.numel(), _stream())
     return dl
+
+
+def gan_logits_grad(logits, kind, target, scale, dlogits=None, loss=None):
+    """``bce_logits_grad`` for the GAN training loss ``kind``: "bce"; "lsq" (l - target)^2; "hinge" relu(1 - l) on real (target 1),
+    relu(1 + l) on fake (target 0); "linear" -l (the generator's side of hinge).  dlogits = scale * d loss, loss[0] = scale * sum loss."""
+    _chk(logits, "logits")
+    dl = dlogits if dlogits is not None else torch.empty_like(logits)
+    L.call("cgs_gan_logits_grad", _ptr(logits), _loss_kind(kind, ("bce", "lsq", "linear", "hinge")), float(target), float(scale), _ptr(dl), _ptr(loss),
+           logits.numel(), _stream())
+    return dl
+
+
+def gan_loss(logits, kind, target, dloss=None, out=None):
+    """The loss ``kind`` of ``gan_logits_grad`` per logit, unreduced ("lsq", "hinge", "linear"); with ``dloss`` its input gradient
+    dloss * d loss / d logit."""
+    _chk(logits, "logits")
+    if dloss is not None:
+        _chk(dloss, "dloss")
+    o = out if out is not None else torch.empty_like(logits)
+    L.call("cgs_gan_loss", _ptr(logits), _loss_kind(kind, ("lsq", "linear", "hinge")), float(target), _ptr(dloss), _ptr(o), logits.numel(), _stream())
+    return o
 
 
 def adam_step(w, g, m, v, lr_t, beta1, beta2, eps):

@@ -16,6 +16,14 @@ CONV_FWD, CONV_BWD_DATA, DECONV_FWD, DECONV_BWD_DATA = 0, 1, 2, 3
 FAMILY_IGEMM, FAMILY_QUAD, FAMILY_SMALLN_T, FAMILY_SMALLN_F, FAMILY_PATCH, FAMILY_TAPS, FAMILY_DOT, FAMILY_IGEMM_BX6 = 0, 1, 2, 3, 4, 5, 6, 7
 CONTRACTION_F32, CONTRACTION_BX6, CONTRACTION_BX6_ALL = 0, 1, 2
 CONTRACTIONS = {"f32": CONTRACTION_F32, "bx6": CONTRACTION_BX6, "bx6_all": CONTRACTION_BX6_ALL}
+LOSS_BCE, LOSS_LSQ, LOSS_LINEAR, LOSS_HINGE = 0, 1, 2, 3
+LOSSES = {"bce": LOSS_BCE, "lsq": LOSS_LSQ, "linear": LOSS_LINEAR, "hinge": LOSS_HINGE}
+
+
+class LadamSeed(C.Structure):
+    """cgs_ladam_seed of include/cgs_hip.h: the ladam rule's per-sample state, advanced by a seed launch."""
+    _fields_ = [("s_real", C.c_void_p), ("loss_avg", C.c_void_p), ("gain", C.c_void_p), ("first", C.c_int)]
+
 
 _p, _i, _f, _z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _ll = C.c_longlong
@@ -82,6 +90,12 @@ SIGNATURES = {
     "cgs_refine_select_rows": (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _p]),
     "cgs_refine_select2": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p, _i, _p]),
     "cgs_linear_out1_bce": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p]),
+    "cgs_linear_out1_seed": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "cgs_refine_loss_seed": (_i, [_p, _i, _p, _p, _i, _i, _p, _p]),
+    "cgs_refine_update_ladam": (_i, [_p, _p, _p, _p, _p, _f, _i, _i, _f, _f, _i, _i, _p]),
+    "cgs_ladam_gain": (_i, [_p, _p, _p, _i, _i, _p]),
+    "cgs_gan_logits_grad": (_i, [_p, _i, _f, _f, _p, _p, _i, _p]),
+    "cgs_gan_loss": (_i, [_p, _i, _f, _p, _p, _z, _p]),
     "cgs_mlp2d_sigmoid_saliency": (_i, [_p, _p, _i, _i, _p, _p, _p, _i, _f, _p]),
     "cgs_refine2d": (_i, [_p, _p, _i, _i, _p, _f, _f, _i, _f, _i, _p, _p, _p, _i, _p]),
     "cgs_refine2d_devbase": (_i, [_p, _p, _i, _i, _p, _p, _f, _i, _f, _i, _p, _p, _p, _i, _p]),

@@ -142,9 +142,22 @@ class GAN(object):
         self._engines[ekey] = (hit[0], ops.generation())
         return hit[0]
 
-    def build_refiner(self, rollout_steps, rollout_rate, rollout_method="momentum"):
-        """nsgan/GAN.py:179-181."""
+    @staticmethod
+    def loss_refine_lsq(logits):
+        """The refiner's loss against a least-squares discriminator: (logit - 1)^2, unreduced."""
+        return ops.least_squares_loss(logits, 1.0)
+
+    @staticmethod
+    def loss_refine_linear(logits):
+        """The refiner's loss against a hinge / Wasserstein critic: -logit, unreduced."""
+        return ops.hinge_loss(logits)
+
+    def build_refiner(self, rollout_steps, rollout_rate, rollout_method="momentum", loss="bce"):
+        """nsgan/GAN.py:179-181.  ``loss``: "bce" (the reference's, :176-177), "lsq" or "linear"."""
         from .sampling.collaborator import Refiner
+        closures = {"bce": self.loss_refine, "lsq": self.loss_refine_lsq, "linear": self.loss_refine_linear}
+        if loss not in closures:
+            raise ValueError(f"loss {loss!r}: expected one of {sorted(closures)}")
         refiner = Refiner(rollout_steps=rollout_steps, rollout_rate=rollout_rate, rollout_method=rollout_method)
-        refiner.set_env(self.discriminator_refine, self.feature_to_data, self.loss_refine)
+        refiner.set_env(self.discriminator_refine, self.feature_to_data, closures[loss])
         return refiner

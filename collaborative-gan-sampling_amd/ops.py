@@ -275,6 +275,20 @@ class _BceOnes(torch.autograd.Function):
         return K.bce_ones_bwd(dloss.contiguous(), logits)
 
 
+class _GanLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, kind, target):
+        logits = logits.contiguous()
+        ctx.save_for_backward(logits)
+        ctx.kind, ctx.target = kind, target
+        return K.gan_loss(logits, kind, target)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (logits,) = ctx.saved_tensors
+        return K.gan_loss(logits, ctx.kind, ctx.target, dloss.contiguous()), None, None
+
+
 # ----------------------------------------------------------------------------- the operator API
 def concat(tensors, axis, *args, **kwargs):
     """nsgan/ops.py:12-17."""
@@ -380,6 +394,20 @@ def linear(input_, output_size, scope=None, stddev=0.02, bias_start=0.0, with_w=
 def sigmoid_cross_entropy_with_logits_ones(logits):
     """tf.nn.sigmoid_cross_entropy_with_logits(logits, labels=ones), unreduced (nsgan/GAN.py:176-177)."""
     return _BceOnes.apply(logits)
+
+
+def least_squares_loss(logits, target=1.0):
+    """(logits - target)^2, unreduced: the least-squares GAN loss (target 1 on real data and on the generator's / refiner's side, 0 on
+    D's fake side).  One kernel forward and one backward (``cgs_gan_loss``)."""
+    return _GanLoss.apply(logits, "lsq", float(target))
+
+
+def hinge_loss(logits, real=None):
+    """The hinge GAN loss, unreduced: ``real=True`` relu(1 - logits), ``real=False`` relu(1 + logits) -- D's two sides -- and
+    ``real=None`` -logits, the generator's / refiner's side."""
+    if real is None:
+        return _GanLoss.apply(logits, "linear", 0.0)
+    return _GanLoss.apply(logits, "hinge", 1.0 if real else 0.0)
 
 
 class _Constant(object):

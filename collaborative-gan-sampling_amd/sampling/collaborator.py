@@ -9,7 +9,8 @@ Execution paths (both all-HIP, no CPU fallback; ``refiner.path`` says which one 
 ``refiner.why_generic`` why the engine was not taken):
   * engine:  if ``discriminator`` / ``feature_to_data`` are a ``cgs_amd.model.GAN``'s own methods -- bound, or wrapped
              in ``functools.partial`` the way nsgan/GAN.py:174-175 wraps them -- and ``func_loss`` computes the
-             cross entropy against ones (GAN.loss_refine, or any closure that evaluates to softplus(-logit), :176-177),
+             cross entropy against ones (GAN.loss_refine, or any closure that evaluates to softplus(-logit), :176-177), the
+             least-squares loss (logit - 1)^2 or the linear loss -logit (``loss_kind`` says which the probe found),
              the whole loop runs as the fused device program (``engine.RefineEngine``): state resident in HBM, no host
              sync, the K-step program replayed as a hipGraph (``use_graph``, default on; eager fallback in-process).
              The engine differentiates softplus(-logit) analytically: a ``func_loss`` with a CUSTOM backward or side
@@ -63,6 +64,9 @@ class Refiner():
         self._gstream = None            # ... the side stream the loops are warmed up and captured on (packed-weight workspaces are per stream)
         self.force_generic = False      # True: never take the engine (e.g. a func_loss with a custom backward that evaluates to BCE-vs-ones)
         self.why_generic = None         # why the last engine detection said no (None while the engine is taken)
+        self.loss_kind = None           # the engine detection's verdict on func_loss: "bce" | "lsq" | "linear" (None: none of them / not asked)
+        self.real_sigmoid_mean = None   # rollout_method "ladam" on the engine: D's mean score on real data (a float or a device scalar); the
+                                        # per-sample loss of policy.py:48-51 is this minus the sample's score (sampling/refiner_cpu.py:28,55)
 
     def set_env(self, discriminator, feature_to_data, func_loss):
         if (getattr(self, "discriminator", None) is not discriminator or getattr(self, "feature_to_data", None) is not feature_to_data
@@ -111,15 +115,16 @@ class Refiner():
     _WARNED = set()            # generic-path reasons already warned about (once per process and reason)
 
     @classmethod
-    def _loss_is_bce_ones(cls, func_loss, device):
-        """Is ``func_loss`` the unreduced cross entropy against all-ones labels, softplus(-logit) (nsgan/GAN.py:176-177)?  The
-        reference passes a local closure, so identity cannot tell: the function is evaluated ONCE on 40 logits -- 24 evenly spaced
-        over [-40, 40] (a clipped / saturating variant deviates there) and 16 seeded random ones -- and compared with softplus(-l)
-        to 4 fp32 ulp relative + 1e-7 (shape kept = no reduction).  Anything else -- another loss, a reduction, an exception --
-        keeps the generic path, which differentiates whatever it is.  Only VALUES are compared: see ``force_generic``."""
+    def _loss_kind(cls, func_loss, device):
+        """Which of the engine's losses is ``func_loss``: "bce", the unreduced cross entropy against all-ones labels softplus(-logit)
+        (nsgan/GAN.py:176-177); "lsq", (logit - 1)^2; "linear", -logit; or None?  The reference passes a local closure, so identity
+        cannot tell: the function is evaluated ONCE on 40 logits -- 24 evenly spaced over [-40, 40] (a clipped / saturating variant
+        deviates there) and 16 seeded random ones -- and compared with each candidate to 4 fp32 ulp relative + 1e-7 (shape kept = no
+        reduction).  Anything else -- another loss, a scaled one, a reduction, an exception -- keeps the generic path, which
+        differentiates whatever it is.  Only VALUES are compared: see ``force_generic``."""
         from ..model import GAN
         if func_loss is GAN.loss_refine:
-            return True
+            return "bce"
         # a bound method is a fresh object at every attribute access: key it by (object, function), and follow the object with WeakMethod
         bound = hasattr(func_loss, "__self__") and hasattr(func_loss, "__func__")
         key = ("m", id(func_loss.__self__), id(func_loss.__func__)) if bound else ("f", id(func_loss))
@@ -128,22 +133,30 @@ class Refiner():
             alive = hit[0]()
             if alive is not None and (alive == func_loss if bound else alive is func_loss):
                 return hit[1]
-        ok = False
+        kind = None
         try:
             l = np.concatenate([np.linspace(-40.0, 40.0, 24), np.random.RandomState(2019).normal(0.0, 6.0, 16)]).astype(np.float32).reshape(40, 1)
             with torch.no_grad():
                 got = func_loss(torch.from_numpy(l).to(device))
-            want = np.logaddexp(0.0, -l.astype(np.float64))
-            ok = (torch.is_tensor(got) and tuple(got.shape) == (40, 1)
-                  and bool((np.abs(got.detach().double().cpu().numpy() - want) <= 4 * 2.0 ** -23 * np.abs(want) + 1e-7).all()))
-        except Exception:                                   # noqa: BLE001 (a loss that cannot take a [40, 1] tensor is not this one)
-            ok = False
+            if torch.is_tensor(got) and tuple(got.shape) == (40, 1):
+                got = got.detach().double().cpu().numpy()
+                l64 = l.astype(np.float64)
+                for name, want in (("bce", np.logaddexp(0.0, -l64)), ("lsq", (l64 - 1.0) ** 2), ("linear", -l64)):
+                    if bool((np.abs(got - want) <= 4 * 2.0 ** -23 * np.abs(want) + 1e-7).all()):
+                        kind = name
+                        break
+        except Exception:                                   # noqa: BLE001 (a loss that cannot take a [40, 1] tensor is none of these)
+            kind = None
         try:       # (the reference makes a new closure per model build: keep no function alive, drop the verdict with it)
             drop = lambda _r, key=key: cls._BCE_PROBE.pop(key, None)        # noqa: E731
-            cls._BCE_PROBE[key] = ((weakref.WeakMethod if bound else weakref.ref)(func_loss, drop), ok)
+            cls._BCE_PROBE[key] = ((weakref.WeakMethod if bound else weakref.ref)(func_loss, drop), kind)
         except TypeError:                                   # not weak-referenceable (a builtin): probe it again next time
             pass
-        return ok
+        return kind
+
+    @classmethod
+    def _loss_is_bce_ones(cls, func_loss, device):
+        return cls._loss_kind(func_loss, device) == "bce"
 
     def _engine_owner(self):
         """The ``model.GAN`` whose layer lists ARE the three callables of ``set_env`` -- in any of the spellings the reference's
@@ -176,10 +189,16 @@ class Refiner():
             return no("discriminator is not GAN.discriminator / GAN.discriminator_refine")
         if f[1] is not GAN.feature_to_data or f[2].get("is_training", False) is not False:
             return no("feature_to_data is not GAN.feature_to_data in inference mode")
-        if self.optimizer.method not in ("momentum", "sgd"):
-            return no(f"rollout_method {self.optimizer.method!r}: the engine runs momentum / sgd")
-        if not self._loss_is_bce_ones(self.func_loss, owner.device):
-            return no("func_loss does not evaluate to the unreduced cross entropy against ones, softplus(-logit) (nsgan/GAN.py:176-177)")
+        if self.optimizer.method == "ladam":
+            if self.real_sigmoid_mean is None:
+                return no("rollout_method 'ladam' needs refiner.real_sigmoid_mean (D's mean score on real data): the map-space refiner "
+                          "passes the rule no loss (sampling/collaborator.py:66 vs policy.py:48-51)")
+        elif self.optimizer.method not in ("momentum", "sgd"):
+            return no(f"rollout_method {self.optimizer.method!r}: the engine runs momentum / sgd / ladam")
+        self.loss_kind = self._loss_kind(self.func_loss, owner.device)
+        if self.loss_kind is None:
+            return no("func_loss evaluates to none of the engine's unreduced losses: softplus(-logit) (cross entropy against ones, "
+                      "nsgan/GAN.py:176-177), (logit - 1)^2, -logit")
         return owner
 
     def _engine_for(self, batch):
@@ -216,9 +235,10 @@ class Refiner():
             self.path = "engine"
             args = (fake_feature, K_steps, self.optimizer.lambda_, self.optimizer.method, mode,
                     self.indices_batch if mode == 'probabilistic' else None, self.vmin, self.vmax)
+            kw = dict(loss=self.loss_kind, real_sigmoid_mean=self.real_sigmoid_mean)
             eng = owner.engine(B, use_graph=self.use_graph, contraction=self.contraction, bn_groups=G)
             try:
-                out = eng.refine(*args)
+                out = eng.refine(*args, **kw)
             except L.GraphCaptureError as ex:                     # the capture block refused (HIP, allocator, another thread's HIP call)
                 # same process, the SAME engine and buffers, launched kernel by kernel instead; the refiner stays eager from here on
                 # and says why.  (Argument errors, OOM or a failure of the eager warm-up are not caught: they are what they are.)
@@ -229,7 +249,7 @@ class Refiner():
                 except Exception:                                 # noqa: BLE001
                     pass
                 eng = owner.demote_engine_to_eager(B, self.contraction, G)      # (the one place the cache's key layout lives: model.GAN)
-                out = eng.refine(*args)
+                out = eng.refine(*args, **kw)
             img, d_l, o_l, o_s, o_f = out
             # the engine returns its own (cached, reused) buffers: hand out copies, so that a second build_refiner -- the
             # reference builds a deterministic and a probabilistic refiner side by side, nsgan/GAN.py:182-183 -- does not

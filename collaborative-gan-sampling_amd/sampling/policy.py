@@ -6,7 +6,8 @@
 
 Host arrays (numpy, the 2-D path of refiner_cpu) are updated IN PLACE like the reference's ``-=``
 on an ndarray; torch tensors get a new tensor back (TF value semantics).  On GPU tensors the
-momentum / sgd update is one fused kernel (cgs_refine_update).
+momentum / sgd update is one fused kernel (cgs_refine_update), and so is ladam's activation-map
+branch (cgs_ladam_gain for the per-sample state, cgs_refine_update_ladam for the map).
 """
 import numpy as np
 
@@ -61,6 +62,8 @@ class PolicyAdaptive(object):
             if loss is None:
                 raise ValueError("ladam needs the per-sample loss (the reference's map-space refiner never passes "
                                  "one: sampling/collaborator.py:66)")
+            if self._is_torch(theta) and theta.is_cuda and theta.dim() >= 2 and theta.shape[1] > 2:
+                return self._device_ladam(theta, grad, loss)
             one = 1.0
             self.momentum = grad if self.momentum is None else self.beta1_ * self.momentum + (one - self.beta1_) * grad
             sq = grad ** 2
@@ -82,4 +85,20 @@ class PolicyAdaptive(object):
             self.momentum = torch.empty_like(theta)
         new_theta = theta.clone()
         K.refine_update(new_theta, self.momentum, grad.contiguous(), self.lambda_, alpha, first)
+        return new_theta
+
+    def _device_ladam(self, theta, grad, loss):
+        """The activation-map branch (:53-59) on device tensors: the running loss and the per-sample gain in one small launch, the map
+        update in one pass (cgs_ladam_gain, cgs_refine_update_ladam)."""
+        from .. import kernels as K
+        n = theta.shape[0]
+        first = self.momentum is None
+        if first:
+            self.momentum, self.mean_square = torch.empty_like(theta), torch.empty_like(theta)
+            self.loss = torch.empty(n, dtype=torch.float32, device=theta.device)
+            self._gain = torch.empty(n, dtype=torch.float32, device=theta.device)
+        loss = torch.as_tensor(loss, dtype=torch.float32, device=theta.device).reshape(-1).expand(n).contiguous()
+        K.ladam_gain(loss, self.loss, self._gain, first)
+        new_theta = theta.clone()
+        K.refine_update_ladam(new_theta, self.momentum, self.mean_square, grad.contiguous(), self._gain, self.lambda_, first)
         return new_theta

@@ -27,7 +27,12 @@ COUT1_WGRAD = True
 
 
 class DShaper:
-    def __init__(self, arch, params, batch_size, device="cuda:0", learning_rate=2e-4, beta1=0.5, beta2=0.999, eps=1e-8):
+    def __init__(self, arch, params, batch_size, device="cuda:0", learning_rate=2e-4, beta1=0.5, beta2=0.999, eps=1e-8, loss="bce"):
+        """``loss``: D's training loss, the mean over every logit of "bce" (the reference's, nsgan/GAN.py:126-131), "lsq" ((l - 1)^2 on real,
+        l^2 on refined: the PatchGAN's usual loss) or "hinge" (relu(1 - l) on real, relu(1 + l) on refined)."""
+        if loss not in ("bce", "lsq", "hinge"):
+            raise L.CgsError(f"DShaper: loss {loss!r}: expected 'bce', 'lsq' or 'hinge'")
+        self.loss = loss
         self.A = ARCHS[arch] if isinstance(arch, str) else arch
         self.dev = torch.device(device)
         self.B = int(batch_size)
@@ -98,7 +103,10 @@ class DShaper:
             for i, (x, target) in enumerate(((real, 1.0), (refined, 0.0))):
                 logits = self.tape.forward(x.contiguous())
                 n = logits.numel()
-                K.bce_logits_grad(logits, target, 1.0 / n, self.dlogits, self.loss_buf[i:i + 1])
+                if self.loss == "bce":
+                    K.bce_logits_grad(logits, target, 1.0 / n, self.dlogits, self.loss_buf[i:i + 1])
+                else:
+                    K.gan_logits_grad(logits, self.loss, target, 1.0 / n, self.dlogits, self.loss_buf[i:i + 1])
                 self._backward(self.dlogits, accumulate=(i == 1))
             return self.loss_buf.sum()
 

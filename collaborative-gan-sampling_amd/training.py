@@ -23,7 +23,12 @@ BN_DECAY = 0.9      # nsgan/ops.py:21
 
 
 class GStepper:
-    def __init__(self, arch, params, batch_size, device="cuda:0", learning_rate=2e-4, beta1=0.5, beta2=0.999, eps=1e-8):
+    def __init__(self, arch, params, batch_size, device="cuda:0", learning_rate=2e-4, beta1=0.5, beta2=0.999, eps=1e-8, loss="bce"):
+        """``loss``: G's training loss, the mean over every logit of "bce" (softplus(-l), nsgan/GAN.py:130-131), "lsq" ((l - 1)^2) or
+        "linear" (-l, the generator's side of a hinge discriminator)."""
+        if loss not in ("bce", "lsq", "linear"):
+            raise L.CgsError(f"GStepper: loss {loss!r}: expected 'bce', 'lsq' or 'linear'")
+        self.loss = loss
         self.A = ARCHS[arch] if isinstance(arch, str) else arch
         self.dev = torch.device(device)
         self.B = int(batch_size)
@@ -113,7 +118,10 @@ class GStepper:
         """g_loss (device scalar tensor) and the gradients of every G variable (left in the ``g_*`` buffers).  D's variables are read only."""
         with torch.cuda.device(self.dev):
             logits = self.d.forward(self.forward(z))
-            K.bce_logits_grad(logits, 1.0, 1.0 / logits.numel(), self.dlogits, self.loss_buf)
+            if self.loss == "bce":
+                K.bce_logits_grad(logits, 1.0, 1.0 / logits.numel(), self.dlogits, self.loss_buf)
+            else:
+                K.gan_logits_grad(logits, self.loss, 1.0, 1.0 / logits.numel(), self.dlogits, self.loss_buf)
             self._backward(self.d.backward(self.dlogits))
             return self.loss_buf[0].clone()
 
@@ -145,10 +153,14 @@ class GanTrainer:
     size), the second captures and replays, later ones replay.  ``path`` names what the last call ran, ``graph_fallback`` why a capture was
     refused (the trainer then goes on with eager launches)."""
 
-    def __init__(self, arch, params, batch_size, device="cuda:0", learning_rate=2e-4, beta1=0.5, engine=None, use_graph=False):
-        self.arch, self.P = arch, params
-        self.dshaper = DShaper(arch, params, batch_size, device, learning_rate=learning_rate, beta1=beta1)
-        self.gstepper = GStepper(arch, params, batch_size, device, learning_rate=learning_rate, beta1=beta1)
+    def __init__(self, arch, params, batch_size, device="cuda:0", learning_rate=2e-4, beta1=0.5, engine=None, use_graph=False, loss="bce"):
+        """``loss``: "bce" (the reference's), "lsq" (least squares on both sides) or "hinge" (D's hinge with the linear loss -l for G)."""
+        if loss not in ("bce", "lsq", "hinge"):
+            raise L.CgsError(f"GanTrainer: loss {loss!r}: expected 'bce', 'lsq' or 'hinge'")
+        self.arch, self.P, self.loss = arch, params, loss
+        self.dshaper = DShaper(arch, params, batch_size, device, learning_rate=learning_rate, beta1=beta1, loss=loss)
+        self.gstepper = GStepper(arch, params, batch_size, device, learning_rate=learning_rate, beta1=beta1,
+                                 loss="linear" if loss == "hinge" else loss)
         self.engine = engine                # an optional RefineEngine on the same parameter tensors: kept coherent after every iteration
         self.use_graph = bool(use_graph)
         self.path, self.graph_fallback = "eager", None

@@ -54,6 +54,25 @@ extern "C" {
 #define CGS_DECONV_FWD 2        /* tf.nn.conv2d_transpose              nsgan/ops.py:55 */
 #define CGS_DECONV_BWD_DATA 3   /* its input gradient                  sampling/collaborator.py:31 */
 
+/* the loss a refinement step descends, per logit and unreduced (the func_loss of Refiner.set_env, sampling/collaborator.py:30-31),
+ * and the D-side training losses (cgs_gan_logits_grad) */
+#define CGS_LOSS_BCE 0     /* softplus(-l)   dl = sigmoid(l) - 1        nsgan/GAN.py:176-177                     */
+#define CGS_LOSS_LSQ 1     /* (l - 1)^2      dl = 2 (l - 1)             least squares, the PatchGAN's usual loss */
+#define CGS_LOSS_LINEAR 2  /* -l             dl = -1                    generator side of hinge / Wasserstein    */
+#define CGS_LOSS_HINGE 3   /* D side only: relu(1 - l) on real, relu(1 + l) on fake                            */
+
+/* The per-sample state of the ladam rule (sampling/policy.py:48-51,56), advanced ONCE per sample by the seed launch of a step:
+ *   loss[b]     = s_real[0] - mean_p sigmoid(logits[b,p])        (sampling/refiner_cpu.py:28,55; the score of cgs_sigmoid_rowmean)
+ *   loss_avg[b] = first ? loss[b] : 0.5 * loss_avg[b] + 0.5 * loss[b]
+ *   gain[b]     = clamp(loss_avg[b] + 0.5, 0, 1e4)^2
+ * Every pointer is device memory; s_real is one float, read at launch time (a captured launch replays with the value of the day). */
+typedef struct cgs_ladam_seed {
+    const float* s_real;
+    float* loss_avg;   /* [B] read (unless first) and written */
+    float* gain;       /* [B] written */
+    int first;
+} cgs_ladam_seed;
+
 int cgs_version(void);
 /* sha256 (64 hex digits) of the kernel sources this library was built from (every .hip and .h file of csrc/, then include/cgs_hip.h), embedded at
  * build time (csrc/Makefile, csrc/stamp.hip).  The host binding refuses a library whose stamp differs from the sources it ships with
@@ -246,6 +265,10 @@ int cgs_linear_fwd(const float* x, const float* w, const float* bias, float* y, 
  * = cgs_linear_fwd(out = 1) followed by cgs_bce_ones_grad_rowmean(P = 1), bit for bit. */
 int cgs_linear_out1_bce(const float* x, const float* w, const float* bias, float* logits, float* dlogits, float* logit_mean, int B, int in,
                         void* stream);
+/* The same head with the loss seed of cgs_refine_loss_seed(kind, ladam) at P = 1: = cgs_linear_fwd(out = 1) followed by that seed, bit
+ * for bit (kind CGS_LOSS_BCE without ladam launches the kernel of cgs_linear_out1_bce itself). */
+int cgs_linear_out1_seed(const float* x, const float* w, const float* bias, float* logits, float* dlogits, float* logit_mean, int B, int in,
+                         int kind, const cgs_ladam_seed* ladam, void* stream);
 /* linear backward-data: dx[B,in] = dy[B,out] @ w^T   (ws: op CGS_CONV_BWD_DATA, kh=kw=1). */
 int cgs_linear_bwd_data(const float* dy, const float* w, float* dx, int B, int in, int out,
                         void* ws, size_t ws_bytes, int ws_prepacked, void* stream);
@@ -326,6 +349,12 @@ int cgs_tanh_bwd(const float* dy, const float* y, float* dx, size_t n, void* str
  * sampling/collaborator.py:31), and the per-sample mean logit over P patch entries
  * (sampling/collaborator.py:34-37).  logits is [B,P]. */
 int cgs_bce_ones_grad_rowmean(const float* logits, float* dlogits, float* logit_mean, int B, int P, void* stream);
+/* The loss seed of any refinement loss: dlogits = d loss(kind) / d logit (CGS_LOSS_BCE, _LSQ, _LINEAR; the gradient of the SUM of the
+ * unreduced loss, collaborator.py:30-31) and logit_mean as cgs_bce_ones_grad_rowmean writes it, bit for bit, whatever the kind (the
+ * selection of collaborator.py:76 does not depend on the loss).  kind CGS_LOSS_BCE gives that entry's dlogits bit for bit.
+ * ladam: NULL, or the ladam rule's per-sample state, advanced by this launch (cgs_ladam_seed above). */
+int cgs_refine_loss_seed(const float* logits, int kind, float* dlogits, float* logit_mean, int B, int P, const cgs_ladam_seed* ladam,
+                         void* stream);
 
 /* loss[i] = softplus(-logits[i]) = tf.nn.sigmoid_cross_entropy_with_logits(labels=1), unreduced (nsgan/GAN.py:176-177),
  * and its input gradient dlogits[i] = dloss[i] * (sigmoid(logits[i]) - 1)  (what tf.gradients emits, collaborator.py:31). */
@@ -334,6 +363,10 @@ int cgs_bce_ones_bwd(const float* dloss, const float* logits, float* dlogits, si
 /* sigmoids[b] = mean over the P logits of sample b of sigmoid(logit): self.fake_sigmoids = tf.nn.sigmoid(self.fake_logits)
  * (nsgan/GAN.py:154-155; P = 1 there), the discriminator score the accept / reject step reads (nsgan/GAN.py:409,422). */
 int cgs_sigmoid_rowmean(const float* logits, float* sigmoids, int B, int P, void* stream);
+/* The GAN training losses unreduced, for the operator API (ops.least_squares_loss / hinge_loss): kind CGS_LOSS_LSQ (l - target)^2,
+ * CGS_LOSS_HINGE relu(1 - l) at target 1 | relu(1 + l) at target 0, CGS_LOSS_LINEAR -l.  dloss == NULL: out[i] = loss(logits[i]);
+ * else out[i] = dloss[i] * d loss / d logit (the formulas of cgs_gan_logits_grad). */
+int cgs_gan_loss(const float* logits, int kind, float target, const float* dloss, float* out, size_t n, void* stream);
 /* y = min(max(x, vmin), vmax): tf.clip_by_value on the refined map (sampling/collaborator.py:69-70). */
 int cgs_clip(const float* x, float vmin, float vmax, float* y, size_t n, void* stream);
 
@@ -343,6 +376,15 @@ int cgs_clip(const float* x, float vmin, float vmax, float* y, size_t n, void* s
  * alpha = 0 and first = 1 give sgd.  n = B*F elements. */
 int cgs_refine_update(float* theta, float* m, const float* g, float rate, float alpha, int first,
                       int use_clip, float vmin, float vmax, size_t n, void* stream);
+/* The ladam state of cgs_ladam_seed from a per-sample loss[B] the caller already holds on the device (PolicyAdaptive.apply_gradient with
+ * a loss): loss_avg = first ? loss : 0.5 * loss_avg + 0.5 * loss; gain = clamp(loss_avg + 0.5, 0, 1e4)^2. */
+int cgs_ladam_gain(const float* loss, float* loss_avg, float* gain, int first, int B, void* stream);
+/* The ladam rule on activation maps (sampling/policy.py:53-59 with :48-51 done by the seed launch), one pass, per element i of B*F:
+ *   m = first ? g : 0.9*m + c1*g ;  v = first ? g*g : 0.5*v + c2*(g*g) ;  theta -= (rate*m / (sqrt(v) + 1e-8)) * gain[i / F]
+ * then the clip of cgs_refine_update.  c1 = (float)(1.0 - 0.9), c2 = (float)(1.0 - 0.5).  Every operation is rounded on its own, in
+ * this order.  gain: the B floats a seed launch given a cgs_ladam_seed, or cgs_ladam_gain, left. */
+int cgs_refine_update_ladam(float* theta, float* m, float* v, const float* g, const float* gain, float rate, int first, int use_clip,
+                            float vmin, float vmax, int B, int F, void* stream);
 /* Best-sample selection (sampling/collaborator.py:76-83): for each sample b
  *   upd = forced ? forced[b] == step_index : logit[b] > best_logit[b]      (strict >)
  *   best_logit[b], best_theta[b,:], best_step[b] = upd ? (logit[b], theta[b,:], step_index+1) : unchanged
@@ -493,6 +535,14 @@ int cgs_conv2d_nhwc_bwd_weight_cout1(const float* x, const float* dy, float* dw,
 /* dlogits[i] = scale*(sigmoid(logits[i]) - target); loss_sum[0] = scale * sum_i BCE(logits[i], target) (may be NULL).
  * tf.nn.sigmoid_cross_entropy_with_logits + reduce_mean (nsgan/GAN.py:126-131) with scale = 1/n. */
 int cgs_bce_logits_grad(const float* logits, float target, float scale, float* dlogits, float* loss_sum, int n, void* stream);
+/* The same seed for the other GAN training losses, one block, the same fixed-order sum.  With t = target (1 real, 0 fake; the
+ * generator's step is CGS_LOSS_LSQ with target 1, or CGS_LOSS_LINEAR):
+ *   CGS_LOSS_BCE     as cgs_bce_logits_grad, bit for bit
+ *   CGS_LOSS_LSQ     loss (l - t)^2                      dl = scale * 2 (l - t)
+ *   CGS_LOSS_HINGE   loss relu(1 - l) | relu(1 + l)      dl = scale * (l < 1 ? -1 : 0) | scale * (l > -1 ? 1 : 0)
+ *   CGS_LOSS_LINEAR  loss -l                             dl = -scale
+ * loss_sum[0] = scale * sum_i loss_i (may be NULL).  target must be 0 or 1 for CGS_LOSS_HINGE. */
+int cgs_gan_logits_grad(const float* logits, int kind, float target, float scale, float* dlogits, float* loss_sum, int n, void* stream);
 /* Adam (tf.train.AdamOptimizer semantics, nsgan/GAN.py:141-146): m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
  * w -= lr_t * m / (sqrt(v) + eps), lr_t = lr*sqrt(1-b2^t)/(1-b1^t) supplied by the caller. */
 int cgs_adam_step(float* w, const float* g, float* m, float* v, float lr_t, float beta1, float beta2, float eps,
