@@ -1161,3 +1161,35 @@ def mode_stats_accumulate(x, centeroids, thres, state):
             raise L.CgsError(f"mode_stats_accumulate: unsupported size (n={n}, k={k})")
         ws = _moments_workspace(need, x.device)
         L.call("cgs_mode_stats_accumulate", _ptr(x), n, _ptr(centeroids), k, float(thres), _ptr(state), _ptr(ws), ws.numel() * 8, _stream())
+
+
+# ----------------------------------------------------------------------------- density map of a 2-D pool (csrc/kde2d.hip)
+KDE_MAX_CELLS = 1 << 20
+
+
+def kde2d_accumulate(x, axis_x, axis_y, whiten, state):
+    """Add the un-normalised Gaussian kernel sums of the 2-D samples ``x`` (device fp32 [n, 2]) on the grid ``axis_x`` x ``axis_y`` (device
+    fp32 [gx], [gy]) to ``state``: float64 [gx * gy + 1] on the same device (row-major [gx][gy] sums | n).  ``whiten``: float64 [3] on the
+    device, w00, w10, w11 of the inverse Cholesky factor of the kernel covariance (metrics.kde_whiten).  The host twin is
+    metrics.density_state_of."""
+    _chk(x, "x")
+    if x.dim() != 2 or x.shape[1] != 2:
+        raise L.CgsError(f"kde2d_accumulate: x must be [n, 2], got {tuple(x.shape)}")
+    for t, name in ((axis_x, "axis_x"), (axis_y, "axis_y")):
+        _chk(t, name)
+        if t.dim() != 1 or t.device != x.device:
+            raise L.CgsError(f"kde2d_accumulate: {name} must be a 1-D fp32 tensor on {x.device}")
+    gx, gy = axis_x.shape[0], axis_y.shape[0]
+    if gx < 1 or gy < 1 or gx * gy > KDE_MAX_CELLS:
+        raise L.CgsError(f"kde2d_accumulate: grid {gx} x {gy} outside 1 <= gx, gy, gx * gy <= 2^20")
+    _f64_dev(whiten, "whiten", (3,), x.device, "kde2d_accumulate")
+    _f64_dev(state, "state", (gx * gy + 1,), x.device, "kde2d_accumulate")
+    n = x.shape[0]
+    if n == 0:
+        return
+    with torch.cuda.device(x.device):
+        need = int(L.load().cgs_kde2d_ws_bytes(n, gx, gy))
+        if need == 0:
+            raise L.CgsError(f"kde2d_accumulate: unsupported size (n={n}, grid {gx} x {gy})")
+        ws = _moments_workspace(need, x.device)
+        L.call("cgs_kde2d_accumulate", _ptr(x), n, _ptr(axis_x), gx, _ptr(axis_y), gy, _ptr(whiten), _ptr(state), _ptr(ws), ws.numel() * 8, _stream())

@@ -131,6 +131,8 @@ SIGNATURES = {
     "cgs_calibration_accumulate": (_i, [_p, _i, _i, _p, _i, _p, _p, _z, _p]),
     "cgs_mode_stats_ws_bytes": (_z, [_i, _i]),
     "cgs_mode_stats_accumulate": (_i, [_p, _i, _p, _i, C.c_double, _p, _p, _z, _p]),
+    "cgs_kde2d_ws_bytes": (_z, [_i, _i, _i]),
+    "cgs_kde2d_accumulate": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _z, _p]),
 }
 
 _lib = None

@@ -412,3 +412,132 @@ def all_reduce_modes(stats, group=None):
     k = st["counts"].shape[0]
     h = _all_reduce_flat(stats, lambda s: np.concatenate([s["counts"].astype(np.float64), [float(s["n"]), float(s["good"]), s["sum_min"]]]), [], group)
     return st if h is None else _mode_state(np.rint(h[:k]), round(h[k]), round(h[k + 1]), h[k + 2])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The density map of a 2-D pool in the same streaming form: the arithmetic of the reference's draw_kde
+# (utils_sampling.py:97-112) without the drawing.  Grid: each axis is np.linspace(-scale, scale, nbins) rounded to fp32, the map is defined
+# at those coordinates widened exactly, index [i, j] = the point (x_i, y_j) as np.mgrid lays it out.  Bandwidth: C = f^2 cov(samples,
+# ddof=1), f = bw_scale n^(-1/6) (Scott's factor for d = 2, halved by set_bandwidth(k.factor / 2.)); C = L L^T, W = L^-1 lower triangular.
+# density(g) = sum_k exp(-1/2 |W (g - x_k)|^2) / (n 2 pi sqrt(det C)).  A STATE is {"sums" [gx, gy]: the un-normalised kernel sums, "n",
+# "whiten" [3]: w00, w10, w11}; with the bandwidth fixed it ADDS across batches, slots and ranks.
+def kde_axes(scale, nbins=100):
+    """One axis of the reference's grid (np.mgrid[-scale:scale:nbins*1j]) as the fp32 coordinates the map is defined at."""
+    return np.linspace(-scale, scale, nbins).astype(np.float32)
+
+
+def kde_whiten(cov, n, bw_scale=0.5):
+    """(whiten, norm) of a pool of ``n`` samples with covariance ``cov`` ([2, 2], ddof = 1): whiten = [w00, w10, w11] of W = L^-1 with
+    L L^T = (bw_scale n^(-1/6))^2 cov, norm = n 2 pi sqrt(det C).  ValueError for n < 2 and for a covariance that is not positive definite
+    to working precision (a collinear pool): scipy's gaussian_kde raises there too."""
+    cov = np.asarray(cov, dtype=np.float64)
+    if cov.shape != (2, 2):
+        raise ValueError(f"kde_whiten: covariance {cov.shape} is not [2, 2]")
+    if n < 2:
+        raise ValueError(f"kde_whiten: a bandwidth needs at least 2 samples, got {n}")
+    c = (bw_scale * float(n) ** (-1.0 / 6.0)) ** 2 * cov
+    try:
+        l = np.linalg.cholesky(c)
+    except np.linalg.LinAlgError:
+        l = None
+    # (rounding can leave a collinear pool a pivot of ~1e-16 c11 instead of 0: below 64 eps of c11 the factor carries no digit)
+    if l is None or not np.isfinite(l).all() or l[1, 1] ** 2 <= 64.0 * np.finfo(np.float64).eps * c[1, 1]:
+        raise ValueError("kde_whiten: the pool's covariance is not positive definite (fewer than 2 distinct samples, or a collinear pool)")
+    whiten = np.array([1.0 / l[0, 0], -l[1, 0] / (l[0, 0] * l[1, 1]), 1.0 / l[1, 1]])
+    return whiten, float(n * 2.0 * np.pi * l[0, 0] * l[1, 1])
+
+
+def _density_state(sums, n, whiten):
+    return dict(sums=np.asarray(sums, dtype=np.float64), n=int(n), whiten=np.asarray(whiten, dtype=np.float64).reshape(3))
+
+
+def density_state_of(samples, axis_x, axis_y, whiten, chunk=512):
+    """The state of a [n, 2] pool on the grid ``axis_x`` x ``axis_y`` in float64 numpy: sums[i, j] = sum_k exp(-1/2 |W (g_ij - x_k)|^2),
+    difference first, then whitened (``chunk`` samples at a time: n gx gy terms)."""
+    x = np.asarray(samples, dtype=np.float64).reshape(-1, 2)
+    ax, ay = np.asarray(axis_x, dtype=np.float64).reshape(-1), np.asarray(axis_y, dtype=np.float64).reshape(-1)
+    w00, w10, w11 = np.asarray(whiten, dtype=np.float64).reshape(3)
+    sums = np.zeros((ax.size, ay.size))
+    for a in range(0, x.shape[0], chunk):
+        dx = ax[None, :, None] - x[a:a + chunk, 0][:, None, None]           # [m, gx, 1]
+        dy = ay[None, None, :] - x[a:a + chunk, 1][:, None, None]           # [m, 1, gy]
+        u, v = w00 * dx, w10 * dx + w11 * dy
+        sums += np.exp(-0.5 * (u * u + v * v)).sum(axis=0)
+    return _density_state(sums, x.shape[0], [w00, w10, w11])
+
+
+def density_merge(a, b):
+    """The state of the union of two pools under ONE bandwidth."""
+    if a["sums"].shape != b["sums"].shape or not np.array_equal(a["whiten"], b["whiten"]):
+        raise ValueError("density_merge: the states are of different grids or bandwidths and do not add")
+    return _density_state(a["sums"] + b["sums"], a["n"] + b["n"], a["whiten"])
+
+
+def density_values(state, norm=None):
+    """The [gx, gy] float64 map: sums / (n 2 pi sqrt(det C)) with the state's own n and sqrt(det C) = 1 / (w00 w11) of its bandwidth;
+    ``norm`` (``kde_whiten``'s, for the pool the bandwidth came from) replaces that divisor."""
+    if norm is None:
+        norm = state["n"] * 2.0 * np.pi / (state["whiten"][0] * state["whiten"][2])
+    return state["sums"] / norm
+
+
+class DensityMap(_DeviceStats):
+    """The density state of every 2-D sample handed to ``update`` on a fixed grid under a FIXED bandwidth (which is what makes it additive):
+    gx gy + 1 doubles on the device (csrc/kde2d.hip)."""
+
+    def __init__(self, axis_x, axis_y, whiten, device):
+        ax, ay = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (axis_x, axis_y))
+        w = np.ascontiguousarray(whiten, dtype=np.float64).reshape(-1)
+        if ax.size < 1 or ay.size < 1 or ax.size * ay.size > 1 << 20:
+            raise ValueError(f"grid {ax.size} x {ay.size} outside 1 <= gx, gy, gx * gy <= 2^20")
+        if w.shape != (3,):
+            raise ValueError("whiten must hold the three numbers w00, w10, w11 (kde_whiten)")
+        self.gx, self.gy, self.whiten_host = ax.size, ay.size, w
+        self._init(device, self.gx * self.gy + 1, "DensityMap")
+        self.axis_x, self.axis_y = self.torch.from_numpy(ax).to(self.device), self.torch.from_numpy(ay).to(self.device)
+        self.whiten = self.torch.from_numpy(w).to(self.device)
+
+    def update(self, x):
+        """Add the samples ``x`` (device fp32 [n, 2])."""
+        from . import kernels as K
+        return self._chained(lambda: K.kde2d_accumulate(x, self.axis_x, self.axis_y, self.whiten, self.vec))
+
+    def state(self):
+        h = self._host()
+        return _density_state(h[:-1].reshape(self.gx, self.gy), round(h[-1]), self.whiten_host)
+
+    def values(self, norm=None):
+        return density_values(self.state(), norm)
+
+
+def all_reduce_density(stats, group=None):
+    """The density state of every rank's pool together (same grid, same bandwidth on every rank): ONE SUM all-reduce of gx gy + 1 doubles.
+    ``stats``: a state or a ``DensityMap``."""
+    st = stats.state() if isinstance(stats, DensityMap) else stats
+    h = _all_reduce_flat(stats, lambda s: np.concatenate([s["sums"].reshape(-1), [float(s["n"])]]), [], group)
+    return st if h is None else _density_state(h[:-1].reshape(st["sums"].shape), round(h[-1]), st["whiten"])
+
+
+def kde_grid(samples, scale, nbins=100, bw_scale=0.5, device=None):
+    """The map ``draw_kde(samples, scale, fname)`` colours, computed on the device in two passes: the pool's covariance from a
+    ``PoolMoments`` (five doubles to the host), ``kde_whiten``, one ``DensityMap.update``.  ``samples``: [n, 2], a host array or a device
+    tensor (taken as fp32).  Returns (zi [nbins, nbins] float64, (vmin, vmax)) with the colour limits draw_kde hands to pcolormesh:
+    (min, max(0.2 max, min))."""
+    import torch
+    if isinstance(samples, torch.Tensor):
+        dev = samples.device if device is None else torch.device(device)
+        x = samples.to(dev, torch.float32).contiguous()
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        x = torch.from_numpy(np.array(samples, dtype=np.float32, order="C")).to(dev)
+    if x.dim() != 2 or x.shape[1] != 2:
+        raise ValueError(f"kde_grid: samples {tuple(x.shape)} are not [n, 2]")
+    n = x.shape[0]
+    if n < 2:
+        raise ValueError(f"kde_grid: a bandwidth needs at least 2 samples, got {n}")
+    _, cov = PoolMoments(2, dev).update(x).mean_cov(ddof=1)
+    whiten, norm = kde_whiten(cov, n, bw_scale)
+    axis = kde_axes(scale, nbins)
+    zi = DensityMap(axis, axis, whiten, dev).update(x).values(norm)
+    lo, hi = float(zi.min()), float(zi.max())
+    return zi, (lo, max(hi * 0.2, lo))

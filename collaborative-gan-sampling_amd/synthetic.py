@@ -283,7 +283,18 @@ def proposer(refiner, generate, discriminator):
     return propose, score
 
 
-def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_batch, centeroids, std, mh_sampler=None, diagnostics=False):
+def landscape_grid(scale, ngrids=21):
+    """The [ngrids^2, 2] float64 grid the reference scores for its critic landscape (synthetic/main.py:318-329): row i * ngrids + j is
+    (-scale + i * step, -scale + j * step), step = 2 scale / (ngrids - 1), each in the reference's order of operations."""
+    step = 2 * scale / (ngrids - 1)
+    axis = -scale + np.arange(ngrids) * step
+    grid = np.zeros((ngrids * ngrids, 2))
+    grid[:, 0], grid[:, 1] = np.repeat(axis, ngrids), np.tile(axis, ngrids)
+    return grid
+
+
+def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_batch, centeroids, std, mh_sampler=None, diagnostics=False,
+                           maps=None):
     """The "shape"-mode evaluation of synthetic/main.py:215-263 on the device refiner: refine the evaluation batch, report its
     quality, then D-score -> MH fill (thinning T = 20, chain seeded with mean(real_sigmoid)) until ``len(eval_batch)`` samples
     are accepted (proposal counter advancing only for productive batches, :251) and report the collaborative sample's
@@ -293,11 +304,18 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
     ``diagnostics=True``: D's scores of ``eval_batch`` (label 0) and ``target_batch`` (label 1) go into a ``metrics.CalibrationStats``
     as in synthetic/main.py:115-123 and the result gains "calibration" (``metrics.calibration_diagnostics``: the row's z_dawid brier ece
     mce, computed in double where the reference's fp32 arrays give fp32 sums); the pools' quality then comes from ``metrics.ModeStats``
-    on the device, the pools taken as fp32.  Draws, samples and ``eff`` are those of ``diagnostics=False``."""
+    on the device, the pools taken as fp32.  Draws, samples and ``eff`` are those of ``diagnostics=False``.
+    ``maps=dict(scale=region, nbins=100, grid_scale=..., ngrids=21)``: what the reference's ``--eval_type full`` draws, without the
+    drawing.  The result gains "maps": the [nbins, nbins] float64 density maps (``metrics.kde_grid``, draw_kde of main.py:142,222,256,337)
+    of the pools under "standard", "refinement", "collaborate" and "target", and "landscape": (grid, sigmoid), D's score on
+    ``landscape_grid(grid_scale, ngrids)`` (main.py:115,130,318-333; ``grid_scale`` defaults to ``scale``).  The maps draw nothing from the
+    numpy stream and are made after everything else: every other entry is that of ``maps=None``."""
     from . import metrics as Mx
     from .evaluate import collaborate
     from .sampling import IndependenceSampler
     thres = std * 4
+    if maps is not None and ("scale" not in maps or set(maps) - {"scale", "nbins", "grid_scale", "ngrids"}):      # before any draw
+        raise ValueError(f"maps: needs 'scale', takes 'nbins', 'grid_scale', 'ngrids'; got {sorted(maps)}")
     if diagnostics:
         dev = discriminator.dev
         real_modes = Mx.ModeStats(centeroids, thres, dev).update(_upload(target_batch, dev)).state()
@@ -327,6 +345,12 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
     samples, eff = collaborate(propose, score, mh, len(eval_batch), float(np.mean(real_sigmoid)),
                                base=(refined, score(refined)), count_only_productive=True)      # :229-253
     out["collaborate"] = dict(quality(samples), eff=float(eff))
+    if maps is not None:
+        scale, nbins = maps["scale"], maps.get("nbins", 100)
+        pools = (("standard", eval_batch), ("refinement", refined), ("collaborate", samples), ("target", target_batch))
+        out["maps"] = {name: Mx.kde_grid(pool, scale, nbins, device=discriminator.dev)[0] for name, pool in pools}
+        grid = landscape_grid(maps.get("grid_scale", scale), maps.get("ngrids", 21))
+        out["maps"]["landscape"] = (grid, discriminator.sigmoid_and_saliency(grid, want_saliency=False)[0].cpu().numpy())
     return out
 
 

@@ -617,6 +617,22 @@ size_t cgs_mode_stats_ws_bytes(int n, int k);
 int cgs_mode_stats_accumulate(const float* x, int n, const double* centeroids, int k, double thres, double* state, void* ws, size_t ws_bytes,
                               void* stream);
 
+/* ---- the density map of a 2-D sample pool on a grid, additive, in double on the device (csrc/kde2d.hip) ----
+ * The arithmetic of the reference's draw_kde (sampling/utils_sampling.py:97-112).  x: [n][2] fp32; axis_x: gx fp32 coordinates, axis_y:
+ * gy; whiten: the three doubles w00, w10, w11 of the lower-triangular W = L^-1, C = L L^T the kernel covariance, ON THE DEVICE.  The
+ * call ADDS to state, gx * gy + 1 contiguous doubles:
+ *     [i * gy + j]  sum_k exp(-1/2 |W (g_ij - x_k)|^2),  g_ij = (axis_x[i], axis_y[j])  (UN-normalised)        [gx * gy]  n
+ * The density is state[i * gy + j] / (state[gx * gy] * 2 pi sqrt(det C)), sqrt(det C) = 1 / (w00 w11): the reader's division.  Per pair
+ * the difference of the raw fp32 coordinates is taken first and whitened after, in fp32, through v_exp_f32; fp32 sums run over at most
+ * 128 samples and are then added in double.  The samples are cut into slices whose number depends on (n, gx * gy) alone, each slice
+ * leaves one double per cell in ws, a second launch adds them in ascending order and then to state: no floating-point atomics, two
+ * calls on the same inputs from the same state end bit-equal.
+ * Errors: gx < 1, gy < 1, gx * gy > 2^20, n < 0 or n > 2^30 is CGS_EINVAL before any launch (the query then returns 0); n == 0 is a no-op
+ * that dereferences nothing (query 0); ws: cgs_kde2d_ws_bytes(n, gx, gy) bytes, 8-byte aligned, CGS_EWORKSPACE if smaller. */
+size_t cgs_kde2d_ws_bytes(int n, int gx, int gy);
+int cgs_kde2d_accumulate(const float* x, int n, const float* axis_x, int gx, const float* axis_y, int gy, const double* whiten, double* state,
+                         void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
