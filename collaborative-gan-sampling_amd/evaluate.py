@@ -120,17 +120,19 @@ class FusedProposer:
             self.feat_width = self.engines[0].feature_width()
             self.feat_dev = [torch.empty((n, self.feat_width), dtype=torch.float32, device=self.dev) for _ in range(depth)]
         self.depth, self.launched = depth, 0
+        self.img_dev = [None] * depth              # the engine's own image buffer of the slot's latest round (valid until the slot is launched again)
         self.indices = None
         if mode == "probabilistic":      # the reference bakes ONE draw of size batch_size into the graph, for every batch (collaborator.py:54-56)
             one = np.asarray(indices) if indices is not None else np.random.randint(steps + 1, size=self.b)
             self.indices = np.tile(one, self.G)
 
-    def launch(self, z, refine=True, calibration=None):
+    def launch(self, z, refine=True, calibration=None, to_host=True):
         """Queue one round on the next slot: z [G*b, z_dim] (host array) -> images + sigmoids in the slot's pinned buffers.
         ``refine=False``: the standard samples instead (fake_images / fake_sigmoids, nsgan/GAN.py:153-155).  Returns the slot.
         ``calibration`` (a metrics.CalibrationStats, optional): the round's sigmoids are added to it with label 0 on the slot's stream,
         from the device buffer the scoring pass wrote -- with ``refine=False`` the ``sigmoid_standard`` half of nsgan/GAN.py:287-301;
-        nothing more is copied to the host."""
+        nothing more is copied to the host.  ``to_host=False``: neither images nor sigmoids are copied to the pinned buffers (``result`` then
+        only waits); the round is read on the device, from ``img_dev[slot]`` / ``sig_dev[slot]`` (``reject_fill_fused``)."""
         torch = self.torch
         k = self.launched % self.depth
         self.launched += 1
@@ -143,12 +145,15 @@ class FusedProposer:
                 img = e.refine_from_z(self.z_dev[k], self.steps, self.rate, method=self.method, **kw)[0]
             else:
                 img = e.generate(self.z_dev[k])
-            self.img_host[k].copy_(img, non_blocking=True)        # (before score(): D's forward re-uses no G buffer, but keep the order plain)
+            self.img_dev[k] = img
+            if to_host:
+                self.img_host[k].copy_(img, non_blocking=True)    # (before score(): D's forward re-uses no G buffer, but keep the order plain)
             if self.feat_dev is not None:
                 e.score_with_features(img, out=self.sig_dev[k], feat_out=self.feat_dev[k])
             else:
                 e.score(img, out=self.sig_dev[k])
-            self.sig_host[k].copy_(self.sig_dev[k], non_blocking=True)
+            if to_host:
+                self.sig_host[k].copy_(self.sig_dev[k], non_blocking=True)
             self.done[k].record(st)
             if calibration is not None:                           # (behind ``done``: result(k) does not wait for it)
                 calibration.update(self.sig_dev[k], 0)
@@ -311,6 +316,185 @@ def collaborate_fused(proposer, mh_sampler, eval_size, real_sigmoid_mean, base=N
         stats.update(rounds=rounds, proposed=cnt_propose - eval_size, host_chain_s=t_chain, device_wait_s=t_wait,
                      discarded_batches=drawn - (cnt_propose - eval_size) // b)
     return out, cnt / cnt_propose
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The DRS leg of the evaluation (nsgan/GAN.py:311-346, synthetic/main.py:149-169): the same fill loop with the Rejector in the chain's place.
+def reject_fill(propose, score, rejector, eval_size, real_sigmoid_max, base=None, min_efficiency=None, count_only_productive=False,
+                shift_percent=100.0, epsilon=1e-8, max_rounds=100000):
+    """Fill ``eval_size`` samples by discriminator rejection sampling: the counterpart of ``collaborate``.
+
+    propose()            -> a batch of standard samples as ndarray [B, ...]      (fake_images / gan.generates)
+    score(batch)         -> discriminator sigmoids [B, 1]                        (fake_sigmoids)
+    rejector             -> a ``sampling.Rejector``; its bound is seeded with ``real_sigmoid_max`` (np.amax(sigmoid_real), GAN.py:314)
+    base                 -> optional (samples, sigmoids) for the first pass (the standard evaluation set, GAN.py:315, main.py:153)
+    min_efficiency       -> GAN.py:283,323: once proposals exceed eval_size / min_efficiency, stop rejecting and take whole batches
+    count_only_productive-> main.py:163-169: the proposal counter only advances for batches that yielded samples
+    shift_percent        -> 100.0 at every call site of the reference
+    One deliberate difference: GAN.py:326 stores a batch's accepted rows only when something had been accepted before, which leaves
+    rows of np.empty garbage in the evaluation set while the counter moves on.  The rows are stored always here: uninitialised memory
+    defines no parity.
+    Returns (samples [eval_size, ...], efficiency = accepted / proposed)."""
+    out, cnt, cnt_propose = None, 0, eval_size
+    rejector.set_score_max(real_sigmoid_max)
+    if base is not None:
+        acc = rejector.sampling(base[0], base[1], epsilon=epsilon, shift_percent=shift_percent)
+        if acc.shape[0] > 0:
+            out = np.empty((eval_size,) + acc.shape[1:], dtype=acc.dtype)
+            k = min(acc.shape[0], eval_size)
+            out[:k] = acc[:k]
+        cnt = acc.shape[0]
+    max_propose = eval_size / min_efficiency if min_efficiency else float("inf")
+    rounds = 0
+    while cnt < eval_size:
+        rounds += 1
+        if rounds > max_rounds:
+            raise RuntimeError("reject_fill: no sample accepted in %d rounds" % max_rounds)
+        batch = propose()
+        B = batch.shape[0]
+        if out is None:
+            out = np.empty((eval_size,) + batch.shape[1:], dtype=np.float32)
+        if cnt_propose < max_propose:
+            acc = rejector.sampling(batch, score(batch), epsilon=epsilon, shift_percent=shift_percent)
+            n = acc.shape[0]
+            if n > 0:
+                k = min(n, eval_size - cnt)
+                out[cnt:cnt + k] = acc[:k]
+            cnt += n
+            if n > 0 or not count_only_productive:
+                cnt_propose += B
+        else:                                                                       # too inefficient: take the batch as is
+            k = min(B, eval_size - cnt)
+            out[cnt:cnt + k] = batch[:k]
+            cnt += B
+            cnt_propose += B
+    return out, cnt / cnt_propose
+
+
+def reject_fill_fused(proposer, rejector, eval_size, real_sigmoid_max, base=None, min_efficiency=None, shift_percent=100.0, epsilon=1e-8,
+                      max_rounds=100000, stats=None, moments=None, calibration=None):
+    """``reject_fill`` (count_only_productive=False: the nsgan form, nsgan/GAN.py:311-346) over a ``FusedProposer`` and a
+    ``sampling.DeviceRejector``: G logical batches of standard samples per round (``launch(..., refine=False)``), the accept decision
+    and the compaction queued on the slot's stream behind the round, the pool on the device from start to end.  Per round the host
+    receives the G accept counts and nothing else; no image, accepted or rejected, is copied to it.
+    ``real_sigmoid_max``: a device tensor of the real scores (reduced on the device) or a host scalar / array.
+    ``base``: (samples, sigmoids) of the standard evaluation set, device tensors or host arrays, decided as ONE batch (GAN.py:315);
+    with ``moments`` it must be (samples, sigmoids, features).
+    ``moments`` (a metrics.PoolMoments; needs ``FusedProposer(features=True)``) / ``calibration`` (a metrics.CalibrationStats): D's
+    features / scores of exactly the rows of the returned pool are compacted beside it and added once, from the device, at the end
+    (the scores with label 0).
+    Returns (pool: device fp32 tensor [eval_size, ...], efficiency) -- the rows, their order, the efficiency, ``rejector.D_tilde_M``
+    and the global numpy stream afterwards are those of ``reject_fill`` with a host ``Rejector`` fed the same scores one batch at a time."""
+    import time
+    import torch
+    if moments is not None:
+        if proposer.feat_dev is None:
+            raise ValueError("reject_fill_fused(moments=...) needs FusedProposer(features=True)")
+        if base is not None and len(base) != 3:
+            raise ValueError("reject_fill_fused(moments=...): base must carry features too, as (samples, sigmoids, features)")
+    b, G, dev = proposer.b, proposer.G, proposer.dev
+    n = b * G
+
+    def on_device(x):
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        return t.to(dev, torch.float32).contiguous()
+
+    pool = feat_pool = sig_pool = None
+
+    def pools_for(rows_like):
+        nonlocal pool, feat_pool, sig_pool
+        if pool is None:
+            pool = torch.empty((eval_size,) + tuple(rows_like.shape[1:]), dtype=torch.float32, device=dev)
+            if moments is not None:
+                feat_pool = torch.empty((eval_size, proposer.feat_width), dtype=torch.float32, device=dev)
+            if calibration is not None:
+                sig_pool = torch.empty((eval_size, 1), dtype=torch.float32, device=dev)
+
+    def compact_all(imgs, sigs, feats, offset, take_all=None):
+        rejector.compact(imgs, pool, offset, take_all)
+        if feat_pool is not None:
+            rejector.compact(feats, feat_pool, offset, take_all)
+        if sig_pool is not None:
+            rejector.compact(sigs, sig_pool, offset, take_all)
+
+    cnt, cnt_propose = 0, eval_size
+    rejector.set_score_max(real_sigmoid_max)                                           # nsgan/GAN.py:314
+    if base is not None:
+        imgs, sigs = on_device(base[0]), on_device(base[1])
+        pools_for(imgs)
+        _, counts, _ = rejector.decide_device(sigs, None, shift_percent, epsilon, groups=1)     # :315, the whole set as one batch
+        compact_all(imgs, sigs, on_device(base[2]) if moments is not None else None, 0)
+        cnt = int(counts.cpu()[0])
+    chain = torch.cuda.Event()                                                         # (the rounds run on the slots' streams)
+    chain.record(torch.cuda.current_stream(dev))
+    max_propose = eval_size / min_efficiency if min_efficiency else float("inf")
+    t_wait = 0.0
+    drawn = 0                                          # logical batches drawn so far: batch i meets cnt_propose = eval_size + i*b
+    pending = []                                       # rounds in flight: (slot, uniforms per logical batch, RNG state after each)
+
+    def launch_round():
+        nonlocal drawn
+        zs, us, states = [], [], []
+        for _ in range(G):
+            zs.append(np.random.uniform(-1, 1, [b, proposer.zdim]).astype(np.float32))          # nsgan/GAN.py:321
+            through = eval_size + drawn * b < max_propose                                       # :323, known ahead: +b per iteration (:339)
+            us.append(np.random.rand(b) if through else None)                                   # rejector.py:33, one per proposal
+            states.append(np.random.get_state())
+            drawn += 1
+        pending.append((proposer.launch(np.concatenate(zs), refine=False, to_host=False), us, states))
+
+    rounds = 0
+    final_state = None
+    while cnt < eval_size:
+        rounds += 1
+        if rounds > max_rounds:
+            raise RuntimeError("reject_fill_fused: no sample accepted in %d rounds" % max_rounds)
+        while len(pending) < proposer.depth:
+            launch_round()
+        slot, us, states = pending.pop(0)
+        G1 = sum(u is not None for u in us)            # the batches that go through the rejector come first: the counter only grows
+        imgs, sigs = proposer.img_dev[slot], proposer.sig_dev[slot]
+        pools_for(imgs)
+        st = proposer.streams[slot]
+        t0 = time.perf_counter()
+        with torch.cuda.stream(st):                    # (behind the slot's ``done``: the same stream)
+            st.wait_event(chain)                       # the decide + compact before this one, whichever stream it ran on
+            mask = torch.zeros(n, dtype=torch.uint8, device=dev) if G1 < G else None
+            if G1 > 0:
+                m, counts, _ = rejector.decide_device(sigs[:G1 * b], np.concatenate(us[:G1]), shift_percent, epsilon, groups=G1)
+                if mask is None:
+                    mask = m
+                else:
+                    mask[:G1 * b].copy_(m)
+            flags = None if G1 == G else [j >= G1 for j in range(G)]
+            rejector.last_accept = mask
+            compact_all(imgs, sigs, proposer.feat_dev[slot] if moments is not None else None, min(cnt, eval_size), flags)
+            accepted = counts.cpu().numpy() if G1 > 0 else np.zeros(0, dtype=np.int32)          # the round's only read-back
+        t_wait += time.perf_counter() - t0
+        for j in range(G):
+            cnt += int(accepted[j]) if j < G1 else b
+            cnt_propose += b
+            if cnt >= eval_size:
+                final_state = states[j]
+                if j < G1 - 1:                         # the reference's loop stops here: later batches never reach its rejector
+                    with torch.cuda.stream(st):
+                        rejector.rewind_to(j)
+                break
+        chain = torch.cuda.Event()
+        chain.record(st)
+    for slot, _, _ in pending:                         # rounds drawn ahead that the reference's loop never reaches: drained, discarded
+        proposer.result(slot)
+    if final_state is not None:
+        np.random.set_state(final_state)               # the global stream where the one-batch-at-a-time loop leaves it
+    torch.cuda.current_stream(dev).wait_event(chain)
+    if moments is not None:
+        moments.update(feat_pool)
+    if calibration is not None:
+        calibration.update(sig_pool, 0)
+    if stats is not None:
+        stats.update(rounds=rounds, proposed=cnt_propose - eval_size, device_wait_s=t_wait,
+                     discarded_batches=drawn - (cnt_propose - eval_size) // b)
+    return pool, cnt / cnt_propose
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

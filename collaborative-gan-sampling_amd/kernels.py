@@ -1193,3 +1193,96 @@ def kde2d_accumulate(x, axis_x, axis_y, whiten, state):
             raise L.CgsError(f"kde2d_accumulate: unsupported size (n={n}, grid {gx} x {gy})")
         ws = _moments_workspace(need, x.device)
         L.call("cgs_kde2d_accumulate", _ptr(x), n, _ptr(axis_x), gx, _ptr(axis_y), gy, _ptr(whiten), _ptr(state), _ptr(ws), ws.numel() * 8, _stream())
+
+
+# ----------------------------------------------------------------------------- rejection sampling (csrc/drs.hip)
+def _dev_typed(t, name, dtype, shape, device, who):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape and t.device == device):
+        raise L.CgsError(f"{who}: {name} must be a contiguous {dtype} {shape} tensor on {device}")
+
+
+def drs_set_max(sig, state):
+    """state[0] = logit(clip(max sig, 1e-14, 1 - 1e-14)): ``Rejector.set_score_max(np.amax(sig))`` on device scores (fp32, any shape, at
+    least one).  ``state``: float64 [1] on the same device."""
+    _chk(sig, "sig")
+    _f64_dev(state, "state", (1,), sig.device, "drs_set_max")
+    if sig.numel() < 1:
+        raise L.CgsError("drs_set_max: no score")
+    with torch.cuda.device(sig.device):
+        L.call("cgs_drs_set_max", _ptr(sig), sig.numel(), _ptr(state), _stream())
+
+
+def drs_decide(sig, uniforms, state, groups=1, shift_percent=60.0, epsilon=1e-8, want_p=False, want_bounds=False):
+    """The accept decision of ``Rejector.sampling`` for ``groups`` logical batches of device scores ``sig`` (fp32 [n] or [n, 1], n a whole
+    number of groups), as if it had been called once per batch in order (include/cgs_hip.h).  ``uniforms``: float64 [n] on the device;
+    ``state``: float64 [1], the running bound, advanced in place; ``shift_percent``: 0..100 or None.
+    -> (mask uint8 [n], counts int32 [groups], P float64 [n] or None, bounds float64 [groups] or None), all on the device."""
+    _chk(sig, "sig")
+    if not (sig.dim() == 1 or (sig.dim() == 2 and sig.shape[1] == 1)):
+        raise L.CgsError(f"drs_decide: sig must be [n] or [n, 1], got {tuple(sig.shape)}")
+    n, dev = sig.shape[0], sig.device
+    try:
+        groups = operator.index(groups)
+    except TypeError:
+        groups = 0
+    if groups < 1 or n < 1 or n % groups:
+        raise L.CgsError(f"drs_decide: {n} scores are not {groups} whole batches")
+    q = -1.0 if shift_percent is None else float(shift_percent)
+    if shift_percent is not None and not 0.0 <= q <= 100.0:
+        raise L.CgsError(f"drs_decide: shift_percent = {shift_percent} outside [0, 100]")
+    if not float(epsilon) > 0.0:
+        raise L.CgsError(f"drs_decide: epsilon = {epsilon} must be positive")
+    _f64_dev(uniforms, "uniforms", (n,), dev, "drs_decide")
+    _f64_dev(state, "state", (1,), dev, "drs_decide")
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    counts = torch.empty(groups, dtype=torch.int32, device=dev)
+    P = torch.empty(n, dtype=torch.float64, device=dev) if want_p else None
+    bounds = torch.empty(groups, dtype=torch.float64, device=dev) if want_bounds else None
+    b = n // groups
+    with torch.cuda.device(dev):
+        need = int(L.load().cgs_drs_ws_bytes(b, groups))
+        if need == 0:
+            raise L.CgsError(f"drs_decide: unsupported size (b={b}, groups={groups})")
+        ws = _moments_workspace(need, dev)
+        L.call("cgs_drs_decide", _ptr(sig), b, groups, _ptr(uniforms), float(epsilon), q, _ptr(state), _ptr(bounds), _ptr(P), _ptr(mask), _ptr(counts),
+               _ptr(ws), ws.numel() * 8, _stream())
+    return mask, counts, P, bounds
+
+
+def compact_rows(src, mask, dst, offset, take_all=None, total=None):
+    """Copy the rows of ``src`` (device fp32 [n, ...]) whose ``mask`` byte (device uint8 [n]) is set -- or every row of a group flagged in
+    ``take_all`` (device uint8 [groups], n a whole number of groups) -- in ascending order to ``dst[offset], dst[offset + 1], ...``
+    (device fp32 [capacity, ...] of the same row shape); rows past the end of ``dst`` are dropped.
+    -> ``total``: int32 [1] on the device, the unclipped number of selected rows."""
+    _chk(src, "src")
+    _chk(dst, "dst")
+    if src.dim() < 1 or dst.dim() != src.dim() or tuple(dst.shape[1:]) != tuple(src.shape[1:]) or dst.device != src.device:
+        raise L.CgsError(f"compact_rows: dst {tuple(dst.shape)} must hold rows of src {tuple(src.shape)} on {src.device}")
+    n, dev = src.shape[0], src.device
+    row = src.numel() // n if n else max(dst.numel() // max(dst.shape[0], 1), 1)
+    if n and row < 1:
+        raise L.CgsError("compact_rows: empty rows")
+    _dev_typed(mask, "mask", torch.uint8, (n,), dev, "compact_rows")
+    groups = 1
+    if take_all is not None:
+        if not (isinstance(take_all, torch.Tensor) and take_all.dim() == 1 and take_all.shape[0] >= 1):
+            raise L.CgsError("compact_rows: take_all must be a 1-D uint8 device tensor, one flag per group")
+        groups = take_all.shape[0]
+        _dev_typed(take_all, "take_all", torch.uint8, (groups,), dev, "compact_rows")
+        if n % groups:
+            raise L.CgsError(f"compact_rows: {n} rows are not {groups} whole groups")
+    offset = operator.index(offset)
+    if offset < 0:
+        raise L.CgsError(f"compact_rows: offset = {offset} is negative")
+    if total is None:
+        total = torch.empty(1, dtype=torch.int32, device=dev)
+    else:
+        _dev_typed(total, "total", torch.int32, (1,), dev, "compact_rows")
+    with torch.cuda.device(dev):
+        need = int(L.load().cgs_compact_rows_ws_bytes(n)) if n else 0
+        if n and need == 0:
+            raise L.CgsError(f"compact_rows: unsupported size (n={n})")
+        ws = _moments_workspace(max(need, 8), dev)
+        L.call("cgs_compact_rows", _ptr(src), n, row, _ptr(mask), _ptr(take_all), groups, _ptr(dst), offset, dst.shape[0], _ptr(total), _ptr(ws),
+               ws.numel() * 8, _stream())
+    return total

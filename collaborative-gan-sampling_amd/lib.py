@@ -133,6 +133,11 @@ SIGNATURES = {
     "cgs_mode_stats_accumulate": (_i, [_p, _i, _p, _i, C.c_double, _p, _p, _z, _p]),
     "cgs_kde2d_ws_bytes": (_z, [_i, _i, _i]),
     "cgs_kde2d_accumulate": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _z, _p]),
+    "cgs_drs_ws_bytes": (_z, [_i, _i]),
+    "cgs_drs_decide": (_i, [_p, _i, _i, _p, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "cgs_drs_set_max": (_i, [_p, _i, _p, _p]),
+    "cgs_compact_rows_ws_bytes": (_z, [_i]),
+    "cgs_compact_rows": (_i, [_p, _i, _i, _p, _p, _i, _p, _ll, _ll, _p, _p, _z, _p]),
 }
 
 _lib = None

@@ -2,6 +2,7 @@
 from .policy import PolicyAdaptive
 from .rejector import Rejector
 from .idpsampler import IndependenceSampler
+from .device_rejector import DeviceRejector
 from . import collaborator, refiner_cpu
 
-__all__ = ["PolicyAdaptive", "Rejector", "IndependenceSampler", "collaborator", "refiner_cpu"]
+__all__ = ["PolicyAdaptive", "Rejector", "DeviceRejector", "IndependenceSampler", "collaborator", "refiner_cpu"]

@@ -354,6 +354,83 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
     return out
 
 
+def evaluate_calibrated(discriminator, generate, eval_batch, target_batch, centeroids, std, rejector=None, mh_sampler=None, diagnostics=False,
+                        maps=None, keep_pools=False):
+    """The "calibrate"-mode evaluation of synthetic/main.py:137-214: the standard pool's quality, then the two samplers a calibrated D
+    is for.  Rejection (:149-181): a ``sampling.DeviceRejector`` with its bound seeded by max(real_sigmoid) and shift_percent = 100
+    decides the evaluation batch and then fresh generator batches of ``len(eval_batch)`` until that many samples are accepted (the
+    proposal counter advancing only for productive batches, :163-169); scores, decisions, compaction and the pool stay on the device,
+    one count per batch comes back.  Hastings (:182-214): ``evaluate.collaborate`` on UNREFINED proposals with the sampler of
+    main.py:77-81 (``IndependenceSampler(T=20)``), chain seeded with mean(real_sigmoid), the evaluation batch as base.
+    Returns {"standard": {...}, "rejection": {..., "eff"}, "hastings": {..., "eff"}} with the reference's four 2-D metrics
+    (``thres`` = 4 std).  ``generate`` / ``diagnostics`` / ``maps`` as in ``evaluate_collaborative`` (the maps' pools: "standard",
+    "rejection", "hastings", "target"); ``keep_pools=True`` adds "pools": the rejection pool (a device tensor) and the hastings pool.
+    The numpy stream is consumed as the reference consumes it: per rejection batch one uniform per proposal, then the chain's."""
+    from . import metrics as Mx
+    from .evaluate import collaborate
+    from .sampling import DeviceRejector, IndependenceSampler
+    thres = std * 4
+    dev = discriminator.dev
+    if maps is not None and ("scale" not in maps or set(maps) - {"scale", "nbins", "grid_scale", "ngrids"}):      # before any draw
+        raise ValueError(f"maps: needs 'scale', takes 'nbins', 'grid_scale', 'ngrids'; got {sorted(maps)}")
+    if diagnostics:
+        real_modes = Mx.ModeStats(centeroids, thres, dev).update(_upload(target_batch, dev)).state()
+
+    def quality(samples):
+        if diagnostics:
+            return Mx.mode_metrics(Mx.ModeStats(centeroids, thres, dev).update(_upload(samples, dev)).state(), real_modes)
+        if isinstance(samples, torch.Tensor):
+            samples = samples.cpu().numpy()
+        mean_dist, good = Mx.metrics_distance(samples, centeroids, thres)
+        return {"mean_dist": float(mean_dist), "good": float(good),
+                "kl": float(Mx.metrics_diversity(target_batch, samples, centeroids, thres)),
+                "js": float(Mx.metrics_distribution(target_batch, samples, centeroids, thres))}
+    if isinstance(generate, MLPGenerator):                                             # training-mode G on fresh noise, main.py:158-159
+        G, noise, n_gen = generate, NoiseDataset(), len(eval_batch)
+        generate = lambda: G.generate(noise.next_batch(n_gen)).cpu().numpy()
+    sigmoid = lambda x: discriminator.sigmoid_and_saliency(x, want_saliency=False)[0]
+    eval_size = len(eval_batch)
+    eval_dev = _upload(eval_batch, dev)
+    real_sig, eval_sig = sigmoid(target_batch), sigmoid(eval_dev)                      # main.py:116-117
+    out = {"standard": quality(eval_batch)}
+    if diagnostics:                                                                    # :123
+        cal = Mx.CalibrationStats(dev)
+        cal.update(eval_sig, 0)
+        cal.update(real_sig, 1)
+        out["calibration"] = cal.diagnostics()
+    # rejection, :149-169
+    rej = rejector if rejector is not None else DeviceRejector(dev)
+    pool = torch.empty((eval_size, 2), dtype=torch.float32, device=dev)
+    rej.set_score_max(real_sig)                                                        # :152
+    _, counts = rej.decide(eval_sig, shift_percent=100.0)                              # :153
+    rej.compact(eval_dev, pool, 0)
+    cnt, cnt_propose = int(counts[0]), eval_size
+    while cnt < eval_size:
+        extra = _upload(generate(), dev)                                               # :158-159
+        _, counts = rej.decide(sigmoid(extra), shift_percent=100.0)                    # :160-161
+        rej.compact(extra, pool, cnt)
+        if counts[0] > 0:
+            cnt += int(counts[0])
+            cnt_propose += eval_size                                                   # :169 (its own constant, whatever the batch holds)
+    out["rejection"] = dict(quality(pool), eff=float(cnt / cnt_propose))
+    # hastings, :182-202
+    mh = mh_sampler if mh_sampler is not None else IndependenceSampler(T=20)           # main.py:80
+    score = lambda batch: sigmoid(batch).cpu().numpy()
+    real_host, eval_host = real_sig.cpu().numpy(), eval_sig.cpu().numpy()
+    samples, eff = collaborate(generate, score, mh, eval_size, float(np.mean(real_host)), base=(eval_batch, eval_host),
+                               count_only_productive=True)
+    out["hastings"] = dict(quality(samples), eff=float(eff))
+    if keep_pools:
+        out["pools"] = {"rejection": pool, "hastings": samples}
+    if maps is not None:
+        scale, nbins = maps["scale"], maps.get("nbins", 100)
+        pools = (("standard", eval_batch), ("rejection", pool.cpu().numpy()), ("hastings", samples), ("target", target_batch))
+        out["maps"] = {name: Mx.kde_grid(p, scale, nbins, device=dev)[0] for name, p in pools}
+        grid = landscape_grid(maps.get("grid_scale", scale), maps.get("ngrids", 21))
+        out["maps"]["landscape"] = (grid, sigmoid(grid).cpu().numpy())
+    return out
+
+
 def _bn_name(k):
     """tf.contrib.layers.batch_norm's default scopes in creation order: BatchNorm, BatchNorm_1, ..."""
     return "generator/BatchNorm" if k == 0 else f"generator/BatchNorm_{k}"

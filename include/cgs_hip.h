@@ -633,6 +633,35 @@ size_t cgs_kde2d_ws_bytes(int n, int gx, int gy);
 int cgs_kde2d_accumulate(const float* x, int n, const float* axis_x, int gx, const float* axis_y, int gy, const double* whiten, double* state,
                          void* ws, size_t ws_bytes, void* stream);
 
+/* ---- discriminator rejection sampling on the device (csrc/drs.hip) ----
+ * cgs_drs_decide: the accept decision of the reference's Rejector (sampling/rejector.py:16-34: acceptance_probability and sampling), once
+ * per logical batch.  sig: groups * b fp32 sigmoids, group g = rows [g b, (g + 1) b); uniforms: one double per row ON THE DEVICE (the
+ * host draws them: np.random.rand(b) per group, in group order); state: one double on the device, the running bound D_tilde_M.  Per
+ * group, in order, as if rejector.sampling had been called once per batch:
+ *     d = logit(clip(double(s), 1e-14, 1 - 1e-14))          M_g = max(M_{g-1}, max d)   (M_{-1} = *state; *state leaves as M_{groups-1})
+ *     F = (d - M_g) - log(1 - exp((d - M_g) - epsilon))     gamma = percentile(F over the group, shift_percent), numpy's linear method
+ *     P = 1 / (1 + exp(-(F - gamma)))                       mask = uniforms < P                   counts[g] = rows of the group accepted
+ * shift_percent in [0, 100], or any negative value for the reference's shift_percent=None (gamma = 0).  The two order statistics behind
+ * gamma come from an exact radix select; every operation is a separately rounded double one in the reference's order (1 - exp(x), not
+ * -expm1(x)), logit in scipy.special's form.  bounds (NULL or groups doubles): M_g per group; P (NULL or one double per row); mask: one
+ * byte per row, 0 or 1; counts: groups ints.  No floating-point atomics: a rerun from the same state is bit-equal.  A NaN score is not
+ * supported.  ws: cgs_drs_ws_bytes(b, groups) bytes, 8-byte aligned, CGS_EWORKSPACE if smaller; b < 1, groups < 1 or > 2^20,
+ * b * groups > 2^30, shift_percent > 100 or NaN, epsilon <= 0: CGS_EINVAL before any launch (the query then returns 0).
+ * cgs_drs_set_max: *state = logit(clip(max of the n scores)) (rejector.py:11-14 on np.amax(sigmoid_real), nsgan/GAN.py:314).
+ * cgs_compact_rows: the stable compaction behind eval_reject[cnt:cnt + k] = batch[accept] (nsgan/GAN.py:324-338, synthetic/main.py:161-167).
+ * src: [n][row] fp32; the rows i with mask[i] != 0, or every row of group i / (n / groups) if take_all (NULL or groups bytes) flags it (the
+ * "too inefficient" branch, GAN.py:332-338), are copied in ascending order of i to dst[offset + k], k = 0, 1, ...; rows with
+ * offset + k >= capacity are dropped (dst: at least capacity rows); *total (a device int) = the UNCLIPPED number of selected rows.  n == 0
+ * writes *total = 0 and nothing else.  ws: cgs_compact_rows_ws_bytes(n) bytes, 4-byte aligned.  n outside [0, 2^30] or no whole number of
+ * groups, row outside [1, 2^22], n * row > 2^40, offset < 0, capacity < 0: CGS_EINVAL before any launch. */
+size_t cgs_drs_ws_bytes(int b, int groups);
+int cgs_drs_decide(const float* sig, int b, int groups, const double* uniforms, double epsilon, double shift_percent, double* state, double* bounds,
+                   double* P, unsigned char* mask, int* counts, void* ws, size_t ws_bytes, void* stream);
+int cgs_drs_set_max(const float* sig, int n, double* state, void* stream);
+size_t cgs_compact_rows_ws_bytes(int n);
+int cgs_compact_rows(const float* src, int n, int row, const unsigned char* mask, const unsigned char* take_all, int groups, float* dst, long long offset,
+                     long long capacity, int* total, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
