@@ -34,10 +34,23 @@ def rel_err(out, ref):
     return ((host(out) - ref).abs().max() / ref.abs().max()).item()
 
 
-@pytest.mark.parametrize("B", [2, 7, 1000, 10000])
+# gen_plan's edges (<= 256 waves of >= 8 contiguous samples, none empty): B = 9 -> waves of 5 and 4; B = 2041 -> 256 waves of 8, the last
+# with ONE sample (its M2 partial is 0, its mean sum / 1); B = 2049, just past the cap -> chunk 9 and 228 waves
+@pytest.mark.parametrize("B", [2, 7, 1000, 10000, 9, 2041, 2049])
 def test_training_forward_and_moving_averages_vs_float64(B):
+    check_training_forward(B, 64, 6)
+
+
+@pytest.mark.parametrize("nhidden,nlayers,B", [(1, 2, 9), (63, 3, 2041), (7, 6, 2049), (1, 2, 2041)])
+def test_training_forward_on_padded_and_shallow_nets(nhidden, nlayers, B):
+    """lane < nh throughout the generator kernels, at one unit, at 63 and at 7; no hidden -> hidden layer at nlayers = 2.  Same float64
+    reference and bars as the 64 x 6 cases."""
+    check_training_forward(B, nhidden, nlayers)
+
+
+def check_training_forward(B, nhidden, nlayers):
     from cgs_amd.synthetic import MLPGenerator, _bn_name
-    P = perturbed_params(B)
+    P = perturbed_params(B, nhidden, nlayers)
     G = MLPGenerator(P, DEV)
     Q = R.to_torch(P, torch.float64)
     rs = np.random.RandomState(B)
@@ -79,7 +92,8 @@ def test_bessel_rule_is_the_recorded_one():
     np.testing.assert_allclose(G.moving_variance[0].cpu().numpy(), 0.1 * 2 * st[0, 1].cpu().numpy(), rtol=1e-6, atol=1e-12)
 
 
-@pytest.mark.parametrize("nhidden,nlayers,B", [(64, 6, 1000), (16, 3, 37)])
+# (one unit at B = 2041, not at B = 9: with these seeds no sample of 9 passes the unit's ReLU, and every gradient below it is exactly zero)
+@pytest.mark.parametrize("nhidden,nlayers,B", [(64, 6, 1000), (16, 3, 37), (64, 6, 9), (64, 6, 2041), (64, 6, 2049), (1, 2, 2041), (63, 3, 2049), (7, 6, 9)])
 def test_g_step_vs_float64_autograd(nhidden, nlayers, B):
     from cgs_amd.synthetic import GStep, MLPGenerator
     P = perturbed_params(11, nhidden, nlayers)

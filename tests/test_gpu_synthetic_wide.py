@@ -12,6 +12,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from mlp2d_cases import ref64          # the float64 forward / backward and the rows near a ReLU kink, stated once for both widths
 from oracle import sampling_ref as S
 
 DEV = "cuda:0"
@@ -25,27 +26,6 @@ def _net(nh, nl, seed, scale):
 def _D(Ws, bs):
     from cgs_amd.synthetic import MLPDiscriminator
     return MLPDiscriminator.from_lists(Ws, bs, DEV)
-
-
-def ref64(Ws, bs, x):
-    """float64 forward, ReLU masks and backward of the float32 weights -> (sigmoid [B], saliency [B,2] with the 1/B factor, near [B]);
-    near[b]: some pre-activation of row b lies within 1e-6 max|z| (max over its layer) of zero -- a rounding may take the other ReLU
-    branch there, which changes one gradient path discretely whatever computes it."""
-    W = [w.astype(np.float64) for w in Ws]
-    b = [v.astype(np.float64) for v in bs]
-    h = np.asarray(x, np.float64)
-    zs, near = [], np.zeros(len(h), bool)
-    for i in range(len(W) - 1):
-        z = h @ W[i] + b[i]
-        near |= (np.abs(z) < 1e-6 * np.abs(z).max()).any(axis=1)
-        zs.append(z)
-        h = np.maximum(z, 0.0)
-    logit = (h @ W[-1] + b[-1])[:, 0]
-    g = np.broadcast_to(W[-1][:, 0], h.shape).copy()
-    for i in range(len(W) - 2, -1, -1):
-        g = (g * (zs[i] > 0)) @ W[i].T
-    sig = 1.0 / (1.0 + np.exp(-logit))
-    return sig, (sig - 1.0)[:, None] * g / len(h), near
 
 
 def _check_vs(sig, sal, want_sig, want_sal, keep, tag):

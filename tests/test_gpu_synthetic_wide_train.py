@@ -37,7 +37,7 @@ def _D(Ws, bs):
 def ref64(Ws, bs, real, fake):
     """float64 forward, ReLU masks, backward and h^T d sums of the float32 weights for
     d_loss = mean BCE(D(real), 1) + mean BCE(D(fake), 0) -> ((loss_real, loss_fake), [dW...], [db...], near [Br + Bf]);
-    near[b]: some pre-activation of row b lies within 1e-6 max|z| (max over its layer) of zero (ref64 of test_gpu_synthetic_wide.py)."""
+    near[b]: some pre-activation of row b lies within 1e-6 max|z| (max over its layer) of zero (ref64 of mlp2d_cases.py)."""
     W = [w.astype(np.float64) for w in Ws]
     b = [v.astype(np.float64) for v in bs]
     Br, Bf = len(real), len(fake)
