@@ -498,7 +498,128 @@ def reject_fill_fused(proposer, rejector, eval_size, real_sigmoid_max, base=None
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# The reference's log rows.  ``diag``: a dict with z_dawid / brier / ece / mce (metrics.calibration_diagnostics).
+# The Metropolis-Hastings legs with the chain on the device (nsgan/GAN.py:348-376 hastings, :398-426 collaborate).
+def hastings_fill_fused(proposer, sampler, eval_size, real_sigmoid_mean, base=None, refine=True, min_efficiency=None, max_rounds=100000,
+                        stats=None, moments=None, calibration=None):
+    """``collaborate`` (count_only_productive=False: the nsgan form) over a ``FusedProposer`` and a ``sampling.DeviceIndependenceSampler``:
+    G logical batches per round (``launch(..., refine=refine, to_host=False)``: ``refine=True`` is the collaborate leg, GAN.py:398-426,
+    ``refine=False`` the hastings leg on standard samples, :348-376), the chain's walk and the gather of the emitted rows queued on the
+    slot's stream behind the round, the pool on the device from start to end.  The chain state is shared by the slots' streams, so the
+    walks are ordered by events in round order; a round queued ahead of the one that fills the pool finds the pool full and leaves the
+    chain untouched, as the reference's loop, which never reaches it, would.  Per round the host receives the G counts and nothing else.
+    z and the uniforms are drawn on the host in the reference's order, exactly as ``collaborate_fused`` draws them.
+    ``real_sigmoid_mean``: a Python float, an ``np.float32`` or a 1-element fp32 device tensor (``sampler.set_score_curr``).
+    ``base``: (samples, sigmoids) for the first pass, device tensors or host arrays, walked as ONE batch (GAN.py:351,402); with
+    ``moments`` it must be (samples, sigmoids, features).
+    ``moments`` (a metrics.PoolMoments; needs ``FusedProposer(features=True)``) / ``calibration`` (a metrics.CalibrationStats): D's
+    features / scores of exactly the rows of the returned pool are gathered beside it and added once, from the device, at the end (the
+    scores with label 0).
+    Returns (pool: device fp32 tensor [eval_size, ...], efficiency) -- the rows, their order, the efficiency, the sampler's final
+    ``d_curr`` and ``cnt_chain`` and the global numpy stream afterwards are those of ``collaborate`` with a host ``IndependenceSampler``
+    fed the same scores one batch at a time."""
+    import time
+    import torch
+    if moments is not None:
+        if proposer.feat_dev is None:
+            raise ValueError("hastings_fill_fused(moments=...) needs FusedProposer(features=True)")
+        if base is not None and len(base) != 3:
+            raise ValueError("hastings_fill_fused(moments=...): base must carry features too, as (samples, sigmoids, features)")
+    b, G, dev = proposer.b, proposer.G, proposer.dev
+
+    def on_device(x):
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        return t.to(dev, torch.float32).contiguous()
+
+    pool = torch.empty((eval_size,) + tuple(proposer.engines[0].A["img"]), dtype=torch.float32, device=dev)
+    feat_pool = torch.empty((eval_size, proposer.feat_width), dtype=torch.float32, device=dev) if moments is not None else None
+    sig_pool = torch.empty((eval_size, 1), dtype=torch.float32, device=dev) if calibration is not None else None
+    fill = torch.zeros(1, dtype=torch.int64, device=dev)               # rows the pool has received, unclipped; the walks advance it
+
+    def walk_and_gather(imgs, sigs, feats, uniforms, groups, take_all):
+        rows, counts, span = sampler.walk_device(sigs, uniforms, groups, take_all, fill, eval_size)
+        sampler.gather(imgs, pool, span, rows)
+        if feat_pool is not None:
+            sampler.gather(feats, feat_pool, span, rows)
+        if sig_pool is not None:
+            sampler.gather(sigs, sig_pool, span, rows)
+        return counts
+
+    cnt, cnt_propose = 0, eval_size
+    sampler.set_score_curr(real_sigmoid_mean)                                          # nsgan/GAN.py:350,401
+    if base is not None:
+        imgs, sigs = on_device(base[0]), on_device(base[1])
+        if tuple(imgs.shape[1:]) != tuple(pool.shape[1:]):
+            raise ValueError(f"hastings_fill_fused: base samples {tuple(imgs.shape)} are not rows of the proposer's {tuple(pool.shape[1:])}")
+        counts = walk_and_gather(imgs, sigs, on_device(base[2]) if moments is not None else None, None, 1, None)      # :351,402
+        cnt = int(counts.cpu()[0])
+    chain = torch.cuda.Event()                                                         # (the rounds run on the slots' streams)
+    chain.record(torch.cuda.current_stream(dev))
+    max_propose = eval_size / min_efficiency if min_efficiency else float("inf")
+    t_wait = t_chain = 0.0
+    drawn = 0                                          # logical batches drawn so far: batch i meets cnt_propose = eval_size + i*b
+    pending = []                                       # rounds in flight: (slot, device counts, RNG state after each logical batch)
+
+    def launch_round():
+        nonlocal drawn, chain
+        zs, us, flags, states = [], [], [], []
+        for _ in range(G):
+            zs.append(np.random.uniform(-1, 1, [b, proposer.zdim]).astype(np.float32))          # nsgan/GAN.py:355,408
+            through_chain = eval_size + drawn * b < max_propose                                 # :357,410, known ahead: +b per iteration
+            us.append(np.random.uniform(0, 1, size=b) if through_chain else np.zeros(b))        # idpsampler.py:50, one per proposal
+            flags.append(not through_chain)
+            states.append(np.random.get_state())
+            drawn += 1
+        st = proposer.streams[proposer.launched % proposer.depth]
+        with torch.cuda.stream(st):                    # (uploaded while the slot's stream is idle: a copy from pageable memory waits for the stream)
+            u_dev = torch.from_numpy(np.concatenate(us)).to(dev)
+            flags_dev = torch.from_numpy(np.asarray(flags, dtype=np.uint8)).to(dev) if any(flags) else None
+        slot = proposer.launch(np.concatenate(zs), refine=refine, to_host=False)
+        with torch.cuda.stream(st):                    # (behind the slot's ``done``: the same stream)
+            st.wait_event(chain)                       # the walk before this one, whichever stream it ran on: the chain state is shared
+            counts = walk_and_gather(proposer.img_dev[slot], proposer.sig_dev[slot], proposer.feat_dev[slot] if moments is not None else None,
+                                     u_dev, G, flags_dev)
+            chain = torch.cuda.Event()
+            chain.record(st)
+        pending.append((slot, counts, states))
+
+    rounds = 0
+    final_state = None
+    while cnt < eval_size:
+        rounds += 1
+        if rounds > max_rounds:
+            raise RuntimeError("hastings_fill_fused: no sample accepted in %d rounds" % max_rounds)
+        while len(pending) < proposer.depth:
+            launch_round()
+        slot, counts, states = pending.pop(0)
+        t0 = time.perf_counter()
+        with torch.cuda.stream(proposer.streams[slot]):
+            emitted = counts.cpu().numpy()                                             # the round's only read-back
+        t1 = time.perf_counter()
+        t_wait += t1 - t0
+        for j in range(G):
+            cnt += int(emitted[j])                     # (never -1 here: the pool was not full when this batch was reached)
+            cnt_propose += b
+            if cnt >= eval_size:
+                final_state = states[j]
+                break
+        t_chain += time.perf_counter() - t1
+    for slot, _, _ in pending:                         # rounds drawn ahead that the reference's loop never reaches: walked by nobody, drained
+        proposer.result(slot)
+    if final_state is not None:
+        np.random.set_state(final_state)               # the global stream where the one-batch-at-a-time loop leaves it
+    torch.cuda.current_stream(dev).wait_event(chain)
+    if moments is not None:
+        moments.update(feat_pool)
+    if calibration is not None:
+        calibration.update(sig_pool, 0)
+    if stats is not None:
+        stats.update(rounds=rounds, proposed=cnt_propose - eval_size, host_chain_s=t_chain, device_wait_s=t_wait,
+                     discarded_batches=drawn - (cnt_propose - eval_size) // b)
+    return pool, cnt / cnt_propose
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The reference's log rows. ``diag``: a dict with z_dawid / brier / ece / mce (metrics.calibration_diagnostics).
 def row_nsgan(ckpt, it, cs, fd, eff, diag):
     """One line of GAN.write (nsgan/GAN.py:493-497): ckpt iter CS FD eff z_dawid brier ece mce."""
     return "%d    %d    %.4f    %.4f    %.4f    %.4f    %.4f    %.4f    %.4f\r\n" % (

@@ -1286,3 +1286,76 @@ def compact_rows(src, mask, dst, offset, take_all=None, total=None):
         L.call("cgs_compact_rows", _ptr(src), n, row, _ptr(mask), _ptr(take_all), groups, _ptr(dst), offset, dst.shape[0], _ptr(total), _ptr(ws),
                ws.numel() * 8, _stream())
     return total
+
+
+# ----------------------------------------------------------------------------- Metropolis-Hastings independence chain (csrc/mh.hip)
+MH_NO_CAPACITY = 1 << 62
+
+
+def mh_walk(sig, uniforms, state, T, B=0, groups=1, take_all=None, fill=None, capacity=None):
+    """``IndependenceSampler.walk`` for ``groups`` logical batches of device scores ``sig`` (fp32 [n] or [n, 1], n a whole number of
+    groups), as if it had been called once per batch in order (include/cgs_hip.h).  ``uniforms``: float64 [n] on the device; ``state``:
+    float64 [2], d and cnt, advanced in place; ``take_all``: None or uint8 [groups] on the device, the batches listed whole instead of
+    walked; ``fill``: int64 [1] on the device, the unclipped number of rows the pool has received, advanced in place, with ``capacity``
+    the pool's rows: a batch that starts with fill >= capacity is not walked (count -1).  Without both it is a plain walk.
+    -> (rows int32 [n]: indices into sig's rows in emission order, counts int32 [groups], span int64 [2]: fill at entry and the number
+    of rows listed), all on the device."""
+    _chk(sig, "sig")
+    if not (sig.dim() == 1 or (sig.dim() == 2 and sig.shape[1] == 1)):
+        raise L.CgsError(f"mh_walk: sig must be [n] or [n, 1], got {tuple(sig.shape)}")
+    n, dev = sig.shape[0], sig.device
+    try:
+        groups, T, B = operator.index(groups), operator.index(T), operator.index(B)
+    except TypeError:
+        raise L.CgsError("mh_walk: groups, T and B must be integers") from None
+    if groups < 1 or n < 1 or n % groups:
+        raise L.CgsError(f"mh_walk: {n} scores are not {groups} whole batches")
+    if T < 0 or B < 0 or T >= 1 << 31 or B >= 1 << 31:
+        raise L.CgsError(f"mh_walk: T = {T} and B = {B} must be in [0, 2^31)")
+    _f64_dev(uniforms, "uniforms", (n,), dev, "mh_walk")
+    _f64_dev(state, "state", (2,), dev, "mh_walk")
+    if take_all is not None:
+        _dev_typed(take_all, "take_all", torch.uint8, (groups,), dev, "mh_walk")
+    if (fill is None) != (capacity is None):
+        raise L.CgsError("mh_walk: fill and capacity come together")
+    if fill is None:
+        fill, capacity = torch.zeros(1, dtype=torch.int64, device=dev), MH_NO_CAPACITY
+    else:
+        _dev_typed(fill, "fill", torch.int64, (1,), dev, "mh_walk")
+        capacity = operator.index(capacity)
+        if capacity < 0:
+            raise L.CgsError(f"mh_walk: capacity = {capacity} is negative")
+    rows = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.empty(groups, dtype=torch.int32, device=dev)
+    span = torch.empty(2, dtype=torch.int64, device=dev)
+    b = n // groups
+    with torch.cuda.device(dev):
+        need = int(L.load().cgs_mh_ws_bytes(b, groups))
+        if need == 0:
+            raise L.CgsError(f"mh_walk: unsupported size (b={b}, groups={groups})")
+        ws = _moments_workspace(need, dev)
+        L.call("cgs_mh_walk", _ptr(sig), b, groups, _ptr(uniforms), T, B, _ptr(take_all), _ptr(state), _ptr(fill), capacity, _ptr(rows), _ptr(counts),
+               _ptr(span), _ptr(ws), ws.numel() * 8, _stream())
+    return rows, counts, span
+
+
+def gather_rows(src, rows, span, dst):
+    """``dst[span[0] + k] = src[rows[k]]`` for k < span[1]: ``src`` device fp32 [n, ...], ``rows`` device int32 [m] (a row may repeat; an
+    index outside [0, n) copies nothing), ``span`` device int64 [2], ``dst`` device fp32 [capacity, ...] of the same row shape; rows past
+    the end of ``dst`` are dropped.  ``rows`` and ``span`` are what ``mh_walk`` returns."""
+    _chk(src, "src")
+    _chk(dst, "dst")
+    if src.dim() < 1 or dst.dim() != src.dim() or tuple(dst.shape[1:]) != tuple(src.shape[1:]) or dst.device != src.device:
+        raise L.CgsError(f"gather_rows: dst {tuple(dst.shape)} must hold rows of src {tuple(src.shape)} on {src.device}")
+    n, dev = src.shape[0], src.device
+    if not (isinstance(rows, torch.Tensor) and rows.dim() == 1):
+        raise L.CgsError("gather_rows: rows must be a 1-D int32 device tensor")
+    _dev_typed(rows, "rows", torch.int32, (rows.shape[0],), dev, "gather_rows")
+    _dev_typed(span, "span", torch.int64, (2,), dev, "gather_rows")
+    if n == 0 or rows.shape[0] == 0 or dst.shape[0] == 0:
+        return
+    row = src.numel() // n
+    if row < 1:
+        raise L.CgsError("gather_rows: empty rows")
+    with torch.cuda.device(dev):
+        L.call("cgs_gather_rows", _ptr(src), n, row, _ptr(rows), rows.shape[0], _ptr(span), _ptr(dst), dst.shape[0], _stream())

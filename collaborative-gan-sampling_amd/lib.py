@@ -138,6 +138,9 @@ SIGNATURES = {
     "cgs_drs_set_max": (_i, [_p, _i, _p, _p]),
     "cgs_compact_rows_ws_bytes": (_z, [_i]),
     "cgs_compact_rows": (_i, [_p, _i, _i, _p, _p, _i, _p, _ll, _ll, _p, _p, _z, _p]),
+    "cgs_mh_ws_bytes": (_z, [_i, _i]),
+    "cgs_mh_walk": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _ll, _p, _p, _p, _p, _z, _p]),
+    "cgs_gather_rows": (_i, [_p, _i, _i, _p, _i, _p, _p, _ll, _p]),
 }
 
 _lib = None

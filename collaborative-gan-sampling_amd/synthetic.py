@@ -293,8 +293,33 @@ def landscape_grid(scale, ngrids=21):
     return grid
 
 
+def _device_chain_fill(mh, discriminator, propose, eval_size, real_sigmoid_mean, base, base_sig):
+    """The fill loop of synthetic/main.py:182-202 / 229-253 with the chain on the device (``mh``: a sampling.DeviceIndependenceSampler):
+    scores stay where D left them, every round is ONE segment of ``eval_size`` proposals, the pool is a device tensor; per round the host
+    reads one count and applies the productive-only counter rule (:196-202, :245-251) to it.  ``propose()`` -> the round's proposals
+    (host array or device tensor); the round's uniforms are drawn after it, where the reference's ``sampling`` call stands.
+    -> (pool: device fp32 [eval_size, 2], efficiency)"""
+    dev = discriminator.dev
+    pool = torch.empty((eval_size, 2), dtype=torch.float32, device=dev)
+    fill = torch.zeros(1, dtype=torch.int64, device=dev)
+    mh.set_score_curr(real_sigmoid_mean)                                               # :183,230
+
+    def one_round(x, sig):
+        rows, counts, span = mh.walk_device(sig, None, 1, None, fill, eval_size)
+        mh.gather(x, pool, span, rows)
+        return int(counts.cpu()[0])                                                    # the round's only read-back
+    cnt, cnt_propose = one_round(_upload(base, dev), base_sig), eval_size
+    while cnt < eval_size:
+        x = _upload(propose(), dev)
+        n = one_round(x, discriminator.sigmoid_and_saliency(x, want_saliency=False)[0])
+        if n > 0:
+            cnt += n
+            cnt_propose += eval_size                                                   # :202,251: only productive rounds count
+    return pool, cnt / cnt_propose
+
+
 def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_batch, centeroids, std, mh_sampler=None, diagnostics=False,
-                           maps=None):
+                           maps=None, keep_pools=False):
     """The "shape"-mode evaluation of synthetic/main.py:215-263 on the device refiner: refine the evaluation batch, report its
     quality, then D-score -> MH fill (thinning T = 20, chain seeded with mean(real_sigmoid)) until ``len(eval_batch)`` samples
     are accepted (proposal counter advancing only for productive batches, :251) and report the collaborative sample's
@@ -309,10 +334,15 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
     drawing.  The result gains "maps": the [nbins, nbins] float64 density maps (``metrics.kde_grid``, draw_kde of main.py:142,222,256,337)
     of the pools under "standard", "refinement", "collaborate" and "target", and "landscape": (grid, sigmoid), D's score on
     ``landscape_grid(grid_scale, ngrids)`` (main.py:115,130,318-333; ``grid_scale`` defaults to ``scale``).  The maps draw nothing from the
-    numpy stream and are made after everything else: every other entry is that of ``maps=None``."""
+    numpy stream and are made after everything else: every other entry is that of ``maps=None``.
+    ``mh_sampler``: a ``sampling.DeviceIndependenceSampler`` runs the collaborate leg's chain on the device (csrc/mh.hip): the refined
+    proposals' scores stay where D left them, the pool is a device tensor handed to ``ModeStats`` and ``kde_grid`` as it is, one count
+    per round comes back; samples, ``eff`` and the numpy stream are those of the host sampler.  ``keep_pools=True`` adds "pools": the
+    refinement pool and the collaborate pool (a device tensor on the device route).
+    """
     from . import metrics as Mx
     from .evaluate import collaborate
-    from .sampling import IndependenceSampler
+    from .sampling import DeviceIndependenceSampler, IndependenceSampler
     thres = std * 4
     if maps is not None and ("scale" not in maps or set(maps) - {"scale", "nbins", "grid_scale", "ngrids"}):      # before any draw
         raise ValueError(f"maps: needs 'scale', takes 'nbins', 'grid_scale', 'ngrids'; got {sorted(maps)}")
@@ -323,6 +353,8 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
     def quality(samples):
         if diagnostics:
             return Mx.mode_metrics(Mx.ModeStats(centeroids, thres, dev).update(_upload(samples, dev)).state(), real_modes)
+        if isinstance(samples, torch.Tensor):
+            samples = samples.cpu().numpy()
         mean_dist, good = Mx.metrics_distance(samples, centeroids, thres)
         return {"mean_dist": float(mean_dist), "good": float(good),
                 "kl": float(Mx.metrics_diversity(target_batch, samples, centeroids, thres)),
@@ -342,9 +374,16 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
     out["refinement"] = quality(refined)
     mh = mh_sampler if mh_sampler is not None else IndependenceSampler(T=20)           # main.py:80
     propose = lambda: refiner.manipulate_sample(generate())                            # :239-241 (eval_size proposals per round)
-    samples, eff = collaborate(propose, score, mh, len(eval_batch), float(np.mean(real_sigmoid)),
-                               base=(refined, score(refined)), count_only_productive=True)      # :229-253
+    if isinstance(mh, DeviceIndependenceSampler):
+        refined_dev = _upload(refined, discriminator.dev)
+        samples, eff = _device_chain_fill(mh, discriminator, propose, len(eval_batch), float(np.mean(real_sigmoid)), refined_dev,
+                                          discriminator.sigmoid_and_saliency(refined_dev, want_saliency=False)[0])
+    else:
+        samples, eff = collaborate(propose, score, mh, len(eval_batch), float(np.mean(real_sigmoid)),
+                                   base=(refined, score(refined)), count_only_productive=True)  # :229-253
     out["collaborate"] = dict(quality(samples), eff=float(eff))
+    if keep_pools:
+        out["pools"] = {"refinement": refined, "collaborate": samples}
     if maps is not None:
         scale, nbins = maps["scale"], maps.get("nbins", 100)
         pools = (("standard", eval_batch), ("refinement", refined), ("collaborate", samples), ("target", target_batch))
@@ -365,10 +404,13 @@ def evaluate_calibrated(discriminator, generate, eval_batch, target_batch, cente
     Returns {"standard": {...}, "rejection": {..., "eff"}, "hastings": {..., "eff"}} with the reference's four 2-D metrics
     (``thres`` = 4 std).  ``generate`` / ``diagnostics`` / ``maps`` as in ``evaluate_collaborative`` (the maps' pools: "standard",
     "rejection", "hastings", "target"); ``keep_pools=True`` adds "pools": the rejection pool (a device tensor) and the hastings pool.
-    The numpy stream is consumed as the reference consumes it: per rejection batch one uniform per proposal, then the chain's."""
+    The numpy stream is consumed as the reference consumes it: per rejection batch one uniform per proposal, then the chain's.
+    ``mh_sampler``: a ``sampling.DeviceIndependenceSampler`` runs the hastings leg's chain on the device (csrc/mh.hip) on the scores D
+    left there; the hastings pool is then a device tensor too, handed to ``ModeStats`` and ``kde_grid`` as it is; samples, ``eff`` and the
+    numpy stream are those of the host sampler."""
     from . import metrics as Mx
     from .evaluate import collaborate
-    from .sampling import DeviceRejector, IndependenceSampler
+    from .sampling import DeviceIndependenceSampler, DeviceRejector, IndependenceSampler
     thres = std * 4
     dev = discriminator.dev
     if maps is not None and ("scale" not in maps or set(maps) - {"scale", "nbins", "grid_scale", "ngrids"}):      # before any draw
@@ -416,9 +458,12 @@ def evaluate_calibrated(discriminator, generate, eval_batch, target_batch, cente
     # hastings, :182-202
     mh = mh_sampler if mh_sampler is not None else IndependenceSampler(T=20)           # main.py:80
     score = lambda batch: sigmoid(batch).cpu().numpy()
-    real_host, eval_host = real_sig.cpu().numpy(), eval_sig.cpu().numpy()
-    samples, eff = collaborate(generate, score, mh, eval_size, float(np.mean(real_host)), base=(eval_batch, eval_host),
-                               count_only_productive=True)
+    real_host = real_sig.cpu().numpy()
+    if isinstance(mh, DeviceIndependenceSampler):
+        samples, eff = _device_chain_fill(mh, discriminator, generate, eval_size, float(np.mean(real_host)), eval_dev, eval_sig)
+    else:
+        samples, eff = collaborate(generate, score, mh, eval_size, float(np.mean(real_host)), base=(eval_batch, eval_sig.cpu().numpy()),
+                                   count_only_productive=True)
     out["hastings"] = dict(quality(samples), eff=float(eff))
     if keep_pools:
         out["pools"] = {"rejection": pool, "hastings": samples}

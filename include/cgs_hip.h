@@ -662,6 +662,42 @@ size_t cgs_compact_rows_ws_bytes(int n);
 int cgs_compact_rows(const float* src, int n, int row, const unsigned char* mask, const unsigned char* take_all, int groups, float* dst, long long offset,
                      long long capacity, int* total, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the Metropolis-Hastings independence chain on the device (csrc/mh.hip) ----
+ * cgs_mh_walk: what the reference's IndependenceSampler (sampling/idpsampler.py:4-53) emits, once per logical batch ("segment").  sig:
+ * groups * b fp32 sigmoids, segment g = rows [g b, (g + 1) b); uniforms: one double per row ON THE DEVICE (the host draws them:
+ * np.random.uniform(0, 1, size=b) per walked segment, in segment order); state: two doubles on the device, d (the score of the chain's
+ * current state; the chain must be started) and cnt (visits since the last emission), both carried from segment to segment and from
+ * call to call.  Per proposal i of a segment, in order, every operation a separately rounded fp32 one, in this order:
+ *     odds  = (s_i * omd) / (df * (1.0f - s_i))        omd = (float)(1.0 - d), df = (float)d, d held as a double
+ *     alpha = odds < 1.0f ? odds : 1.0f                (Python's min(1.0, odds): a NaN gives 1.0)
+ *     moved = !(u_i > (double)alpha);  if moved: d = s_i
+ * and per segment, from the positions pos[0] < pos[1] < ... of its moves (the burn-in B counts moves of THIS segment, the held row is
+ * reset per segment): nothing is emitted unless the segment has more than B moves; first = pos[B]; the visits v = first .. b - 1 are
+ * active, a = v - first; emissions at a = a0, a0 + (T + 1), a0 + 2 (T + 1), ..., a0 = max(0, T + 1 - cnt); the emitted row is the last
+ * move position <= v; cnt afterwards = 1 + (active visits after the last emission), or cnt + (active visits) if nothing was emitted.
+ * This is numpy 2's arithmetic for fp32 scores and a Python-float or np.float32 seed; float64 scores or an np.float64 seed (numpy then
+ * promotes the ratio to double) are not this entry point's.  Scores outside [0, 1] or NaN: an unspecified in-range result, no fault.
+ * The segments are taken in order.  fill (one device long long): the UNCLIPPED number of rows the pool has received so far.  A segment
+ * that starts with *fill >= capacity is NOT walked: counts[g] = -1, state untouched, nothing listed -- rounds queued ahead of the one that
+ * fills the pool leave the chain where the reference's loop would.  A segment flagged in take_all (NULL or groups bytes) is not walked
+ * either: its b rows are listed in order, counts[g] = b, state untouched (the "too inefficient" branch, nsgan/GAN.py:369-375,420-426).
+ * Every other segment is walked; then *fill += counts[g], also past capacity.  rows (groups * b ints): indices into the call's rows, in
+ * emission order; counts: groups ints; span (2 long long): {*fill at entry, rows listed by this call}.  One wavefront owns the chain: it
+ * tests a window of 64 proposals against the current state at once and jumps to the first that moves (moves + windows serial steps); the
+ * emissions follow from the move positions in closed form over the block.  No atomics: a rerun from the same state is bit-equal.
+ * ws: cgs_mh_ws_bytes(b, groups) bytes, 4-byte aligned, CGS_EWORKSPACE if smaller; b < 1, groups < 1 or > 2^20, b * groups > 2^30,
+ * T < 0, B < 0, capacity < 0: CGS_EINVAL before any launch (the query then returns 0 for a bad shape).
+ * cgs_gather_rows: the copy behind eval[cnt:cnt + k] = batch[rows] (nsgan/GAN.py:362-368,413-419, synthetic/main.py:196-200).  src: [n][row]
+ * fp32; dst[span[0] + k] = src[rows[k]] for k < min(span[1], listed_max), listed_max the number of ints rows holds; rows with
+ * span[0] + k >= capacity are dropped (dst: at least capacity rows); a rows[k] outside [0, n) copies nothing for that k; a row may repeat.
+ * 16-byte pieces where row % 4 == 0 and both bases are 16-byte aligned, 4-byte pieces otherwise.  n outside [0, 2^30], row outside
+ * [1, 2^22], n * row > 2^40, listed_max outside [0, 2^30], capacity < 0: CGS_EINVAL before any launch. */
+size_t cgs_mh_ws_bytes(int b, int groups);
+int cgs_mh_walk(const float* sig, int b, int groups, const double* uniforms, int T, int B, const unsigned char* take_all, double* state, long long* fill,
+                long long capacity, int* rows, int* counts, long long* span, void* ws, size_t ws_bytes, void* stream);
+int cgs_gather_rows(const float* src, int n, int row, const int* rows, int listed_max, const long long* span, float* dst, long long capacity,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
