@@ -1097,6 +1097,56 @@ def spatial_mean(x, out=None):
     return o
 
 
+# ----------------------------------------------------------------------------- the Frechet distance from two states (csrc/frechet.hip)
+def _chk_f64(t, name, shape, device=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == tuple(shape)
+            and (device is None or t.device == device)):
+        raise L.CgsError(f"{name}: expected a contiguous float64 {tuple(shape)} tensor on {device or 'the GPU'}, got "
+                         f"{type(t).__name__} {getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))} {getattr(t, 'device', None)}")
+    return t
+
+
+def f64_matmul(a, b, out=None, alpha=1.0, diag=0.0):
+    """out = alpha * a @ b + diag * I for square float64 matrices on the GPU (d <= 2048), in double on the float64 MFMA; ``out`` must not
+    be ``a`` or ``b``."""
+    if not (isinstance(a, torch.Tensor) and a.dim() == 2 and a.shape[0] == a.shape[1]):
+        raise L.CgsError("f64_matmul: a must be a square matrix")
+    d = a.shape[0]
+    _chk_f64(a, "f64_matmul: a", (d, d))
+    _chk_f64(b, "f64_matmul: b", (d, d), a.device)
+    o = out if out is not None else torch.empty((d, d), dtype=torch.float64, device=a.device)
+    _chk_f64(o, "f64_matmul: out", (d, d), a.device)
+    with torch.cuda.device(a.device):
+        L.call("cgs_f64_matmul", _ptr(a), _ptr(b), _ptr(o), d, float(alpha), float(diag), _stream())
+    return o
+
+
+def frechet_from_moments(sum_r, gram_r, shift_r, n_r, sum_f, gram_f, shift_f, n_f, ddof=1, max_iters=48, out=None):
+    """The Frechet distance of two pools from the device tensors of their states (``metrics.PoolMoments``: sum [d] / gram [d, d]
+    float64, shift [d] fp32 or None, n rows), queued on the current stream.  Returns ``out``, 8 device doubles: fd, |dmu|^2, Tr S_r,
+    Tr S_f, Tr (S_r^1/2 S_f S_r^1/2)^1/2, the two roots' iteration counts, status (include/cgs_hip.h).  Nothing is read back here."""
+    if not (isinstance(sum_r, torch.Tensor) and sum_r.dim() == 1):
+        raise L.CgsError("frechet_from_moments: sum_r must be a [d] tensor")
+    d, dev = sum_r.shape[0], sum_r.device
+    for t, name, shape in ((sum_r, "sum_r", (d,)), (gram_r, "gram_r", (d, d)), (sum_f, "sum_f", (d,)), (gram_f, "gram_f", (d, d))):
+        _chk_f64(t, f"frechet_from_moments: {name}", shape, dev)
+    for t, name in ((shift_r, "shift_r"), (shift_f, "shift_f")):
+        if t is not None:
+            _chk(t, name)
+            if tuple(t.shape) != (d,) or t.device != dev:
+                raise L.CgsError(f"frechet_from_moments: {name} must be [{d}] on {dev}")
+    o = out if out is not None else torch.empty(8, dtype=torch.float64, device=dev)
+    _chk_f64(o, "frechet_from_moments: out", (8,), dev)
+    with torch.cuda.device(dev):
+        need = int(L.load().cgs_frechet_ws_bytes(d))
+        if need == 0:
+            raise L.CgsError(f"frechet_from_moments: unsupported width d={d}: 1 <= d <= 2048")
+        ws = _moments_workspace(need, dev)
+        L.call("cgs_frechet_from_moments", _ptr(sum_r), _ptr(gram_r), _ptr(shift_r), int(n_r), _ptr(sum_f), _ptr(gram_f), _ptr(shift_f), int(n_f),
+               d, int(ddof), int(max_iters), _ptr(o), _ptr(ws), ws.numel() * 8, _stream())
+    return o
+
+
 # ----------------------------------------------------------------------------- calibration / mode statistics (csrc/diagnostics.hip)
 CAL_MAX_BINS, MODE_MAX_K = 64, 64
 

@@ -127,6 +127,9 @@ SIGNATURES = {
     "cgs_pool_moments_ws_bytes": (_z, [_i, _i]),
     "cgs_pool_moments_accumulate": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _p, _z, _p]),
     "cgs_spatial_mean": (_i, [_p, _p, _i, _i, _i, _p]),
+    "cgs_f64_matmul": (_i, [_p, _p, _p, _i, C.c_double, C.c_double, _p]),
+    "cgs_frechet_ws_bytes": (_z, [_i]),
+    "cgs_frechet_from_moments": (_i, [_p, _p, _p, _ll, _p, _p, _p, _ll, _i, _i, _i, _p, _p, _z, _p]),
     "cgs_calibration_ws_bytes": (_z, [_i, _i]),
     "cgs_calibration_accumulate": (_i, [_p, _i, _i, _p, _i, _p, _p, _z, _p]),
     "cgs_mode_stats_ws_bytes": (_z, [_i, _i]),

@@ -158,6 +158,52 @@ class PoolMoments:
     def mean_cov(self, ddof=1):
         return moments_mean_cov(self.state(), ddof)
 
+    @classmethod
+    def from_state(cls, state, device):
+        """A pool on ``device`` that holds a host state (e.g. the result of ``all_reduce_moments``): sum / gram uploaded as they are.
+        The shift is kept as fp32 (a PoolMoments shift always is one); a state whose shift is not representable is rebased first."""
+        import torch
+        shift = np.asarray(state["shift"], dtype=np.float64)
+        shift32 = shift.astype(np.float32)
+        if not np.array_equal(shift32.astype(np.float64), shift):
+            state = moments_rebase(state, shift32.astype(np.float64))
+        pm = cls(shift.shape[0], device, shift=shift32)          # raises on a non-GPU device
+        pm.n = int(state["n"])
+        pm.sum = torch.from_numpy(np.ascontiguousarray(state["sum"], dtype=np.float64).reshape(pm.d)).to(pm.device)
+        pm.gram = torch.from_numpy(np.ascontiguousarray(state["gram"], dtype=np.float64).reshape(pm.d, pm.d)).to(pm.device)
+        return pm
+
+
+def frechet_device(real, fake, ddof=1, max_iters=48, details=False):
+    """The Frechet distance of two pools computed on the device from their states (csrc/frechet.hip): both
+    covariances, the two matrix square roots (Newton-Schulz in double on the float64 MFMA) and the traces stay there; the one
+    read-back is the 64-byte record.  ``real`` / ``fake``: ``PoolMoments`` (their queued updates are waited for through their events) or
+    host states, which are uploaded to the other one's device (cuda:current if both are states).  Returns the distance, or with
+    ``details`` the record {fd, dmu2, tr_r, tr_f, tr_root, iters_r, iters_m, status}; status 0 = tolerance met, 1 = stalled and the
+    last good iterate kept (rank-deficient covariances end here), 2 = iteration cap."""
+    import torch
+    from . import kernels as K
+    dev = next((m.device for m in (real, fake) if isinstance(m, PoolMoments)), None)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    real, fake = (m if isinstance(m, PoolMoments) else PoolMoments.from_state(m, dev) for m in (real, fake))
+    if real.d != fake.d or real.device != fake.device:
+        raise ValueError(f"frechet_device: pools of width {real.d} on {real.device} and {fake.d} on {fake.device}")
+    if min(real.n, fake.n) - ddof <= 0:
+        raise ValueError(f"frechet_device: needs more than ddof = {ddof} rows per pool (n = {real.n}, {fake.n})")
+    with torch.cuda.device(real.device):
+        st = torch.cuda.current_stream(real.device)
+        for m in (real, fake):
+            if m._last is not None:
+                st.wait_event(m._last)
+        out = K.frechet_from_moments(real.sum, real.gram, real.shift, real.n, fake.sum, fake.gram, fake.shift, fake.n, ddof=ddof,
+                                     max_iters=max_iters)
+        h = out.cpu().numpy()                                     # the one read-back: 8 doubles
+    if not details:
+        return float(h[0])
+    return dict(fd=float(h[0]), dmu2=float(h[1]), tr_r=float(h[2]), tr_f=float(h[3]), tr_root=float(h[4]), iters_r=int(h[5]), iters_m=int(h[6]),
+                status=int(h[7]))
+
 
 def all_reduce_moments(moments, group=None):
     """The state of the union of every rank's pool: rank 0's shift is broadcast, each rank rebases onto it, and ONE all-reduce adds

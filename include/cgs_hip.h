@@ -592,6 +592,32 @@ int cgs_pool_moments_accumulate(const float* x, int n, int d, const int* rows, i
  * map as one vector per sample (engine.RefineEngine.score_with_features). */
 int cgs_spatial_mean(const float* x, float* out, int B, int HW, int C, void* stream);
 
+/* ---- the Frechet distance of two pools from their moment states, on the device (csrc/frechet.hip) ----
+ * cgs_f64_matmul: C = alpha * A * B + diag * I for row-major d x d doubles, 1 <= d <= 2048; every product and sum a double operation on
+ * v_mfma_f64_16x16x4_f64, each result one accumulation chain in ascending k (no K split, no atomics: reruns are bit-equal).  B is a
+ * general matrix.  c must not alias a or b.  d out of range, a null pointer or an aliased c: CGS_EINVAL before any launch.
+ * cgs_frechet_from_moments: sum / gram are the device doubles of a metrics.PoolMoments ([d] and [d][d]), shift a device float [d] or
+ * NULL (= 0), n the number of rows behind them.  With
+ *     mean = shift + sum / n        cov = (gram - sum sum^T / n) / (n - ddof), symmetrised  (shift-invariant: the pools' shifts may differ)
+ *     dmu  = ((double)shift_r - (double)shift_f) + sum_r / n_r - sum_f / n_f
+ * out (8 device doubles) receives
+ *     [0] fd = |dmu|^2 + Tr S_r + Tr S_f - 2 Tr (S_r^{1/2} S_f S_r^{1/2})^{1/2}     [1] |dmu|^2     [2] Tr S_r     [3] Tr S_f
+ *     [4] Tr (S_r^{1/2} S_f S_r^{1/2})^{1/2}  (= Tr (S_r S_f)^{1/2})     [5] / [6] iterations used by the first / second root
+ *     [7] status: 0 = tolerance met, 1 = stalled and the last good iterate kept, 2 = iteration cap  (the larger of the two roots')
+ * Both roots are of symmetric positive semi-definite matrices, by the coupled Newton-Schulz iteration on A / |A|_F (three products per
+ * step); a step is accepted while the trace still converges, the iteration stops at |delta Tr| <= max(1e-15, d 2^-52) Tr, or -- from the
+ * fifth step on -- discards the step at which |delta Tr| stops shrinking below 1e-6 Tr, or at max_iters.  An exactly zero covariance has
+ * root 0 (no division).  Everything is queued on `stream`: no host synchronisation, no read-back; the stop decision is taken on the
+ * device (traces and norms reduced in a fixed order, a rerun is bit-equal) and turns the remaining queued launches -- their number is
+ * fixed by max_iters -- into early exits.  ws: cgs_frechet_ws_bytes(d) bytes, 8-byte aligned; nothing past them is written.
+ * CGS_EINVAL before any launch: d outside 1..2048 (the query then returns 0), n <= 0 or n - ddof <= 0, a null sum / gram / out, a
+ * misaligned workspace, max_iters outside 1..64; CGS_EWORKSPACE: a null or short workspace. */
+int cgs_f64_matmul(const double* a, const double* b, double* c, int d, double alpha, double diag, void* stream);
+size_t cgs_frechet_ws_bytes(int d);
+int cgs_frechet_from_moments(const double* sum_r, const double* gram_r, const float* shift_r, long long n_r, const double* sum_f,
+                             const double* gram_f, const float* shift_f, long long n_f, int d, int ddof, int max_iters, double* out, void* ws,
+                             size_t ws_bytes, void* stream);
+
 /* ---- calibration and 2-D mode statistics of a pool, additive, in double on the device (csrc/diagnostics.hip) ----
  * Calibration of D's scores (the reference's calibration_diagnostic, sampling/utils_sampling.py:186-299).  p: n fp32 scores, widened to
  * double exactly; label: 0 (fake) or 1 (real), one per call; edges: n_bins + 1 ascending doubles ON THE DEVICE
