@@ -28,7 +28,7 @@ int cgs_set_error(int code, const char* fmt, ...) {
 
 extern "C" {
 
-int cgs_version(void) { return 116; }
+int cgs_version(void) { return 117; }
 const char* cgs_last_error(void) { return g_err; }
 const char* cgs_last_kernel(void) { return g_last_kernel; }
 double cgs_last_executed_flops(void) { return g_last_flops; }
@@ -132,13 +132,15 @@ struct NsArgs { const float *mean, *invstd, *gamma, *beta; float leak; int group
 
 // What an entry point passes beside the plain conv arguments.  FORM_STATS (*_fwd_stats): the launch leaves the column sums of its output
 // as partial rows in stat_part; FORM_NSTATS (*_bwd_data_nstats): the norm backward's two column sums, from ns and x_norm (in ep_aux);
-// FORM_SIGNS (*_signs): a forward leaves the sign mask of its output in sign_out, a backward-data takes aux_signs for the fp32 ep_aux.
-enum ConvForm { FORM_PLAIN, FORM_STATS, FORM_NSTATS, FORM_SIGNS };
+// FORM_SIGNS (*_signs): a forward leaves the sign mask of its output in sign_out, a backward-data takes aux_signs for the fp32 ep_aux;
+// FORM_UPDATE (*_bwd_data_update): the result is not stored -- the momentum step of the refinement loop is applied to ``out`` (the feature) and up_mom.
+enum ConvForm { FORM_PLAIN, FORM_STATS, FORM_NSTATS, FORM_SIGNS, FORM_UPDATE };
 struct ConvExtras {
     ConvForm form = FORM_PLAIN;
     float* stat_part = nullptr; size_t stat_part_bytes = 0;
     NsArgs ns = {};
     unsigned* sign_out = nullptr; const unsigned* aux_signs = nullptr;
+    float* up_mom = nullptr; float up_rate = 0.f, up_alpha = 0.f; int up_first = 0;
 };
 
 static int run_dir(const ConvCall& c, int B, const float* in, const float* w, const float* bias, float* out, int epilogue,
@@ -161,6 +163,7 @@ static int run_dir(const ConvCall& c, int B, const float* in, const float* w, co
     const int fam = choose_family(L, dirT, p, ws != nullptr, ws_bytes, !((uintptr_t)in & 15), !((uintptr_t)ws & 15), rest_al);
     if (x.stat_part && fam != CGS_FAMILY_IGEMM && fam != CGS_FAMILY_IGEMM_BX6) return cgs_set_error(CGS_EINVAL, "%s: fused statistics are an implicit-GEMM feature (see cgs_conv_stat_partials)", who);
     if (nstats && (!x.stat_part || fam != CGS_FAMILY_IGEMM)) return cgs_set_error(CGS_EINVAL, "%s: norm-backward statistics are a feature of the exact-fp32 implicit GEMM (see cgs_conv_stat_layout)", who);
+    if (x.form == FORM_UPDATE && (!x.up_mom || fam != CGS_FAMILY_IGEMM)) return cgs_set_error(CGS_EINVAL, "%s: the fused update is a feature of the exact-fp32 implicit GEMM (see cgs_conv_update_form)", who);
     if (x.sign_out && fam != CGS_FAMILY_IGEMM && fam != CGS_FAMILY_IGEMM_BX6) return cgs_set_error(CGS_EINVAL, "%s: this call cannot leave a sign mask (see cgs_conv_signs_ok)", who);
     if (x.aux_signs && fam != CGS_FAMILY_PATCH && fam != CGS_FAMILY_TAPS) return cgs_set_error(CGS_EINVAL, "%s: this call cannot take a sign mask (see cgs_conv_signs_ok)", who);
     if (((uintptr_t)x.sign_out & 3) || ((uintptr_t)x.aux_signs & 3)) return cgs_set_error(CGS_EINVAL, "%s: sign mask must be 4-byte aligned", who);
@@ -182,6 +185,7 @@ static int run_dir(const ConvCall& c, int B, const float* in, const float* w, co
     p.in = in; p.bias = bias; p.ep_a = ep_a; p.ep_b = ep_b; p.ep_aux = ep_aux; p.out = out;
     p.stat_part = x.stat_part;
     if (nstats) { p.ns_mean = x.ns.mean; p.ns_inv = x.ns.invstd; p.ns_gamma = x.ns.gamma; p.ns_beta = x.ns.beta; p.ns_leak = x.ns.leak; p.ns_gimg = x.ns.group_images >= B ? 0 : x.ns.group_images; }
+    if (x.form == FORM_UPDATE) { p.up_mom = x.up_mom; p.up_rate = x.up_rate; p.up_alpha = x.up_alpha; p.up_first = x.up_first; }
     p.sign_out = x.sign_out;
     p.sign_plane = (long)B * (dirT ? L.Hb * L.Wb : L.Hs * L.Ws);
     const bool bx6 = fam == CGS_FAMILY_IGEMM_BX6;
@@ -198,6 +202,7 @@ static int run_dir(const ConvCall& c, int B, const float* in, const float* w, co
     const size_t chunk = images_per_launch(p), in_img = in_image_floats(p), out_img = out_image_floats(p);
     if (chunk < 1) return cgs_set_error(CGS_EINVAL, "%s: one image exceeds 2 GiB", who);
     if (x.stat_part && !whole_batch_in_one_launch(p)) return cgs_set_error(CGS_EINVAL, "%s: fused statistics need the batch in one launch", who);
+    if (p.up_mom && !whole_batch_in_one_launch(p)) return cgs_set_error(CGS_EINVAL, "%s: the fused update needs the batch in one launch", who);
     for (size_t b0 = 0; b0 < (size_t)B; b0 += chunk) {
         p.B = (int)(B - b0 < chunk ? B - b0 : chunk);
         p.in = in + b0 * in_img;
@@ -263,6 +268,11 @@ static int conv_entry(const char* who, int op, const float* in, const float* w, 
         const size_t need = (size_t)G * 2 * (c.bwd ? Cin : Cout) * sizeof(float);        // [rows][2][channels of the tensor the launch writes]
         if (!x.stat_part || x.stat_part_bytes < need) return cgs_set_error(CGS_EWORKSPACE, "%s: partials buffer %zu < %zu bytes", who, x.stat_part_bytes, need);
         if ((uintptr_t)x.stat_part & 15) return cgs_set_error(CGS_EINVAL, "%s: partials buffer must be 16-byte aligned", who);
+    }
+    if (x.form == FORM_UPDATE) {          // (asked BEFORE anything is launched: a refused call leaves the feature and the momentum buffer untouched)
+        if (!cgs_conv_update_form(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, ws_bytes, nullptr))
+            return cgs_set_error(CGS_EINVAL, "%s: not available for this call (cgs_conv_update_form == 0)", who);
+        if (!out || !x.up_mom || (((uintptr_t)out | (uintptr_t)x.up_mom) & 15)) return cgs_set_error(CGS_EINVAL, "%s: theta and m must be 16-byte aligned tensors", who);
     }
     return run_dir(c, B, in, w, bias, out, epilogue, ep_a, ep_b, ep_aux, ws, ws_bytes, prepacked, (hipStream_t)stream, who, x);
 }
@@ -361,6 +371,21 @@ int cgs_conv_stat_layout(int op, int B, int H, int W, int Cin, int Ho, int Wo, i
     return (int)(cls_rows * p.nclasses);
 }
 
+// ---- the fused momentum update (cgs_hip.h, cgs_*_bwd_data_update): where the call would apply it, 0 = not offered ----
+int cgs_conv_update_form(int op, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw, size_t ws_bytes,
+                         int* row_order) {
+    if (row_order) *row_order = 0;
+    if (op != CGS_CONV_BWD_DATA && op != CGS_DECONV_BWD_DATA) return 0;
+    const ConvPlan q = conv_plan_of(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, CGS_EPI_NONE, ws_bytes);
+    if (q.fam != CGS_FAMILY_IGEMM || check_layer(q.c.L, "conv_update_form")) return 0;
+    if (q.c.dirT && (sh > 2 || sw > 2)) return 0;
+    if (!whole_batch_in_one_launch(q.g)) return 0;                  // the entry point would split the batch
+    const size_t packed = cgs_packed_floats(q.g) * sizeof(float);
+    if (ws_bytes < packed) return 0;
+    if (row_order) *row_order = cgs_igemm_row_order(q.g);
+    return cgs_igemm_update_form(q.g, ws_bytes - packed);
+}
+
 // ---- sign masks (cgs_hip.h): the activation gradient of relu / lrelu needs one bit per element of the saved activation ----
 int cgs_conv_signs_ok(int op, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw, int epilogue,
                       size_t ws_bytes) {
@@ -434,6 +459,24 @@ int cgs_deconv2d_nhwc_bwd_data_nstats(const float* dy, const float* w, float* dx
     return conv_entry("deconv2d_nhwc_bwd_data_nstats", CGS_DECONV_BWD_DATA, dy, w, nullptr, dx, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, CGS_EPI_NONE, nullptr,
                       nullptr, x_norm, ws, ws_bytes, ws_prepacked, stream, ConvExtras{FORM_NSTATS, stat_part, stat_part_bytes, NsArgs{mean, invstd, gamma, beta,
                       leak, group_images}});
+}
+
+int cgs_conv2d_nhwc_bwd_data_update(const float* dy, const float* w, float* theta, float* m, int B, int H, int W, int Cin, int Cout, int kh,
+                                    int kw, int sh, int sw, float rate, float alpha, int first, void* ws, size_t ws_bytes, int ws_prepacked,
+                                    void* stream) {
+    ConvExtras x;
+    x.form = FORM_UPDATE; x.up_mom = m; x.up_rate = rate; x.up_alpha = alpha; x.up_first = first ? 1 : 0;
+    return conv_entry("conv2d_nhwc_bwd_data_update", CGS_CONV_BWD_DATA, dy, w, nullptr, theta, B, H, W, Cin, 0, 0, Cout, kh, kw, sh, sw, CGS_EPI_NONE, nullptr,
+                      nullptr, nullptr, ws, ws_bytes, ws_prepacked, stream, x);
+}
+
+int cgs_deconv2d_nhwc_bwd_data_update(const float* dy, const float* w, float* theta, float* m, int B, int H, int W, int Cin, int Ho, int Wo,
+                                      int Cout, int kh, int kw, int sh, int sw, float rate, float alpha, int first, void* ws, size_t ws_bytes,
+                                      int ws_prepacked, void* stream) {
+    ConvExtras x;
+    x.form = FORM_UPDATE; x.up_mom = m; x.up_rate = rate; x.up_alpha = alpha; x.up_first = first ? 1 : 0;
+    return conv_entry("deconv2d_nhwc_bwd_data_update", CGS_DECONV_BWD_DATA, dy, w, nullptr, theta, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, CGS_EPI_NONE,
+                      nullptr, nullptr, nullptr, ws, ws_bytes, ws_prepacked, stream, x);
 }
 
 int cgs_deconv2d_nhwc_fwd_signs(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,

@@ -94,7 +94,14 @@ struct IgemmParams {
     const float* ns_beta = nullptr;
     float ns_leak = 1.f;
     int ns_gimg = 0;
-    int vec;             // the 32-channel-chunk K order / 16-byte row gathers apply: Cred % 32 == 0 and at most 16 taps per axis
+    // Fused momentum update (up_mom != null; CGS_EPI_NONE, no bias, no statistics / sign mask, N % 4 == 0, VEC): the launch is the backward-data
+    // pass whose result g is the gradient w.r.t. the refined feature; instead of storing g, the element's owner applies refine_update1 to
+    // out (= the feature theta, read AND written) and up_mom (the momentum buffer, same shape) -- the igemm_up_kernel twin's epilogue, or the
+    // reduce kernel of a split-K / tail-split launch.  g itself never goes to memory.
+    float* up_mom = nullptr;
+    float up_rate = 0.f, up_alpha = 0.f;
+    int up_first = 0;
+    int vec;            // the 32-channel-chunk K order / 16-byte row gathers apply: Cred % 32 == 0 and at most 16 taps per axis
     int prio_t[3];       // progress thresholds (1/256 of the block's K tiles) at which a block steps its wave priority down; 0 = off
     // tail split (igemm.hip, "tail split"): the LAST tail_n tiles of the launch (the end of the last class in dispatch order) are each
     // contracted by tail_s blocks over disjoint K ranges into compact partial tiles slab[tail tile][split][BM][BN], which
@@ -130,7 +137,10 @@ size_t cgs_igemm_bx6_packed_bytes(const IgemmParams& p);
 int cgs_pack_weights_bx6(const IgemmParams& p, const CgsLayer& L, bool dirT, const float* w, void* packed, hipStream_t s);
 int cgs_igemm_bx6_launch(const IgemmParams& p, hipStream_t s);
 int cgs_contraction_mode();                             // thread-local: CGS_CONTRACTION_* (api.hip)
-int cgs_igemm_row_order(const IgemmParams& p);         // GEMM row order the launcher will pick: 0 (image, pixel); 1 (pixel, image); 2 (pixel, image) in whole 128-image tiles
+// where a launch of this geometry (behind its packed weights: slab_bytes of workspace) would apply the fused momentum update: CGS_UPDATE_* of
+// cgs_hip.h, 0 = it cannot (the launcher then refuses up_mom)
+int cgs_igemm_update_form(const IgemmParams& p, size_t slab_bytes);
+int cgs_igemm_row_order(const IgemmParams& p);       // GEMM row order the launcher will pick: 0 (image, pixel); 1 (pixel, image); 2 (pixel, image) in whole 128-image tiles
 size_t cgs_convt_quad_ws_floats_bound(int kh, int kw, int Cs);
 int cgs_convt_taps_ok(const CgsLayer& L);          // 4x4 stride-2 transposed conv to one channel: all 16 taps as MFMA columns (convt_taps.hip)
 int cgs_convt_taps_launch(const CgsLayer& L, int B, const float* in, const float* w, const float* bias, float* out, int epilogue,
@@ -202,6 +212,21 @@ __device__ __forceinline__ void ladam_seed1(const cgs_ladam_seed& la, int b, flo
     la.loss_avg[b] = avg;
     const float c = fminf(fmaxf(avg + 0.5f, 0.f), 10000.f);
     la.gain[b] = c * c;
+}
+// The momentum / sgd step of the refinement loop on ONE element, once (policy.py:27-37; the clip: collaborator.py:69-70): m <- alpha * m +
+// rate * g (the first step: rate * g), theta <- theta - m.  elementwise.hip's refine_update_kernel and the update epilogues of igemm.hip
+// (igemm_epilogue.h, the reduce kernels) call it: sampling/policy.py is bit-exact against the reference's op sequence, so that sequence
+// lives here only -- separately rounded mul / add in every caller.
+__device__ __forceinline__ void refine_update1(float g, float rate, float alpha, int first, int use_clip, float vmin, float vmax, float& theta,
+                                               float& m) {
+#pragma clang fp contract(off)
+    const float lg = rate * g;
+    const float am = alpha * m;
+    const float mv = first ? lg : am + lg;
+    m = mv;
+    float t = theta - mv;
+    if (use_clip) t = fminf(fmaxf(t, vmin), vmax);
+    theta = t;
 }
 #endif
 

@@ -310,14 +310,10 @@ int cgs_clip(const float* x, float vmin, float vmax, float* y, size_t n, void* s
 __global__ __launch_bounds__(256) void refine_update_kernel(float* __restrict__ theta, float* __restrict__ m,
                                                             const float* __restrict__ g, float rate, float alpha,
                                                             int first, int use_clip, float vmin, float vmax, size_t n) {
-#pragma clang fp contract(off)   // separately rounded mul / add, the reference's op sequence (policy.py:33-36)
-    GRID_STRIDE(i, n) {
-        const float lg = rate * g[i];
-        const float am = alpha * m[i];
-        const float mv = first ? lg : am + lg;
+    GRID_STRIDE(i, n) {              // (the element's op sequence: refine_update1, cgs_internal.h -- shared with the update epilogues of igemm.hip)
+        float t = theta[i], mv = m[i];
+        refine_update1(g[i], rate, alpha, first, use_clip, vmin, vmax, t, mv);
         m[i] = mv;
-        float t = theta[i] - mv;
-        if (use_clip) t = fminf(fmaxf(t, vmin), vmax);          // collaborator.py:69-70
         theta[i] = t;
     }
 }

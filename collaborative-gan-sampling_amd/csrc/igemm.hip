@@ -142,8 +142,11 @@ int cgs_pack_weights(const IgemmParams& p, const CgsLayer& L, bool dirT, const f
 // kernel: the branch's mere presence cost the launches that never take it 6 % (the dominant kernel of the headline 680 -> 724 us per launch in
 // alternating processes on one box, profiles/r06_l_nstat_branch_presence_ab.txt) -- so igemm_kernel is compiled without it, exactly as
 // before round 6, and only the launches that want the sums run igemm_ns_kernel.
-template <int BM, int BN, int NW, bool VEC, int TBK, bool PAR, bool NS>
+// UP: the epilogue applies the refinement loop's momentum step at the element it would have stored (IgemmParams::up_*) -- a second compile-time
+// twin for the same reason, igemm_up_kernel, instantiated for the VEC tiles only (the launcher offers the fused update for nothing else).
+template <int BM, int BN, int NW, bool VEC, int TBK, bool PAR, bool NS, bool UP = false>
 __device__ __forceinline__ void igemm_body(const IgemmParams& p) {
+    static_assert(!(NS && UP), "one twin per launch");
     constexpr int BK = TBK;                       // K tile (shadows the packing granule; TBK divides it)
     constexpr int LDA = BK + 4;                   // padded A row (floats): keeps the b128 fragment reads conflict-free
     constexpr int NT = 64 * NW;                   // threads per block
@@ -781,7 +784,12 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             if (n < p.N) {
                 const int* rp = rowpix + wm * (BM / WM) + ph * ER;
-                if constexpr (NS) {               // norm-BACKWARD statistics of the gradient this launch produces (IgemmParams::ns_*; the launcher picks this twin for them only)
+                if constexpr (UP) {               // the momentum step on theta (p.out) and p.up_mom instead of the store (the launcher picks this twin for it only)
+                    // (a wave whose 64 rows all lie past M has no live row: it loads and stores nothing.  Four rows' loads in flight before their stores
+                    // in the 32-deep kernels, as in the sums twin; two in the 16-deep ones, whose registers decide the fourth resident block: the
+                    // compiler's resource remarks give 106-108 VGPRs against the plain kernel's 118 -- the K loop stays the peak)
+                    epilogue_rows_update<ER, RPP, LDE, ((VEC && TBK == 32) ? 4 : 2)>(p, E, rp, rsub, c4, n, bias);
+                } else if constexpr (NS) {        // norm-BACKWARD statistics of the gradient this launch produces (IgemmParams::ns_*; the launcher picks this twin for them only)
                     // a wave's 64 rows lie in ONE statistics group (cgs_conv_stat_layout admits only such launches): its parameters once per wave and pass
                     // (a wave whose 64 rows all lie past M -- the second half of a last tile with M % 128 == 64 -- stores nothing, but its parameter
                     // loads must still hit a real group: row M - 1's.  Found by the topology fuzz: batch 3 x 64 pixels read the statistics of "sample 3")
@@ -829,6 +837,7 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p) {
         }
         return;
     }
+    if constexpr (UP) return;      // (the update twin is launched for N % 4 == 0 only: cgs_igemm_update_form)
 #pragma unroll     // (must stay fully unrolled: a run-time tn would index the accumulator array and push it to scratch)
     for (int tn = 0; tn < TN; ++tn) {
         const int n = n0 + wn * WTN + tn * 32 + j;
@@ -857,8 +866,13 @@ template <int BM, int BN, int NW, bool VEC, int TBK, bool PAR>
 __global__ __launch_bounds__(64 * NW, 2) void igemm_kernel(IgemmParams p) { igemm_body<BM, BN, NW, VEC, TBK, PAR, false>(p); }
 template <int BM, int BN, int NW, bool VEC, int TBK, bool PAR>
 __global__ __launch_bounds__(64 * NW, 2) void igemm_ns_kernel(IgemmParams p) { igemm_body<BM, BN, NW, VEC, TBK, PAR, true>(p); }
+template <int BM, int BN, int NW, bool VEC, int TBK, bool PAR>
+__global__ __launch_bounds__(64 * NW, 2) void igemm_up_kernel(IgemmParams p) { igemm_body<BM, BN, NW, VEC, TBK, PAR, false, true>(p); }
 
 // out[pix(m)][n] = epi(bias[n] + sum_s slab[s][m][n]): fixed summation order -> deterministic
+// UP (compile-time, as in the main kernel): the sum is the gradient w.r.t. the refined feature -- the momentum step on p.out / p.up_mom instead
+// of the store (N % 4 == 0, no epilogue: whole 16-byte quads)
+template <bool UP>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(IgemmParams p) {
     const IgemmClass& c = p.cls[blockIdx.y];
     const int RC = c.R * c.C;
@@ -887,6 +901,19 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(IgemmParams p) {
         if (p.pix_major) { rem = m / p.B; b = m - rem * p.B; } else { b = m / RC; rem = m - b * RC; }
         r = rem / c.C; cc = rem - r * c.C;
         const size_t o = (size_t)((b * p.Hout + r * p.So + c.py) * p.Wout + cc * p.So + c.px) * p.N;
+        if constexpr (UP) {
+            if (n >= p.N) continue;          // (a quad of the padding columns up to Np; N % 4 == 0: a quad is inside N or past it)
+            f32x4 t = *(const f32x4*)(p.out + o + n), mv = *(const f32x4*)(p.up_mom + o + n);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float te = t[e], me = mv[e];
+                refine_update1(a[e] + (p.bias ? p.bias[n + e] : 0.f), p.up_rate, p.up_alpha, p.up_first, 0, 0.f, 0.f, te, me);
+                t[e] = te; mv[e] = me;
+            }
+            *(f32x4*)(p.up_mom + o + n) = mv;
+            *(f32x4*)(p.out + o + n) = t;
+            continue;
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if (n + e >= p.N) break;
@@ -961,6 +988,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(IgemmParams p)
 // Tail split, second half: block = one tail tile.  out[pix(m)][n] = epi(bias[n] + sum_z slab[tile][z][m - m0][n - n0]), the K slices
 // added in index order (deterministic); the tile decode is the main kernel's (same wi -> (m-tile, n-tile), same row -> pixel map).
 #define TAIL_RSPLIT 16
+template <bool UP>
 __global__ __launch_bounds__(256) void tail_reduce_kernel(IgemmParams p, int BM, int BN) {
     const int cls_i = p.nclasses - 1;
     const IgemmClass& c = p.cls[cls_i];
@@ -1004,6 +1032,18 @@ __global__ __launch_bounds__(256) void tail_reduce_kernel(IgemmParams p, int BM,
         if (p.pix_major) { rem = m / p.B; b = m - rem * p.B; } else { b = m / RC; rem = m - b * RC; }
         const int r = rem / c.C, cc = rem - r * c.C;
         const size_t o = (size_t)((b * p.Hout + r * p.So + c.py) * p.Wout + cc * p.So + c.px) * p.N + n;
+        if constexpr (UP) {          // (the momentum step instead of the store, as in the update twin's epilogue)
+            f32x4 t = *(const f32x4*)(p.out + o), mv = *(const f32x4*)(p.up_mom + o);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float te = t[e], me = mv[e];
+                refine_update1(a[e] + bias[e], p.up_rate, p.up_alpha, p.up_first, 0, 0.f, 0.f, te, me);
+                t[e] = te; mv[e] = me;
+            }
+            *(f32x4*)(p.up_mom + o) = mv;
+            *(f32x4*)(p.out + o) = t;
+            continue;
+        }
         f32x4 aux = {0.f, 0.f, 0.f, 0.f};
         if (p.epilogue >= CGS_EPI_RELU_BWD_AFFINE) aux = *(const f32x4*)(p.ep_aux + o);
         f32x4 y;
@@ -1225,9 +1265,37 @@ size_t cgs_igemm_splitk_bytes(const IgemmParams& p) {
     return n * sizeof(float);
 }
 
-template <int BM, int BN, int NW, bool VEC, int TBK, bool PAR, bool NS>
+// The fused momentum update (IgemmParams::up_*): where would a launch of this geometry, with slab_bytes of workspace behind its packed
+// weights, apply it -- the planning steps of cgs_igemm_launch in its order (split-K first, then the tile and the tail split), so the answer
+// given before a capture is the launch's own.  0 = not offered: the generic-K gather (Cred % 32 != 0), N % 4 != 0, an epilogue, statistics
+// or a sign mask on the same launch, the tall 256 x 64 tile (no twin is instantiated for it).
+int cgs_igemm_update_form(const IgemmParams& p_in, size_t slab_bytes) {
+    IgemmParams p = p_in;
+    if (!p.vec || (p.N & 3) || p.epilogue != CGS_EPI_NONE || p.bias || p.stat_part || p.sign_out) return 0;
+    p.splitk = 1; p.slab = nullptr;
+    p.tail_from = p.tail_n = p.tail_s = 0;
+    cgs_igemm_row_policy(p, 128);
+    const size_t need = cgs_igemm_splitk_bytes(p);
+    if (need && slab_bytes >= need) return CGS_UPDATE_SPLITK;
+    IgemmTiles tiles = igemm_choose_tiles(p);
+    IgemmTail tl = igemm_choose_tail(p, tiles);
+    bool tail_fits = tl.s > 1 && slab_bytes >= igemm_tail_bytes(tl, tiles.wide);
+    if (tiles.wide_for_tail && !tail_fits) {
+        tiles = igemm_choose_tiles(p, false);
+        tl = igemm_choose_tail(p, tiles);
+        tail_fits = tl.s > 1 && slab_bytes >= igemm_tail_bytes(tl, tiles.wide);
+    }
+    if (tiles.tall) return 0;
+    return tail_fits ? CGS_UPDATE_TAIL : CGS_UPDATE_EPILOGUE;
+}
+
+// TW: the kernel twin -- 0 igemm_kernel, 1 igemm_ns_kernel (norm-backward sums), 2 igemm_up_kernel (fused momentum update)
+template <int BM, int BN, int NW, bool VEC, int TBK, bool PAR, int TW>
 static int launch_cfg(const IgemmParams& p, hipStream_t s) {
-    void (*const kern)(IgemmParams) = NS ? igemm_ns_kernel<BM, BN, NW, VEC, TBK, PAR> : igemm_kernel<BM, BN, NW, VEC, TBK, PAR>;
+    void (*kern)(IgemmParams);
+    if constexpr (TW == 2) kern = igemm_up_kernel<BM, BN, NW, VEC, TBK, PAR>;
+    else if constexpr (TW == 1) kern = igemm_ns_kernel<BM, BN, NW, VEC, TBK, PAR>;
+    else kern = igemm_kernel<BM, BN, NW, VEC, TBK, PAR>;
     constexpr int EH = (VEC && TBK == 16) ? 2 : 1;
     constexpr int WM = BM / 64;
     constexpr size_t kloop_f = (size_t)2 * BM * (TBK + 4) + 2 * TBK * BN, stage_f = (size_t)NW * (BM / WM / EH) * (BN / (NW / WM) + 4);
@@ -1273,7 +1341,8 @@ static int launch_cfg(const IgemmParams& p, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3((unsigned)gx, gy, p.splitk > 1 ? p.splitk : 1), dim3(64 * NW), smem, s, q);
     CGS_CHECK_LAUNCH("igemm");
     if (p.tail_s > 1) {
-        hipLaunchKernelGGL(tail_reduce_kernel, dim3((unsigned)p.tail_n, TAIL_RSPLIT), dim3(256), 0, s, q, BM, BN);
+        if (p.up_mom) hipLaunchKernelGGL(tail_reduce_kernel<true>, dim3((unsigned)p.tail_n, TAIL_RSPLIT), dim3(256), 0, s, q, BM, BN);
+        else hipLaunchKernelGGL(tail_reduce_kernel<false>, dim3((unsigned)p.tail_n, TAIL_RSPLIT), dim3(256), 0, s, q, BM, BN);
         CGS_CHECK_LAUNCH("tail_reduce");
     }
     if (p.splitk > 1) {
@@ -1281,12 +1350,13 @@ static int launch_cfg(const IgemmParams& p, hipStream_t s) {
         for (int i = 0; i < p.nclasses; ++i) { long t = (long)p.B * p.cls[i].R * p.cls[i].C * (p.Np / 4); if (t > tot) tot = t; }
         unsigned rb = (unsigned)((tot + 63) / 64 > 4096 ? 4096 : (tot + 63) / 64);       // 64 output quads per 256-thread block
         if (p.stat_part) hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3((unsigned)p.stat_cls_rows, (unsigned)((p.N + 31) / 32), p.nclasses), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rb, p.nclasses), dim3(256), 0, s, p);
+        else if (p.up_mom) hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3(rb, p.nclasses), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(rb, p.nclasses), dim3(256), 0, s, p);
         CGS_CHECK_LAUNCH("splitk_reduce");
     }
     // the name rocprofv3 prints for this instantiation
     static char name[64];
-    snprintf(name, sizeof(name), "%s<%d, %d, %d, %s, %d, %s>", NS ? "igemm_ns_kernel" : "igemm_kernel", BM, BN, NW, VEC ? "true" : "false", TBK, PAR ? "true" : "false");
+    snprintf(name, sizeof(name), "%s<%d, %d, %d, %s, %d, %s>", TW == 2 ? "igemm_up_kernel" : TW == 1 ? "igemm_ns_kernel" : "igemm_kernel", BM, BN, NW, VEC ? "true" : "false", TBK, PAR ? "true" : "false");
     cgs_note_kernel(name);
     return CGS_OK;
 }
@@ -1458,13 +1528,23 @@ int cgs_igemm_launch(const IgemmParams& p_in, void* slab, size_t slab_bytes, hip
     bool half = vec && wide && deep && p.splitk > 1 && !p.tap_parity && (long)p.B * maxRC <= 64;
     // (a launch that leaves the norm-backward sums runs the igemm_ns_kernel twin of its tile; every other launch the kernel of the rounds before)
     const bool ns = p.stat_part && p.ns_mean;
-#define LC(...) (ns ? launch_cfg<__VA_ARGS__, true>(p, s) : launch_cfg<__VA_ARGS__, false>(p, s))
+    // (the fused momentum update: the igemm_up_kernel twin of the four VEC tiles -- a split-K launch leaves raw slabs from the plain kernel and
+    // updates in splitk_reduce_kernel<true>; what cgs_igemm_update_form said for this geometry must be what was planned here)
+    if (p.up_mom) {
+        const int form = p.splitk > 1 ? CGS_UPDATE_SPLITK : (p.tail_s > 1 ? CGS_UPDATE_TAIL : CGS_UPDATE_EPILOGUE);
+        if (!vec || tall || cgs_igemm_update_form(p_in, slab ? slab_bytes : 0) != form)
+            return cgs_set_error(CGS_EINVAL, "igemm: the fused update is not offered for this launch (cgs_conv_update_form)");
+    }
+    const bool upk = p.up_mom && p.splitk == 1;
+#define LC(...) (ns ? launch_cfg<__VA_ARGS__, 1>(p, s) : launch_cfg<__VA_ARGS__, 0>(p, s))
+#define LCU(...) (upk ? launch_cfg<__VA_ARGS__, 2>(p, s) : LC(__VA_ARGS__))
     if (half) return LC(64, 128, 4, true, 32, false);
     if (tall) return p.tap_parity ? LC(256, 64, 4, true, 16, true) : LC(256, 64, 4, true, 16, false);
-    if (vec && !deep && !p.tap_parity) return wide ? LC(128, 128, 4, true, 16, false) : LC(128, 64, 4, true, 16, false);
-    if (vec && !deep && p.tap_parity) return wide ? LC(128, 128, 4, true, 16, true) : LC(128, 64, 4, true, 16, true);
-    if (vec && p.tap_parity) return wide ? LC(128, 128, 4, true, 32, true) : LC(128, 64, 4, true, 32, true);
-    if (vec) return wide ? LC(128, 128, 4, true, 32, false) : LC(128, 64, 4, true, 32, false);
+    if (vec && !deep && !p.tap_parity) return wide ? LCU(128, 128, 4, true, 16, false) : LCU(128, 64, 4, true, 16, false);
+    if (vec && !deep && p.tap_parity) return wide ? LCU(128, 128, 4, true, 16, true) : LCU(128, 64, 4, true, 16, true);
+    if (vec && p.tap_parity) return wide ? LCU(128, 128, 4, true, 32, true) : LCU(128, 64, 4, true, 32, true);
+    if (vec) return wide ? LCU(128, 128, 4, true, 32, false) : LCU(128, 64, 4, true, 32, false);
     return wide ? LC(128, 128, 4, false, 16, false) : LC(128, 64, 4, false, 16, false);
+#undef LCU
 #undef LC
 }

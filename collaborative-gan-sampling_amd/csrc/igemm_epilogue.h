@@ -121,3 +121,47 @@ __device__ __forceinline__ void epilogue_rows(const IgemmParams& p, const float*
         }
     }
 }
+
+// Row pass of the update twin (IgemmParams::up_*): the staged value g = acc + bias is the gradient w.r.t. the refined feature; it is not
+// stored -- the lane applies the momentum step (refine_update1, cgs_internal.h: elementwise.hip's refine_update_kernel, element by element)
+// to its 4 channels of theta (p.out) and the momentum buffer (p.up_mom) at the address g would have gone to.  The rows go in groups of UPU
+// as the norm-backward sums' x loads do, and for the same reason: the compiler may not move a row's loads above the row before's stores (it
+// cannot know that theta and the momentum buffer do not overlap), so a group's loads are issued first, then its rows are updated and stored.
+template <int ROWS, int RPP, int LDE, int UPU>
+__device__ __forceinline__ void epilogue_rows_update(const IgemmParams& p, const float* E, const int* rowpix_tile, int rsub, int c4, int n,
+                                                     f32x4 bias) {
+    constexpr int ITERS = ROWS / RPP;
+    static_assert(ITERS % UPU == 0, "row groups");
+    const float rate = p.up_rate, alpha = p.up_alpha;
+    const int first = p.up_first;
+#pragma unroll
+    for (int it0 = 0; it0 < ITERS; it0 += UPU) {
+        f32x4 th[UPU], mo[UPU];
+        int pixs[UPU];
+#pragma unroll
+        for (int u = 0; u < UPU; ++u) {
+            pixs[u] = rowpix_tile[(it0 + u) * RPP + rsub];
+            th[u] = mo[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (pixs[u] >= 0) {
+                const size_t o = (size_t)pixs[u] * p.N + n;
+                th[u] = *(const f32x4*)(p.out + o);
+                mo[u] = *(const f32x4*)(p.up_mom + o);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UPU; ++u) {
+            if (pixs[u] < 0) continue;
+            const f32x4 v = *(const f32x4*)(E + ((it0 + u) * RPP + rsub) * LDE + c4);
+            f32x4 t = th[u], m = mo[u];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float te = t[e], me = m[e];
+                refine_update1(v[e] + bias[e], rate, alpha, first, 0, 0.f, 0.f, te, me);
+                t[e] = te; m[e] = me;
+            }
+            const size_t o = (size_t)pixs[u] * p.N + n;
+            *(f32x4*)(p.up_mom + o) = m;
+            *(f32x4*)(p.out + o) = t;
+        }
+    }
+}

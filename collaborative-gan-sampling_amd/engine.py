@@ -87,13 +87,23 @@ class _Conv(_Stage):
             return K.conv2d_fwd_stats(x, self.w, self.b, self.part, self.s, self.s, out=self.out)
         return K.conv2d_fwd(x, self.w, self.b, self.s, self.s, self.epi, out=self.out)
 
-    def bwd(self, dy):
+    def update_form(self):
+        """Where this stage's backward-data would apply a ``K.FusedUpdate`` to its input (None: not offered; ``K.conv_update_form``)."""
+        if self.bwd_epi[0] != L.EPI_NONE or self.bwd_nstat is not None:
+            return None
+        B, H, W, Cin = self.dx.shape
+        kh, kw, _, Cout = self.w.shape
+        return K.conv_update_form(L.CONV_BWD_DATA, B, H, W, Cin, 0, 0, Cout, kh, kw, self.s, self.s)
+
+    def bwd(self, dy, update=None):
         if not self.pre_folded:
             if self.epi == L.EPI_LRELU:
                 dy = K.lrelu_bwd(dy, self.out, out=dy)
             elif self.epi == L.EPI_TANH:
                 dy = K.tanh_bwd(dy, self.out, out=dy)
         e, a, aux = self.bwd_epi
+        if update is not None:
+            return K.conv2d_bwd_data(dy, self.w, self.in_hw, self.s, self.s, update=update)
         return K.conv2d_bwd_data(dy, self.w, self.in_hw, self.s, self.s, out=self.dx, epilogue=e, ep_a=a, ep_aux=aux, nstat=self.bwd_nstat)
 
 
@@ -124,13 +134,21 @@ class _Deconv(_Stage):
         return K.deconv2d_fwd(x, self.w, self.b, self.out_hw, self.s, self.s, self.epi, self.a, self.c, out=self.out, signs=self.signs,
                               part=self.part)
 
-    def bwd(self, dy):
+    def update_form(self):
+        """As ``_Conv.update_form``."""
+        if self.bwd_epi[0] != L.EPI_NONE or self.bwd_nstat is not None or self.bwd_signs is not None:
+            return None
+        return K.conv_update_form(L.DECONV_BWD_DATA, *self.call_dims(), self.s, self.s)
+
+    def bwd(self, dy, update=None):
         if not self.pre_folded:
             if self.epi == L.EPI_AFFINE_RELU:
                 dy = K.affine_relu_bwd(dy, self.out, self.a, out=dy)
             elif self.epi == L.EPI_TANH:
                 dy = K.tanh_bwd(dy, self.out, out=dy)
         e, a, aux = self.bwd_epi
+        if update is not None:
+            return K.deconv2d_bwd_data(dy, self.w, self.in_hw, self.s, self.s, update=update)
         return K.deconv2d_bwd_data(dy, self.w, self.in_hw, self.s, self.s, out=self.dx, epilogue=e, ep_a=a, ep_aux=aux,
                                    ep_signs=self.bwd_signs, nstat=self.bwd_nstat)
 
@@ -458,20 +476,12 @@ def link_backward_fusion(stages):
         below.pre_folded = True
 
 
-# Largest norm input (bytes) whose backward sums ride on the backward-data launch above it.  The fusion pays where launches are latency-bound
-# (the reference's batch 64, single calls of <= 256 images, config 5's 8-image batches: -0.7 ... -2.8 % per call); on the
-# matrix-bound launches of the big batches (dcgan64 at batch 1024: 67 / 134 MB norm inputs) it is a wash -- the sums twin's dearer epilogue and the
-# saved pass cancel, -0.2 % +- the noise of a same-process A/B (profiles/r06_m_*, r06_o_*) -- and those launches would merely move from the
-# headline's dominant kernel to its twin's name in every kernel table.
-NSTAT_MAX_BYTES = 48 * 2 ** 20
-
-
 def link_norm_backward_stats(stages, B):
     """For each norm stage (batch statistics, per logical batch or per sample) whose successor is a conv / deconv stage: that stage's
     backward-data launch produces the gradient at the norm's output, so it can leave the norm backward's two column sums in its
     epilogue (include/cgs_hip.h, cgs_*_bwd_data_nstats) -- the norm's own sums pass over dy and x, 2 of its 5 tensor passes, is gone.
     Only where the library offers it for the call (exact-fp32 implicit GEMM, groups that end on 64-row boundaries of the launch's row
-    order); everything else keeps the three-kernel backward.  Call after the norms' groups are final (set_groups re-allocates the
+    order) -- at every size: the library's own "not available" is the only limit; everything else keeps the three-kernel backward.  Call after the norms' groups are final (set_groups re-allocates the
     saved statistics)."""
     for below, above in zip(stages[:-1], stages[1:]):
         if isinstance(below, _Residual):
@@ -485,8 +495,6 @@ def link_norm_backward_stats(stages, B):
         else:
             continue
         C = below.out.shape[-1]
-        if below.out.numel() * 4 > NSTAT_MAX_BYTES:
-            continue
         if isinstance(above, _Conv):
             H, W, Cin = above.dx.shape[1:]
             kh, kw, _, Cout = above.w.shape
@@ -513,10 +521,12 @@ class Tape:
             x = st.fwd(x)
         return x
 
-    def backward(self, dy):
-        for st in reversed(self.stages):
+    def backward(self, dy, update=None):
+        """``update`` (a K.FusedUpdate): the first stage's backward-data applies it instead of storing the gradient w.r.t. the tape's input
+        (only where that stage's ``update_form()`` offers it); returns None then."""
+        for st in reversed(self.stages[1:]):
             dy = st.bwd(dy)
-        return dy
+        return self.stages[0].bwd(dy) if update is None else self.stages[0].bwd(dy, update=update)
 
 
 # ----------------------------------------------------------------------------- the loop
@@ -626,6 +636,15 @@ class RefineEngine:
         drop_partials(self.d.stages); drop_partials(self.g_tail.stages)
         # the norm backward's column sums ride on the backward-data launch of the conv above (across the G-tail / D seam too)
         link_norm_backward_stats(self.g_tail.stages + self.d.stages, B)
+        # The momentum / sgd step rides on the backward-data launch that produces its gradient -- the G tail's first layer -- where the library
+        # offers that (K.conv_update_form; asked here, before any capture).  ``fused_update = False`` keeps the separate cgs_refine_update launch
+        # and leaves the feature gradient in that stage's ``dx`` (a caller that wants to read it; A/B measurements); a clip (vmin / vmax) and
+        # the ladam rule always take the separate kernels.
+        first = self.g_tail.stages[0]
+        self.update_form = first.update_form() if isinstance(first, (_Conv, _Deconv)) else None
+        # (not by default where the launch's TAIL tiles are split over K: the update then runs in two places, the twin's epilogue and the tail
+        # reduce pass, and mnist 32 x 64 measured +-0 with it -- 72.51 -> 72.67 ms per step inside a +-0.2 ms noise floor)
+        self.fused_update = self.update_form is not None and self.update_form[0] != "tail"
 
     # -- parameters changed under the engine ---------------------------------------------------
     def _sync_weights(self):
@@ -752,9 +771,10 @@ class RefineEngine:
             K.refine_loss_seed(logits, loss, self.dlogits, logit_out, ladam, first)
         return logits
 
-    def backward_to_feature(self):
-        """d sum_b loss(logit_b) / d theta for the loss of the last ``forward_logits``, through D then the G tail (collaborator.py:31)."""
-        return self.g_tail.backward(self.d.backward(self.dlogits))
+    def backward_to_feature(self, update=None):
+        """d sum_b loss(logit_b) / d theta for the loss of the last ``forward_logits``, through D then the G tail (collaborator.py:31).
+        ``update``: see ``Tape.backward``."""
+        return self.g_tail.backward(self.d.backward(self.dlogits), update=update)
 
     @_entry
     def compute_forward_logits_and_grad(self, feature, loss="bce"):
@@ -776,7 +796,13 @@ class RefineEngine:
         self.best_step.fill_(1.0)                                   # collaborator.py:60 (starts at 1)
         self.tickets.zero_()                                        # (already zero unless an earlier call died between its launches)
         forced = self.forced if probabilistic else None
+        fused = self.fused_update and self.update_form is not None and ladam is None and not (vmin and vmax)     # (the clip: refine_update's own test)
         for i in range(steps):
+            if fused:                                               # the update is the epilogue of the last backward-data launch
+                self.backward_to_feature(update=K.FusedUpdate(th, self.mom, rate, alpha, first=(i == 0)))
+                self.forward_logits(th, self.logit, loss, ladam, False)
+                K.refine_select2(render, self.images, th, self.best_theta, self.logit, forced, i, self.best_logit, self.best_step, self.tickets)
+                continue
             g = self.backward_to_feature()
             if ladam is None:
                 K.refine_update(th, self.mom, g, rate, alpha, first=(i == 0), vmin=vmin, vmax=vmax)
@@ -827,7 +853,7 @@ class RefineEngine:
                     self.mean_square = torch.empty_like(self.mom)
                 ladam = self._ladam
                 ladam.set_real(real_sigmoid_mean)                   # a device scalar the seed launches read: a new value replays the same graph
-            key = (steps, float(rate), alpha, prob, vmin, vmax, loss, method)
+            key = (steps, float(rate), alpha, prob, vmin, vmax, loss, method, bool(self.fused_update))
             if not self.use_graph:
                 self._program(steps, rate, alpha, prob, vmin, vmax, loss, ladam)
             else:

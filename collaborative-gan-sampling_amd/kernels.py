@@ -301,14 +301,58 @@ class NormBwdStats:
         return (_ptr(self.x), _ptr(self.mean), _ptr(self.invstd), _ptr(self.gamma), _ptr(self.beta), self.leak, self.group_images)
 
 
-def conv2d_bwd_data(dy, w, in_hw, sh=2, sw=2, out=None, epilogue=L.EPI_NONE, ep_a=None, ep_aux=None, nstat=None):
+class FusedUpdate:
+    """What a backward-data call needs to apply the refinement loop's momentum / sgd step INSTEAD of storing its result (include/cgs_hip.h,
+    cgs_*_bwd_data_update): the result is the gradient w.r.t. ``theta``; ``theta`` and the momentum buffer ``m`` (its shape) are updated in
+    place exactly as ``refine_update`` without a clip would.  Only where ``conv_update_form`` offers it for the call."""
+    __slots__ = ("theta", "m", "rate", "alpha", "first")
+
+    def __init__(self, theta, m, rate, alpha, first):
+        self.theta, self.m, self.rate, self.alpha, self.first = _chk(theta, "theta"), _chk(m, "m"), float(rate), float(alpha), bool(first)
+
+    def args(self):
+        return (self.rate, self.alpha, 1 if self.first else 0)
+
+
+UPDATE_FORMS = {0: None, 1: "epilogue", 2: "splitk", 3: "tail"}
+
+
+def conv_update_form(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw):
+    """Where the backward-data call ``op`` (CONV_BWD_DATA / DECONV_BWD_DATA; arguments as the entry point's) would apply a ``FusedUpdate``:
+    ("epilogue" | "splitk" | "tail", row order 0 / 1 / 2 of the launch), or None when the library does not offer it for the call
+    (include/cgs_hip.h, cgs_conv_update_form).  Answers for the workspace ``WS`` hands that call."""
+    import ctypes as C
+    _, nbytes = WS.plan(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, L.EPI_NONE)
+    order = C.c_int(0)
+    form = int(L.load().cgs_conv_update_form(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, nbytes, C.addressof(order)))
+    return (UPDATE_FORMS[form], order.value) if form > 0 else None
+
+
+def _update_nbytes(dy, w, update):
+    # dy and w once, theta read and written, m written (and read from the second step on); the gradient itself never goes to memory
+    return _nb(dy, w, update.theta, update.theta, update.m) + (0.0 if update.first else _nb(update.m))
+
+
+def conv2d_bwd_data(dy, w, in_hw, sh=2, sw=2, out=None, epilogue=L.EPI_NONE, ep_a=None, ep_aux=None, nstat=None, update=None):
     """Input gradient of conv2d_fwd (Conv2DBackpropInput; sampling/collaborator.py:31).
     ``epilogue`` = one of the *_BWD modes folds the activation gradient of the layer below in.
-    ``nstat`` (a NormBwdStats; no epilogue): the result is the gradient at the output of a norm -- leave that norm's backward sums too."""
+    ``nstat`` (a NormBwdStats; no epilogue): the result is the gradient at the output of a norm -- leave that norm's backward sums too.
+    ``update`` (a FusedUpdate; no epilogue, no nstat): the gradient is not stored, the momentum step is applied instead; returns None."""
     _chk(dy, "dy"); _chk(w, "w")
     kh, kw, Cin, Cout = w.shape
     B = dy.shape[0]
     H, W = in_hw
+    if update is not None:
+        if epilogue != L.EPI_NONE or nstat is not None or tuple(update.theta.shape) != (B, H, W, Cin) or update.m.shape != update.theta.shape:
+            raise L.CgsError("conv2d_bwd_data: the fused update comes with no epilogue, on theta and m of the gradient's shape")
+        ws, pre = WS.get(w, L.CONV_BWD_DATA, kh, kw, sh, sw, Cin, Cout, (B, H, W), epilogue, ptrs=(_ptr(dy), _ptr(update.theta), _ptr(update.m)))
+        pr = _Prof(2.0 * B * dy.shape[1] * dy.shape[2] * Cout * kh * kw * Cin, f"conv_bwd {H}x{W} {Cin}<-{Cout}",
+                   _update_nbytes(dy, w, update)) if PROFILE is not None else None
+        L.call("cgs_conv2d_nhwc_bwd_data_update", _ptr(dy), _ptr(w), _ptr(update.theta), _ptr(update.m), B, H, W, Cin, Cout, kh, kw, sh, sw,
+               *update.args(), _ptr(ws), ws.numel() * 4, pre, _stream())
+        if pr is not None:
+            pr.done()
+        return None
     dx = out if out is not None else torch.empty((B, H, W, Cin), dtype=torch.float32, device=dy.device)
     ws, pre = WS.get(w, L.CONV_BWD_DATA, kh, kw, sh, sw, Cin, Cout, (B, H, W), epilogue,
                      ptrs=(_ptr(dy), _ptr(dx), _ptr(ep_a), _ptr(ep_aux)))
@@ -365,14 +409,26 @@ def deconv2d_fwd(x, w, bias, out_hw, sh=2, sw=2, epilogue=L.EPI_NONE, ep_a=None,
     return y
 
 
-def deconv2d_bwd_data(dy, w, in_hw, sh=2, sw=2, out=None, epilogue=L.EPI_NONE, ep_a=None, ep_aux=None, ep_signs=None, nstat=None):
+def deconv2d_bwd_data(dy, w, in_hw, sh=2, sw=2, out=None, epilogue=L.EPI_NONE, ep_a=None, ep_aux=None, ep_signs=None, nstat=None, update=None):
     """Input gradient of deconv2d_fwd: a strided 'SAME' conv of dy with the deconv weights.
     ``ep_signs``: the sign mask of the saved activation instead of ``ep_aux`` (relu' / lrelu' epilogues, where ``conv_signs_ok``).
-    ``nstat``: as in conv2d_bwd_data."""
+    ``nstat``, ``update``: as in conv2d_bwd_data."""
     _chk(dy, "dy"); _chk(w, "w")
     kh, kw, Cout, Cin = w.shape
     B, Ho, Wo, _ = dy.shape
     H, W = in_hw
+    if update is not None:
+        if epilogue != L.EPI_NONE or nstat is not None or ep_signs is not None or tuple(update.theta.shape) != (B, H, W, Cin) \
+                or update.m.shape != update.theta.shape:
+            raise L.CgsError("deconv2d_bwd_data: the fused update comes with no epilogue, on theta and m of the gradient's shape")
+        ws, pre = WS.get(w, L.DECONV_BWD_DATA, kh, kw, sh, sw, Cin, Cout, (B, H, W), epilogue, (Ho, Wo),
+                         ptrs=(_ptr(dy), _ptr(update.theta), _ptr(update.m)))
+        pr = _Prof(2.0 * B * H * W * Cin * kh * kw * Cout, f"deconv_bwd {H}x{W} {Cin}<-{Cout}", _update_nbytes(dy, w, update)) if PROFILE is not None else None
+        L.call("cgs_deconv2d_nhwc_bwd_data_update", _ptr(dy), _ptr(w), _ptr(update.theta), _ptr(update.m), B, H, W, Cin, Ho, Wo, Cout, kh, kw,
+               sh, sw, *update.args(), _ptr(ws), ws.numel() * 4, pre, _stream())
+        if pr is not None:
+            pr.done()
+        return None
     dx = out if out is not None else torch.empty((B, H, W, Cin), dtype=torch.float32, device=dy.device)
     ws, pre = WS.get(w, L.DECONV_BWD_DATA, kh, kw, sh, sw, Cin, Cout, (B, H, W), epilogue, (Ho, Wo),
                      ptrs=(_ptr(dy), _ptr(dx), _ptr(ep_a), _ptr(ep_aux)))

@@ -231,6 +231,34 @@ int cgs_deconv2d_nhwc_bwd_data(const float* dy, const float* w, float* dx,
                                int epilogue, const float* ep_a, const float* ep_aux,
                                void* ws, size_t ws_bytes, int ws_prepacked, void* stream);
 
+/* ---- the refinement loop's momentum step inside the backward-data launch that produces its gradient ------------------------------
+ * sampling/collaborator.py:31,66 descends theta along g = d loss / d theta, and g is the RESULT of the backward-data pass of the
+ * generator tail's first layer; it serves nothing but cgs_refine_update (below), which reads g, theta and m and writes theta and m in a
+ * launch of its own.  cgs_conv2d_nhwc_bwd_data_update / cgs_deconv2d_nhwc_bwd_data_update are cgs_conv2d_nhwc_bwd_data /
+ * cgs_deconv2d_nhwc_bwd_data (no epilogue) that do not store g: at the element g[i] would have gone to they apply
+ *     m[i] <- first ? rate * g[i] : alpha * m[i] + rate * g[i];   theta[i] <- theta[i] - m[i]
+ * -- cgs_refine_update without the clip, the same separately rounded operations on the same fp32 value of g: theta and m come out
+ * bit-identical to the two-launch form.  theta and m have the shape of dx, 16-byte aligned.
+ * cgs_conv_update_form (op = CGS_CONV_BWD_DATA / CGS_DECONV_BWD_DATA; arguments as the entry point's) says BEFORE the call -- and before a
+ * graph capture -- where the update would be applied: in the implicit GEMM's own epilogue, or in the reduce pass of a launch that is split
+ * over K or whose tail tiles are; 0 = not offered (another kernel family or contraction mode, Cin % 4 != 0, a reduction that is not whole
+ * 32-channel chunks, the 256 x 64 tile, a batch the library would split): the entry point then returns CGS_EINVAL and touches neither
+ * theta nor m -- use the plain backward-data + cgs_refine_update.  *row_order (may be NULL): the launch's GEMM row order, 0 = (image,
+ * pixel), 1 = (pixel, image), 2 = (pixel, image) in whole 128-image tiles. */
+#define CGS_UPDATE_EPILOGUE 1   /* the igemm_up_kernel twin's epilogue                          */
+#define CGS_UPDATE_SPLITK 2     /* the reduce pass of a launch split over K                     */
+#define CGS_UPDATE_TAIL 3       /* the twin's epilogue, and the reduce pass of the tail tiles   */
+int cgs_conv_update_form(int op, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw,
+                         size_t ws_bytes, int* row_order);
+int cgs_conv2d_nhwc_bwd_data_update(const float* dy, const float* w, float* theta, float* m,
+                                    int B, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw,
+                                    float rate, float alpha, int first,
+                                    void* ws, size_t ws_bytes, int ws_prepacked, void* stream);
+int cgs_deconv2d_nhwc_bwd_data_update(const float* dy, const float* w, float* theta, float* m,
+                                      int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw,
+                                      float rate, float alpha, int first,
+                                      void* ws, size_t ws_bytes, int ws_prepacked, void* stream);
+
 /* ---- sign masks -------------------------------------------------------------------------------------------------------
  * d relu / d lrelu need ONE BIT of the saved activation (is it > 0), not the fp32 tensor: where the consumer of that
  * gradient is an HBM-bound kernel -- the backward-data of the generator's last, 3-channel deconv (a strided conv of the
