@@ -5,10 +5,12 @@ nothing else: every FLOP below runs in libcgs_hip.so.  Activations are NHWC fp32
 layouts are the reference's (nsgan/ops.py:39,51,76).  Packed-weight workspaces are cached per
 (weight storage, version, op): frozen weights are packed once.
 """
+import ctypes
 import math
 import operator
 import weakref
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -24,12 +26,37 @@ def _chk(t, name):
     return t
 
 
+def _typed(t, who, name, dtype, shape, device=None):
+    """The one typed-tensor check: a contiguous ``dtype`` tensor of exactly ``shape`` on the GPU (on ``device`` when given)."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)
+            and (device is None or t.device == device)):
+        raise L.CgsError(f"{who}: {name} must be a contiguous {dtype} {tuple(shape)} tensor on {device or 'the GPU'}, got "
+                         f"{type(t).__name__} {getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))} {getattr(t, 'device', None)}")
+    return t
+
+
 def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+def _out(out, like_or_shape, device=None, dtype=torch.float32):
+    """``out`` if given, else a fresh tensor like a tensor / of a shape (on ``device``)."""
+    if out is not None:
+        return out
+    if isinstance(like_or_shape, torch.Tensor):
+        return torch.empty_like(like_or_shape)
+    return torch.empty(like_or_shape, dtype=dtype, device=device)
+
+
+def _stats(stats, shape, device):
+    """The (mean, invstd) pair of a norm: the caller's, or fresh fp32 tensors of ``shape``."""
+    if stats is not None:
+        return stats
+    return torch.empty(shape, dtype=torch.float32, device=device), torch.empty(shape, dtype=torch.float32, device=device)
 
 
 # ---- optional per-kernel timing (bench.py): {name: [flops, [(ev_start, ev_end), ...], executed_flops, algorithmic_bytes]} or None.
@@ -42,29 +69,26 @@ PROFILE = None
 PROFILE_BY_LAYER = False      # key the records by kernel + layer shape instead of kernel only
 
 
-class _Prof:
-    __slots__ = ("name", "flops", "e0", "nbytes", "op")
-
-    def __init__(self, flops, tag="", nbytes=0.0, op=None):
-        self.name, self.flops, self.e0, self.nbytes, self.op = tag, flops, None, nbytes, op
-        if PROFILE is not None:
-            self.e0 = torch.cuda.Event(enable_timing=True)
-            self.e0.record()
-
-    def done(self):
-        if self.e0 is not None:
-            e1 = torch.cuda.Event(enable_timing=True)
-            e1.record()
-            if self.op is not None:
-                kname, executed = self.op, self.flops
-            else:
-                kname = L.load().cgs_last_kernel().decode()        # the instantiation the dispatcher actually launched
-                executed = float(L.load().cgs_last_executed_flops()) or self.flops     # minus the skipped zero-padding taps
-            rec = PROFILE.setdefault(kname + " " + self.name if PROFILE_BY_LAYER and self.name else kname, [0.0, [], 0.0, 0.0])
-            rec[0] += self.flops
-            rec[1].append((self.e0, e1))
-            rec[2] += executed
-            rec[3] += self.nbytes
+def _launch(prof, name, *args):
+    """``L.call(name, *args)``; with ``PROFILE`` set, timed under the record ``prof()`` = (flops, algorithmic bytes, op, tag) describes:
+    keyed by ``op``, or (op None) by the kernel the dispatcher launched, plus the layer ``tag`` under ``PROFILE_BY_LAYER``.  ``prof`` is
+    a callable so that an unprofiled call formats no tag and sums no bytes."""
+    if PROFILE is None:
+        return L.call(name, *args)
+    flops, nbytes, op, tag = prof()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    L.call(name, *args)
+    e1.record()
+    executed = flops
+    if op is None:
+        op = L.load().cgs_last_kernel().decode()                           # the instantiation the dispatcher actually launched
+        executed = float(L.load().cgs_last_executed_flops()) or flops      # minus the skipped zero-padding taps
+    rec = PROFILE.setdefault(op + " " + tag if PROFILE_BY_LAYER and tag else op, [0.0, [], 0.0, 0.0])
+    rec[0] += flops
+    rec[1].append((e0, e1))
+    rec[2] += executed
+    rec[3] += nbytes
 
 
 def _nb(*tensors):
@@ -179,20 +203,109 @@ class _WsCache:
 
 
 WS = _WsCache()
-_bn_ws = {}
+
+
+class _Scratch:
+    """Scratch buffers of one kind, one per (caller's key, device, HIP stream): a kernel's scratch is ordered only with the work of the
+    stream it ran on.  A buffer holds ``max(nbytes, floor) // itemsize + pad`` elements.  Asked with a byte count it grows: a larger
+    request replaces the buffer.  Asked with a callable (a size query, made only when the key has no buffer yet) it never does: the
+    norm kernels leave sums there that ``*_param_grads`` reads in a later call, and captured hipGraphs hold the address."""
+
+    def __init__(self, dtype=torch.float32, pad=0, floor=0):
+        self._d = {}
+        self.dtype, self.itemsize, self.pad, self.floor = dtype, torch.empty(0, dtype=dtype).element_size(), pad, floor
+
+    def get(self, nbytes, device, key=()):
+        key = (*key, device.index, torch.cuda.current_stream(device).cuda_stream)
+        ws = self._d.get(key)
+        if callable(nbytes):
+            if ws is not None:
+                return ws
+            nbytes = nbytes()
+        elif ws is not None and ws.numel() * self.itemsize >= nbytes:
+            return ws
+        ws = self._d[key] = torch.empty(max(nbytes, self.floor) // self.itemsize + self.pad, dtype=self.dtype, device=device)
+        return ws
+
+    def values(self):
+        return self._d.values()
+
+
+_bn_ws, _in_ws = _Scratch(), _Scratch(pad=4)                         # keyed (C,) and (B, HW, C): fixed once made
+_wgrad_ws, _mom_ws = _Scratch(pad=4, floor=16), _Scratch(torch.float64, pad=1, floor=8)      # one per stream, grow-only
 
 
 def _bn_workspace(M, C, device):
-    key = (C, device.index, torch.cuda.current_stream(device).cuda_stream)     # one scratch area per stream
+    return _bn_ws.get(lambda: L.bn_ws_bytes(M, C), device, (C,))
 
-    ws = _bn_ws.get(key)
-    if ws is None:
-        ws = torch.empty(L.bn_ws_bytes(M, C) // 4, dtype=torch.float32, device=device)
-        _bn_ws[key] = ws
-    return ws
+
+def _in_workspace(B, HW, C, device):
+    return _in_ws.get(lambda: int(L.load().cgs_instnorm_ws_bytes(B, HW, C)), device, (B, HW, C))
 
 
 # ----------------------------------------------------------------------------- conv family
+# op -> (tag of the profile record, its arrow, is the (Ho, Wo) pair part of the entry points' geometry, {form: entry point})
+_CONV = {
+    L.CONV_FWD: ("conv_fwd", "->", False, {"plain": "cgs_conv2d_nhwc_fwd", "stats": "cgs_conv2d_nhwc_fwd_stats"}),
+    L.CONV_BWD_DATA: ("conv_bwd", "<-", False, {"plain": "cgs_conv2d_nhwc_bwd_data", "nstats": "cgs_conv2d_nhwc_bwd_data_nstats",
+                                                "update": "cgs_conv2d_nhwc_bwd_data_update"}),
+    L.DECONV_FWD: ("deconv_fwd", "->", True, {"plain": "cgs_deconv2d_nhwc_fwd", "stats": "cgs_deconv2d_nhwc_fwd_stats",
+                                              "signs": "cgs_deconv2d_nhwc_fwd_signs"}),
+    L.DECONV_BWD_DATA: ("deconv_bwd", "<-", True, {"plain": "cgs_deconv2d_nhwc_bwd_data", "nstats": "cgs_deconv2d_nhwc_bwd_data_nstats",
+                                                   "signs": "cgs_deconv2d_nhwc_bwd_data_signs", "update": "cgs_deconv2d_nhwc_bwd_data_update"}),
+}
+
+
+def _conv_call(op, form, bufs, w, geom, mid, ptrs, traffic, epilogue=L.EPI_NONE, part=None):
+    """One launch of the conv family, the Python side of ``conv_entry`` (csrc/api.hip): every entry point takes its tensors ``bufs``,
+    the geometry (``geom`` = (B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw); the conv ops' entry points and workspace plan go without
+    Ho, Wo), the form's own arguments ``mid``, the packed-weight workspace, the partial-row buffer ``part`` of a statistics form, the
+    stream.  ``ptrs``: the device pointers ``WS.get`` checks for alignment; ``traffic()``: the algorithmic bytes of the record."""
+    B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw = geom
+    what, arrow, with_out_hw, entries = _CONV[op]
+    ws, pre = WS.get(w, op, kh, kw, sh, sw, Cin, Cout, (B, H, W), epilogue, (Ho, Wo) if with_out_hw else (0, 0), ptrs=ptrs)
+    mh, mw = (H, W) if with_out_hw else (Ho, Wo)                      # the grid the contraction runs over: the strided side
+    _launch(lambda: (2.0 * B * mh * mw * Cin * Cout * kh * kw, traffic(), None, f"{what} {H}x{W} {Cin}{arrow}{Cout}"),
+            entries[form], *bufs, *(geom if with_out_hw else (B, H, W, Cin, Cout, kh, kw, sh, sw)), *mid, _ptr(ws), ws.numel() * 4, pre,
+            *(() if part is None else (_ptr(part), part.numel() * 4)), _stream())
+
+
+def _conv_fwd(op, x, w, bias, y, geom, epilogue, ep_a, ep_b, signs=None, part=None, part_ptr=()):
+    """The forward forms: plain / signs (fused epilogue, the mask behind it) and stats (no epilogue: the partial rows behind the workspace)."""
+    mid = () if part is not None else (epilogue, _ptr(ep_a), _ptr(ep_b)) + (() if signs is None else (signs.data_ptr(),))
+    _conv_call(op, "stats" if part is not None else "plain" if signs is None else "signs", (_ptr(x), _ptr(w), _ptr(bias), _ptr(y)), w, geom, mid,
+               (_ptr(x), _ptr(bias), _ptr(y)) + (part_ptr or (_ptr(ep_a), _ptr(ep_b))), lambda: _nb(x, w, y), epilogue, part)
+    return y
+
+
+def _conv_bwd_data(op, who, dy, w, geom, out, epilogue, ep_a, ep_aux, ep_signs, nstat, update):
+    """The backward-data forms: plain / signs (fused epilogue), nstats (the norm-backward sums too), update (the momentum step instead
+    of the result; returns None)."""
+    B, H, W, Cin = geom[:4]
+    if update is not None:
+        if epilogue != L.EPI_NONE or nstat is not None or ep_signs is not None or tuple(update.theta.shape) != (B, H, W, Cin) \
+                or update.m.shape != update.theta.shape:
+            raise L.CgsError(f"{who}: the fused update comes with no epilogue, on theta and m of the gradient's shape")
+        # dy and w once, theta read and written, m written (and read from the second step on); the gradient itself never goes to memory
+        _conv_call(op, "update", (_ptr(dy), _ptr(w), _ptr(update.theta), _ptr(update.m)), w, geom, update.args(),
+                   (_ptr(dy), _ptr(update.theta), _ptr(update.m)),
+                   lambda: _nb(dy, w, update.theta, update.theta, update.m) + (0.0 if update.first else _nb(update.m)))
+        return None
+    if nstat is not None and (epilogue != L.EPI_NONE or ep_signs is not None):
+        raise L.CgsError(f"{who}: norm-backward statistics come with no epilogue")
+    dx = _out(out, (B, H, W, Cin), dy.device)
+    if nstat is not None:
+        form, mid = "nstats", nstat.args()
+    elif ep_signs is not None:
+        form, mid = "signs", (epilogue, _ptr(ep_a), ep_signs.data_ptr())
+    else:
+        form, mid = "plain", (epilogue, _ptr(ep_a), _ptr(ep_aux))
+    _conv_call(op, form, (_ptr(dy), _ptr(w), _ptr(dx)), w, geom, mid, (_ptr(dy), _ptr(dx), _ptr(ep_a), _ptr(ep_aux)),
+               lambda: _nb(dy, w, dx, ep_aux if ep_signs is None else ep_signs, nstat.x if nstat is not None else None), epilogue,
+               nstat.part if nstat is not None else None)
+    return dx
+
+
 def conv2d_fwd(x, w, bias, sh=2, sw=2, epilogue=L.EPI_NONE, ep_a=None, ep_b=None, out=None):
     """tf.nn.conv2d 'SAME' + bias (+ fused epilogue).  nsgan/ops.py:41-44."""
     _chk(x, "x"); _chk(w, "w")
@@ -200,16 +313,8 @@ def conv2d_fwd(x, w, bias, sh=2, sw=2, epilogue=L.EPI_NONE, ep_a=None, ep_b=None
     kh, kw, Cin2, Cout = w.shape
     if Cin2 != Cin:
         raise L.CgsError(f"conv2d: weight Cin {Cin2} != input channels {Cin}")
-    y = out if out is not None else torch.empty((B, same_out(H, sh), same_out(W, sw), Cout), dtype=torch.float32, device=x.device)
-    ws, pre = WS.get(w, L.CONV_FWD, kh, kw, sh, sw, Cin, Cout, (B, H, W), epilogue,
-                     ptrs=(_ptr(x), _ptr(bias), _ptr(y), _ptr(ep_a), _ptr(ep_b)))
-    Ho, Wo = y.shape[1], y.shape[2]
-    pr = _Prof(2.0 * B * Ho * Wo * Cout * kh * kw * Cin, f"conv_fwd {H}x{W} {Cin}->{Cout}", _nb(x, w, y)) if PROFILE is not None else None
-    L.call("cgs_conv2d_nhwc_fwd", _ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, H, W, Cin, Cout, kh, kw, sh, sw,
-           epilogue, _ptr(ep_a), _ptr(ep_b), _ptr(ws), ws.numel() * 4, pre, _stream())
-    if pr is not None:
-        pr.done()
-    return y
+    y = _out(out, (B, same_out(H, sh), same_out(W, sw), Cout), x.device)
+    return _conv_fwd(L.CONV_FWD, x, w, bias, y, (B, H, W, Cin, y.shape[1], y.shape[2], Cout, kh, kw, sh, sw), epilogue, ep_a, ep_b)
 
 
 def conv_stat_partials(x_shape, w_shape, sh=2, sw=2):
@@ -224,11 +329,10 @@ def conv_stat_layout(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, group_image
     """Where the partial rows of every group of ``group_images`` consecutive images lie in the buffer ``conv2d_fwd_stats`` /
     ``deconv2d_fwd(part=...)`` fill: (rows_total, rows_per_seg, nseg, seg_stride), or None when the fused statistics are not
     available for the call (include/cgs_hip.h, cgs_conv_stat_layout)."""
-    import ctypes as C
     _, nbytes = WS.plan(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, L.EPI_NONE)
-    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    a, b, c = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
     rows = int(L.load().cgs_conv_stat_layout(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, int(group_images), nbytes,
-                                             C.addressof(a), C.addressof(b), C.addressof(c)))
+                                             ctypes.addressof(a), ctypes.addressof(b), ctypes.addressof(c)))
     return (rows, a.value, b.value, c.value) if rows > 0 else None
 
 
@@ -238,15 +342,12 @@ def groupnorm_lrelu_fwd_from_partials(x, part, layout, groups, scale, offset, le
     _chk(x, "x"); _chk(part, "part")
     C_ = x.shape[-1]
     Mg = x.numel() // (groups * C_)
-    y = out if out is not None else torch.empty_like(x)
-    mean, invstd = stats if stats is not None else (torch.empty((groups, C_), dtype=torch.float32, device=x.device),
-                                                     torch.empty((groups, C_), dtype=torch.float32, device=x.device))
+    y = _out(out, x)
+    mean, invstd = _stats(stats, (groups, C_), x.device)
     ws = _in_workspace(groups, Mg, C_, x.device)
-    pr = _Prof(0.0, "", _nb(x, y), op="groupnorm_lrelu_fwd_from_partials") if PROFILE is not None else None
-    L.call("cgs_groupnorm_lrelu_fwd_from_partials", _ptr(x), _ptr(part), groups, layout[1], layout[2], layout[3], _ptr(scale), _ptr(offset),
-           eps, leak, _ptr(y), _ptr(mean), _ptr(invstd), Mg, C_, _ptr(ws), ws.numel() * 4, _stream())
-    if pr is not None:
-        pr.done()
+    _launch(lambda: (0.0, _nb(x, y), "groupnorm_lrelu_fwd_from_partials", ""),
+            "cgs_groupnorm_lrelu_fwd_from_partials", _ptr(x), _ptr(part), groups, layout[1], layout[2], layout[3], _ptr(scale), _ptr(offset),
+            eps, leak, _ptr(y), _ptr(mean), _ptr(invstd), Mg, C_, _ptr(ws), ws.numel() * 4, _stream())
     return y, mean, invstd
 
 
@@ -258,15 +359,9 @@ def conv2d_fwd_stats(x, w, bias, part, sh=2, sw=2, out=None):
     kh, kw, Cin2, Cout = w.shape
     if Cin2 != Cin:
         raise L.CgsError(f"conv2d: weight Cin {Cin2} != input channels {Cin}")
-    y = out if out is not None else torch.empty((B, same_out(H, sh), same_out(W, sw), Cout), dtype=torch.float32, device=x.device)
-    ws, pre = WS.get(w, L.CONV_FWD, kh, kw, sh, sw, Cin, Cout, (B, H, W), L.EPI_NONE, ptrs=(_ptr(x), _ptr(bias), _ptr(y), _ptr(part)))
-    Ho, Wo = y.shape[1], y.shape[2]
-    pr = _Prof(2.0 * B * Ho * Wo * Cout * kh * kw * Cin, f"conv_fwd {H}x{W} {Cin}->{Cout}", _nb(x, w, y)) if PROFILE is not None else None
-    L.call("cgs_conv2d_nhwc_fwd_stats", _ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, H, W, Cin, Cout, kh, kw, sh, sw,
-           _ptr(ws), ws.numel() * 4, pre, _ptr(part), part.numel() * 4, _stream())
-    if pr is not None:
-        pr.done()
-    return y
+    y = _out(out, (B, same_out(H, sh), same_out(W, sw), Cout), x.device)
+    return _conv_fwd(L.CONV_FWD, x, w, bias, y, (B, H, W, Cin, y.shape[1], y.shape[2], Cout, kh, kw, sh, sw), L.EPI_NONE, None, None,
+                     part=part, part_ptr=(_ptr(part),))
 
 
 def bn_train_lrelu_fwd_from_partials(x, part, gamma, beta, leak=LEAK, eps=BN_EPS, out=None, stats=None):
@@ -274,15 +369,12 @@ def bn_train_lrelu_fwd_from_partials(x, part, gamma, beta, leak=LEAK, eps=BN_EPS
     _chk(x, "x")
     C = x.shape[-1]
     M = x.numel() // C
-    y = out if out is not None else torch.empty_like(x)
-    mean, invstd = stats if stats is not None else (torch.empty(C, dtype=torch.float32, device=x.device),
-                                                    torch.empty(C, dtype=torch.float32, device=x.device))
+    y = _out(out, x)
+    mean, invstd = _stats(stats, C, x.device)
     ws = _bn_workspace(M, C, x.device)
-    pr = _Prof(0.0, "", _nb(x, y), op="bn_train_lrelu_fwd_from_partials") if PROFILE is not None else None     # read x, write y
-    L.call("cgs_bn_train_lrelu_fwd_from_partials", _ptr(x), _ptr(part), part.shape[0], _ptr(gamma), _ptr(beta), eps, leak, _ptr(y),
-           _ptr(mean), _ptr(invstd), M, C, _ptr(ws), ws.numel() * 4, _stream())
-    if pr is not None:
-        pr.done()
+    _launch(lambda: (0.0, _nb(x, y), "bn_train_lrelu_fwd_from_partials", ""),                          # read x, write y
+            "cgs_bn_train_lrelu_fwd_from_partials", _ptr(x), _ptr(part), part.shape[0], _ptr(gamma), _ptr(beta), eps, leak, _ptr(y),
+            _ptr(mean), _ptr(invstd), M, C, _ptr(ws), ws.numel() * 4, _stream())
     return y, mean, invstd
 
 
@@ -321,16 +413,10 @@ def conv_update_form(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw):
     """Where the backward-data call ``op`` (CONV_BWD_DATA / DECONV_BWD_DATA; arguments as the entry point's) would apply a ``FusedUpdate``:
     ("epilogue" | "splitk" | "tail", row order 0 / 1 / 2 of the launch), or None when the library does not offer it for the call
     (include/cgs_hip.h, cgs_conv_update_form).  Answers for the workspace ``WS`` hands that call."""
-    import ctypes as C
     _, nbytes = WS.plan(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, L.EPI_NONE)
-    order = C.c_int(0)
-    form = int(L.load().cgs_conv_update_form(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, nbytes, C.addressof(order)))
+    order = ctypes.c_int(0)
+    form = int(L.load().cgs_conv_update_form(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, nbytes, ctypes.addressof(order)))
     return (UPDATE_FORMS[form], order.value) if form > 0 else None
-
-
-def _update_nbytes(dy, w, update):
-    # dy and w once, theta read and written, m written (and read from the second step on); the gradient itself never goes to memory
-    return _nb(dy, w, update.theta, update.theta, update.m) + (0.0 if update.first else _nb(update.m))
 
 
 def conv2d_bwd_data(dy, w, in_hw, sh=2, sw=2, out=None, epilogue=L.EPI_NONE, ep_a=None, ep_aux=None, nstat=None, update=None):
@@ -340,36 +426,10 @@ def conv2d_bwd_data(dy, w, in_hw, sh=2, sw=2, out=None, epilogue=L.EPI_NONE, ep_
     ``update`` (a FusedUpdate; no epilogue, no nstat): the gradient is not stored, the momentum step is applied instead; returns None."""
     _chk(dy, "dy"); _chk(w, "w")
     kh, kw, Cin, Cout = w.shape
-    B = dy.shape[0]
+    B, Ho, Wo, _ = dy.shape
     H, W = in_hw
-    if update is not None:
-        if epilogue != L.EPI_NONE or nstat is not None or tuple(update.theta.shape) != (B, H, W, Cin) or update.m.shape != update.theta.shape:
-            raise L.CgsError("conv2d_bwd_data: the fused update comes with no epilogue, on theta and m of the gradient's shape")
-        ws, pre = WS.get(w, L.CONV_BWD_DATA, kh, kw, sh, sw, Cin, Cout, (B, H, W), epilogue, ptrs=(_ptr(dy), _ptr(update.theta), _ptr(update.m)))
-        pr = _Prof(2.0 * B * dy.shape[1] * dy.shape[2] * Cout * kh * kw * Cin, f"conv_bwd {H}x{W} {Cin}<-{Cout}",
-                   _update_nbytes(dy, w, update)) if PROFILE is not None else None
-        L.call("cgs_conv2d_nhwc_bwd_data_update", _ptr(dy), _ptr(w), _ptr(update.theta), _ptr(update.m), B, H, W, Cin, Cout, kh, kw, sh, sw,
-               *update.args(), _ptr(ws), ws.numel() * 4, pre, _stream())
-        if pr is not None:
-            pr.done()
-        return None
-    dx = out if out is not None else torch.empty((B, H, W, Cin), dtype=torch.float32, device=dy.device)
-    ws, pre = WS.get(w, L.CONV_BWD_DATA, kh, kw, sh, sw, Cin, Cout, (B, H, W), epilogue,
-                     ptrs=(_ptr(dy), _ptr(dx), _ptr(ep_a), _ptr(ep_aux)))
-    Ho, Wo = dy.shape[1], dy.shape[2]
-    pr = _Prof(2.0 * B * Ho * Wo * Cout * kh * kw * Cin, f"conv_bwd {H}x{W} {Cin}<-{Cout}",
-               _nb(dy, w, dx, ep_aux, nstat.x if nstat is not None else None)) if PROFILE is not None else None
-    if nstat is not None:
-        if epilogue != L.EPI_NONE:
-            raise L.CgsError("conv2d_bwd_data: norm-backward statistics come with no epilogue")
-        L.call("cgs_conv2d_nhwc_bwd_data_nstats", _ptr(dy), _ptr(w), _ptr(dx), B, H, W, Cin, Cout, kh, kw, sh, sw, *nstat.args(),
-               _ptr(ws), ws.numel() * 4, pre, _ptr(nstat.part), nstat.part.numel() * 4, _stream())
-    else:
-        L.call("cgs_conv2d_nhwc_bwd_data", _ptr(dy), _ptr(w), _ptr(dx), B, H, W, Cin, Cout, kh, kw, sh, sw,
-               epilogue, _ptr(ep_a), _ptr(ep_aux), _ptr(ws), ws.numel() * 4, pre, _stream())
-    if pr is not None:
-        pr.done()
-    return dx
+    return _conv_bwd_data(L.CONV_BWD_DATA, "conv2d_bwd_data", dy, w, (B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw), out, epilogue, ep_a, ep_aux,
+                          None, nstat, update)
 
 
 def conv_signs_ok(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue):
@@ -389,24 +449,10 @@ def deconv2d_fwd(x, w, bias, out_hw, sh=2, sw=2, epilogue=L.EPI_NONE, ep_a=None,
     if Cin2 != Cin:
         raise L.CgsError(f"deconv2d: weight Cin {Cin2} != input channels {Cin}")
     Ho, Wo = out_hw
-    y = out if out is not None else torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-    ws, pre = WS.get(w, L.DECONV_FWD, kh, kw, sh, sw, Cin, Cout, (B, H, W), epilogue, (Ho, Wo),
-                     ptrs=(_ptr(x), _ptr(bias), _ptr(y), _ptr(ep_a), _ptr(ep_b)))
-    pr = _Prof(2.0 * B * H * W * Cin * kh * kw * Cout, f"deconv_fwd {H}x{W} {Cin}->{Cout}", _nb(x, w, y)) if PROFILE is not None else None
-    if part is not None:
-        if epilogue != L.EPI_NONE or signs is not None:
-            raise L.CgsError("deconv2d_fwd: the statistics partials are those of the plain output (no epilogue, no sign mask)")
-        L.call("cgs_deconv2d_nhwc_fwd_stats", _ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw,
-               _ptr(ws), ws.numel() * 4, pre, _ptr(part), part.numel() * 4, _stream())
-    elif signs is not None:
-        L.call("cgs_deconv2d_nhwc_fwd_signs", _ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw,
-               epilogue, _ptr(ep_a), _ptr(ep_b), signs.data_ptr(), _ptr(ws), ws.numel() * 4, pre, _stream())
-    else:
-        L.call("cgs_deconv2d_nhwc_fwd", _ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw,
-               epilogue, _ptr(ep_a), _ptr(ep_b), _ptr(ws), ws.numel() * 4, pre, _stream())
-    if pr is not None:
-        pr.done()
-    return y
+    if part is not None and (epilogue != L.EPI_NONE or signs is not None):
+        raise L.CgsError("deconv2d_fwd: the statistics partials are those of the plain output (no epilogue, no sign mask)")
+    y = _out(out, (B, Ho, Wo, Cout), x.device)
+    return _conv_fwd(L.DECONV_FWD, x, w, bias, y, (B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw), epilogue, ep_a, ep_b, signs, part)
 
 
 def deconv2d_bwd_data(dy, w, in_hw, sh=2, sw=2, out=None, epilogue=L.EPI_NONE, ep_a=None, ep_aux=None, ep_signs=None, nstat=None, update=None):
@@ -417,37 +463,8 @@ def deconv2d_bwd_data(dy, w, in_hw, sh=2, sw=2, out=None, epilogue=L.EPI_NONE, e
     kh, kw, Cout, Cin = w.shape
     B, Ho, Wo, _ = dy.shape
     H, W = in_hw
-    if update is not None:
-        if epilogue != L.EPI_NONE or nstat is not None or ep_signs is not None or tuple(update.theta.shape) != (B, H, W, Cin) \
-                or update.m.shape != update.theta.shape:
-            raise L.CgsError("deconv2d_bwd_data: the fused update comes with no epilogue, on theta and m of the gradient's shape")
-        ws, pre = WS.get(w, L.DECONV_BWD_DATA, kh, kw, sh, sw, Cin, Cout, (B, H, W), epilogue, (Ho, Wo),
-                         ptrs=(_ptr(dy), _ptr(update.theta), _ptr(update.m)))
-        pr = _Prof(2.0 * B * H * W * Cin * kh * kw * Cout, f"deconv_bwd {H}x{W} {Cin}<-{Cout}", _update_nbytes(dy, w, update)) if PROFILE is not None else None
-        L.call("cgs_deconv2d_nhwc_bwd_data_update", _ptr(dy), _ptr(w), _ptr(update.theta), _ptr(update.m), B, H, W, Cin, Ho, Wo, Cout, kh, kw,
-               sh, sw, *update.args(), _ptr(ws), ws.numel() * 4, pre, _stream())
-        if pr is not None:
-            pr.done()
-        return None
-    dx = out if out is not None else torch.empty((B, H, W, Cin), dtype=torch.float32, device=dy.device)
-    ws, pre = WS.get(w, L.DECONV_BWD_DATA, kh, kw, sh, sw, Cin, Cout, (B, H, W), epilogue, (Ho, Wo),
-                     ptrs=(_ptr(dy), _ptr(dx), _ptr(ep_a), _ptr(ep_aux)))
-    pr = _Prof(2.0 * B * H * W * Cin * kh * kw * Cout, f"deconv_bwd {H}x{W} {Cin}<-{Cout}",
-               _nb(dy, w, dx, ep_aux if ep_signs is None else ep_signs, nstat.x if nstat is not None else None)) if PROFILE is not None else None
-    if nstat is not None:
-        if epilogue != L.EPI_NONE or ep_signs is not None:
-            raise L.CgsError("deconv2d_bwd_data: norm-backward statistics come with no epilogue")
-        L.call("cgs_deconv2d_nhwc_bwd_data_nstats", _ptr(dy), _ptr(w), _ptr(dx), B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, *nstat.args(),
-               _ptr(ws), ws.numel() * 4, pre, _ptr(nstat.part), nstat.part.numel() * 4, _stream())
-    elif ep_signs is not None:
-        L.call("cgs_deconv2d_nhwc_bwd_data_signs", _ptr(dy), _ptr(w), _ptr(dx), B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw,
-               epilogue, _ptr(ep_a), ep_signs.data_ptr(), _ptr(ws), ws.numel() * 4, pre, _stream())
-    else:
-        L.call("cgs_deconv2d_nhwc_bwd_data", _ptr(dy), _ptr(w), _ptr(dx), B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw,
-               epilogue, _ptr(ep_a), _ptr(ep_aux), _ptr(ws), ws.numel() * 4, pre, _stream())
-    if pr is not None:
-        pr.done()
-    return dx
+    return _conv_bwd_data(L.DECONV_BWD_DATA, "deconv2d_bwd_data", dy, w, (B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw), out, epilogue, ep_a,
+                          ep_aux, ep_signs, nstat, update)
 
 
 def linear_fwd(x, w, bias, epilogue=L.EPI_NONE, out=None):
@@ -457,18 +474,10 @@ def linear_fwd(x, w, bias, epilogue=L.EPI_NONE, out=None):
     K2, N = w.shape
     if K2 != K:
         raise L.CgsError(f"linear: Matrix rows {K2} != input features {K}")
-    y = out if out is not None else torch.empty((B, N), dtype=torch.float32, device=x.device)
-    if N == 1:
-        pr = _Prof(2.0 * B * K, "", _nb(x, w, y), op="linear_out1_fwd") if PROFILE is not None else None
-        L.call("cgs_linear_fwd", _ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, K, N, epilogue, None, 0, 0, _stream())
-        if pr is not None:
-            pr.done()
-        return y
-    ws, pre = WS.get(w, L.CONV_FWD, 1, 1, 1, 1, K, N, (B, 1, 1), epilogue, ptrs=(_ptr(x), _ptr(bias), _ptr(y)))
-    pr = _Prof(2.0 * B * K * N, f"linear_fwd {K}->{N}", _nb(x, w, y)) if PROFILE is not None else None
-    L.call("cgs_linear_fwd", _ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, K, N, epilogue, _ptr(ws), ws.numel() * 4, pre, _stream())
-    if pr is not None:
-        pr.done()
+    y = _out(out, (B, N), x.device)
+    ws, pre = (None, 0) if N == 1 else WS.get(w, L.CONV_FWD, 1, 1, 1, 1, K, N, (B, 1, 1), epilogue, ptrs=(_ptr(x), _ptr(bias), _ptr(y)))
+    _launch(lambda: (2.0 * B * K * N, _nb(x, w, y), "linear_out1_fwd" if N == 1 else None, "" if N == 1 else f"linear_fwd {K}->{N}"),
+            "cgs_linear_fwd", _ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, K, N, epilogue, _ptr(ws), 0 if ws is None else ws.numel() * 4, pre, _stream())
     return y
 
 
@@ -476,18 +485,10 @@ def linear_bwd_data(dy, w, out=None):
     _chk(dy, "dy"); _chk(w, "w")
     B, N = dy.shape
     K = w.shape[0]
-    dx = out if out is not None else torch.empty((B, K), dtype=torch.float32, device=dy.device)
-    if N == 1:
-        pr = _Prof(2.0 * B * K, "", _nb(dy, w, dx), op="linear_out1_bwd") if PROFILE is not None else None
-        L.call("cgs_linear_bwd_data", _ptr(dy), _ptr(w), _ptr(dx), B, K, N, None, 0, 0, _stream())
-        if pr is not None:
-            pr.done()
-        return dx
-    ws, pre = WS.get(w, L.CONV_BWD_DATA, 1, 1, 1, 1, K, N, (B, 1, 1), ptrs=(_ptr(dy), _ptr(dx)))
-    pr = _Prof(2.0 * B * K * N, f"linear_bwd {K}<-{N}", _nb(dy, w, dx)) if PROFILE is not None else None
-    L.call("cgs_linear_bwd_data", _ptr(dy), _ptr(w), _ptr(dx), B, K, N, _ptr(ws), ws.numel() * 4, pre, _stream())
-    if pr is not None:
-        pr.done()
+    dx = _out(out, (B, K), dy.device)
+    ws, pre = (None, 0) if N == 1 else WS.get(w, L.CONV_BWD_DATA, 1, 1, 1, 1, K, N, (B, 1, 1), ptrs=(_ptr(dy), _ptr(dx)))
+    _launch(lambda: (2.0 * B * K * N, _nb(dy, w, dx), "linear_out1_bwd" if N == 1 else None, "" if N == 1 else f"linear_bwd {K}<-{N}"),
+            "cgs_linear_bwd_data", _ptr(dy), _ptr(w), _ptr(dx), B, K, N, _ptr(ws), 0 if ws is None else ws.numel() * 4, pre, _stream())
     return dx
 
 
@@ -498,18 +499,12 @@ def bn_train_lrelu_fwd(x, gamma, beta, leak=LEAK, eps=BN_EPS, out=None, stats=No
     _chk(x, "x")
     C = x.shape[-1]
     M = x.numel() // C
-    y = out if out is not None else torch.empty_like(x)
-    if stats is not None:
-        mean, invstd = stats
-    else:
-        mean = torch.empty(C, dtype=torch.float32, device=x.device)
-        invstd = torch.empty(C, dtype=torch.float32, device=x.device)
+    y = _out(out, x)
+    mean, invstd = _stats(stats, C, x.device)
     ws = _bn_workspace(M, C, x.device)
-    pr = _Prof(0.0, "", _nb(x, x, y), op="bn_train_lrelu_fwd") if PROFILE is not None else None     # statistics pass + apply pass
-    L.call("cgs_bn_train_lrelu_fwd", _ptr(x), _ptr(gamma), _ptr(beta), eps, leak, _ptr(y), _ptr(mean), _ptr(invstd),
-           M, C, _ptr(ws), ws.numel() * 4, _stream())
-    if pr is not None:
-        pr.done()
+    _launch(lambda: (0.0, _nb(x, x, y), "bn_train_lrelu_fwd", ""),     # statistics pass + apply pass
+            "cgs_bn_train_lrelu_fwd", _ptr(x), _ptr(gamma), _ptr(beta), eps, leak, _ptr(y), _ptr(mean), _ptr(invstd),
+            M, C, _ptr(ws), ws.numel() * 4, _stream())
     return y, mean, invstd
 
 
@@ -517,13 +512,11 @@ def bn_train_lrelu_bwd_data(dy, x, gamma, beta, mean, invstd, leak=LEAK, out=Non
     _chk(dy, "dy"); _chk(x, "x")
     C = x.shape[-1]
     M = x.numel() // C
-    dx = out if out is not None else torch.empty_like(x)
+    dx = _out(out, x)
     ws = _bn_workspace(M, C, x.device)
-    pr = _Prof(0.0, "", _nb(dy, x, dy, x, dx), op="bn_train_lrelu_bwd_data") if PROFILE is not None else None   # sums pass (dy, x) + apply pass (dy, x -> dx)
-    L.call("cgs_bn_train_lrelu_bwd_data", _ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), leak,
-           _ptr(dx), M, C, _ptr(ws), ws.numel() * 4, _stream())
-    if pr is not None:
-        pr.done()
+    _launch(lambda: (0.0, _nb(dy, x, dy, x, dx), "bn_train_lrelu_bwd_data", ""),     # sums pass (dy, x) + apply pass (dy, x -> dx)
+            "cgs_bn_train_lrelu_bwd_data", _ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), leak,
+            _ptr(dx), M, C, _ptr(ws), ws.numel() * 4, _stream())
     return dx
 
 
@@ -542,9 +535,8 @@ def bn_sync_fwd_apply(x, gamma, beta, sums, m_total, leak=LEAK, eps=BN_EPS, out=
     _chk(x, "x")
     C = x.shape[-1]
     M = x.numel() // C
-    y = out if out is not None else torch.empty_like(x)
-    mean, invstd = stats if stats is not None else (torch.empty(C, dtype=torch.float32, device=x.device),
-                                                    torch.empty(C, dtype=torch.float32, device=x.device))
+    y = _out(out, x)
+    mean, invstd = _stats(stats, C, x.device)
     ws = _bn_workspace(M, C, x.device)
     L.call("cgs_bn_sync_fwd_apply", _ptr(x), _ptr(gamma), _ptr(beta), eps, leak, sums.data_ptr(), int(m_total), _ptr(y),
            _ptr(mean), _ptr(invstd), M, C, _ptr(ws), ws.numel() * 4, _stream())
@@ -565,23 +557,11 @@ def bn_sync_bwd_apply(dy, x, gamma, beta, mean, invstd, sums, m_total, leak=LEAK
     _chk(dy, "dy"); _chk(x, "x")
     C = x.shape[-1]
     M = x.numel() // C
-    dx = out if out is not None else torch.empty_like(x)
+    dx = _out(out, x)
     ws = _bn_workspace(M, C, x.device)
     L.call("cgs_bn_sync_bwd_apply", _ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), leak,
            sums.data_ptr(), int(m_total), _ptr(dx), M, C, _ptr(ws), ws.numel() * 4, _stream())
     return dx
-
-
-_in_ws = {}
-
-
-def _in_workspace(B, HW, C, device):
-    key = (B, HW, C, device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _in_ws.get(key)
-    if ws is None:
-        ws = torch.empty(int(L.load().cgs_instnorm_ws_bytes(B, HW, C)) // 4 + 4, dtype=torch.float32, device=device)
-        _in_ws[key] = ws
-    return ws
 
 
 def instnorm_lrelu_fwd(x, scale, offset, leak=1.0, eps=BN_EPS, out=None, stats=None):
@@ -590,15 +570,12 @@ def instnorm_lrelu_fwd(x, scale, offset, leak=1.0, eps=BN_EPS, out=None, stats=N
     _chk(x, "x")
     B, C = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * C)
-    y = out if out is not None else torch.empty_like(x)
-    mean, invstd = stats if stats is not None else (torch.empty((B, C), dtype=torch.float32, device=x.device),
-                                                     torch.empty((B, C), dtype=torch.float32, device=x.device))
+    y = _out(out, x)
+    mean, invstd = _stats(stats, (B, C), x.device)
     ws = _in_workspace(B, HW, C, x.device)
-    pr = _Prof(0.0, "", _nb(x, x, y), op="instnorm_lrelu_fwd") if PROFILE is not None else None
-    L.call("cgs_instnorm_lrelu_fwd", _ptr(x), _ptr(scale), _ptr(offset), eps, leak, _ptr(y), _ptr(mean), _ptr(invstd), B, HW, C,
-           _ptr(ws), ws.numel() * 4, _stream())
-    if pr is not None:
-        pr.done()
+    _launch(lambda: (0.0, _nb(x, x, y), "instnorm_lrelu_fwd", ""),
+            "cgs_instnorm_lrelu_fwd", _ptr(x), _ptr(scale), _ptr(offset), eps, leak, _ptr(y), _ptr(mean), _ptr(invstd), B, HW, C,
+            _ptr(ws), ws.numel() * 4, _stream())
     return y, mean, invstd
 
 
@@ -606,13 +583,11 @@ def instnorm_lrelu_bwd_data(dy, x, scale, offset, mean, invstd, leak=1.0, out=No
     _chk(dy, "dy"); _chk(x, "x")
     B, C = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * C)
-    dx = out if out is not None else torch.empty_like(x)
+    dx = _out(out, x)
     ws = _in_workspace(B, HW, C, x.device)
-    pr = _Prof(0.0, "", _nb(dy, x, dy, x, dx), op="instnorm_lrelu_bwd_data") if PROFILE is not None else None
-    L.call("cgs_instnorm_lrelu_bwd_data", _ptr(dy), _ptr(x), _ptr(scale), _ptr(offset), _ptr(mean), _ptr(invstd), leak, _ptr(dx),
-           B, HW, C, _ptr(ws), ws.numel() * 4, _stream())
-    if pr is not None:
-        pr.done()
+    _launch(lambda: (0.0, _nb(dy, x, dy, x, dx), "instnorm_lrelu_bwd_data", ""),
+            "cgs_instnorm_lrelu_bwd_data", _ptr(dy), _ptr(x), _ptr(scale), _ptr(offset), _ptr(mean), _ptr(invstd), leak, _ptr(dx),
+            B, HW, C, _ptr(ws), ws.numel() * 4, _stream())
     return dx
 
 
@@ -622,20 +597,18 @@ def norm_lrelu_bwd_from_partials(dy, x, nstat, groups, out=None):
     _chk(dy, "dy"); _chk(x, "x")
     C_ = x.shape[-1]
     Mg = x.numel() // (groups * C_)
-    dx = out if out is not None else torch.empty_like(x)
+    dx = _out(out, x)
     ws = _in_workspace(groups, Mg, C_, x.device) if groups > 1 else _bn_workspace(Mg, C_, x.device)
     lay = nstat.layout
-    pr = _Prof(0.0, "", _nb(dy, x, dx), op="norm_lrelu_bwd_from_partials") if PROFILE is not None else None
-    L.call("cgs_norm_lrelu_bwd_from_partials", _ptr(dy), _ptr(x), _ptr(nstat.part), groups, lay[1], lay[2], lay[3], _ptr(nstat.gamma), _ptr(nstat.beta),
-           _ptr(nstat.mean), _ptr(nstat.invstd), nstat.leak, _ptr(dx), Mg, C_, _ptr(ws), ws.numel() * 4, _stream())
-    if pr is not None:
-        pr.done()
+    _launch(lambda: (0.0, _nb(dy, x, dx), "norm_lrelu_bwd_from_partials", ""),
+            "cgs_norm_lrelu_bwd_from_partials", _ptr(dy), _ptr(x), _ptr(nstat.part), groups, lay[1], lay[2], lay[3], _ptr(nstat.gamma), _ptr(nstat.beta),
+            _ptr(nstat.mean), _ptr(nstat.invstd), nstat.leak, _ptr(dx), Mg, C_, _ptr(ws), ws.numel() * 4, _stream())
     return dx
 
 
 def add(a, b, out=None):
     _chk(a, "a"); _chk(b, "b")
-    o = out if out is not None else torch.empty_like(a)
+    o = _out(out, a)
     L.call("cgs_add", _ptr(a), _ptr(b), _ptr(o), a.numel(), _stream())
     return o
 
@@ -643,8 +616,7 @@ def add(a, b, out=None):
 def bn_fold(gamma, beta, moving_mean, moving_var, eps=BN_EPS, out=None):
     """Inference-mode bn as a per-channel affine (a, b).  nsgan/GAN.py:87,94.  ``out`` = (a, b) to refresh in place."""
     C = gamma.numel()
-    a, b = out if out is not None else (torch.empty(C, dtype=torch.float32, device=gamma.device),
-                                        torch.empty(C, dtype=torch.float32, device=gamma.device))
+    a, b = _stats(out, C, gamma.device)
     L.call("cgs_bn_fold", _ptr(gamma), _ptr(beta), _ptr(moving_mean), _ptr(moving_var), eps, _ptr(a), _ptr(b), C, _stream())
     return a, b
 
@@ -652,7 +624,7 @@ def bn_fold(gamma, beta, moving_mean, moving_var, eps=BN_EPS, out=None):
 def affine_relu_fwd(x, a, b, out=None):
     _chk(x, "x")
     C = x.shape[-1]
-    y = out if out is not None else torch.empty_like(x)
+    y = _out(out, x)
     L.call("cgs_affine_relu_fwd", _ptr(x), _ptr(a), _ptr(b), _ptr(y), x.numel() // C, C, _stream())
     return y
 
@@ -660,7 +632,7 @@ def affine_relu_fwd(x, a, b, out=None):
 def affine_relu_bwd(dy, y, a, out=None):
     _chk(dy, "dy"); _chk(y, "y")
     C = y.shape[-1]
-    dx = out if out is not None else torch.empty_like(y)
+    dx = _out(out, y)
     L.call("cgs_affine_relu_bwd", _ptr(dy), _ptr(y), _ptr(a), _ptr(dx), y.numel() // C, C, _stream())
     return dx
 
@@ -668,7 +640,7 @@ def affine_relu_bwd(dy, y, a, out=None):
 def affine_fwd(x, a, b, out=None):
     _chk(x, "x")
     C = x.shape[-1]
-    y = out if out is not None else torch.empty_like(x)
+    y = _out(out, x)
     L.call("cgs_affine_fwd", _ptr(x), _ptr(a), _ptr(b), _ptr(y), x.numel() // C, C, _stream())
     return y
 
@@ -676,35 +648,35 @@ def affine_fwd(x, a, b, out=None):
 def affine_bwd(dy, a, out=None):
     _chk(dy, "dy")
     C = dy.shape[-1]
-    dx = out if out is not None else torch.empty_like(dy)
+    dx = _out(out, dy)
     L.call("cgs_affine_bwd", _ptr(dy), _ptr(a), _ptr(dx), dy.numel() // C, C, _stream())
     return dx
 
 
 def lrelu_fwd(x, leak=LEAK, out=None):
     _chk(x, "x")
-    y = out if out is not None else torch.empty_like(x)
+    y = _out(out, x)
     L.call("cgs_lrelu_fwd", _ptr(x), leak, _ptr(y), x.numel(), _stream())
     return y
 
 
 def lrelu_bwd(dy, y, leak=LEAK, out=None):
     _chk(dy, "dy"); _chk(y, "y")
-    dx = out if out is not None else torch.empty_like(y)
+    dx = _out(out, y)
     L.call("cgs_lrelu_bwd", _ptr(dy), _ptr(y), leak, _ptr(dx), y.numel(), _stream())
     return dx
 
 
 def tanh_fwd(x, out=None):
     _chk(x, "x")
-    y = out if out is not None else torch.empty_like(x)
+    y = _out(out, x)
     L.call("cgs_tanh_fwd", _ptr(x), _ptr(y), x.numel(), _stream())
     return y
 
 
 def tanh_bwd(dy, y, out=None):
     _chk(dy, "dy"); _chk(y, "y")
-    dx = out if out is not None else torch.empty_like(y)
+    dx = _out(out, y)
     L.call("cgs_tanh_bwd", _ptr(dy), _ptr(y), _ptr(dx), y.numel(), _stream())
     return dx
 
@@ -715,8 +687,8 @@ def bce_ones_grad_rowmean(logits, dlogits=None, logit_mean=None):
     _chk(logits, "logits")
     B = logits.shape[0]
     P = logits.numel() // B
-    dl = dlogits if dlogits is not None else torch.empty_like(logits)
-    lm = logit_mean if logit_mean is not None else torch.empty(B, dtype=torch.float32, device=logits.device)
+    dl = _out(dlogits, logits)
+    lm = _out(logit_mean, B, logits.device)
     L.call("cgs_bce_ones_grad_rowmean", _ptr(logits), _ptr(dl), _ptr(lm), B, P, _stream())
     return dl, lm
 
@@ -724,7 +696,7 @@ def bce_ones_grad_rowmean(logits, dlogits=None, logit_mean=None):
 def bce_ones_fwd(logits, out=None):
     """softplus(-logits): sigmoid_cross_entropy_with_logits(labels=1), unreduced (nsgan/GAN.py:176-177)."""
     _chk(logits, "logits")
-    o = out if out is not None else torch.empty_like(logits)
+    o = _out(out, logits)
     L.call("cgs_bce_ones_fwd", _ptr(logits), _ptr(o), logits.numel(), _stream())
     return o
 
@@ -732,7 +704,7 @@ def bce_ones_fwd(logits, out=None):
 def bce_ones_bwd(dloss, logits, out=None):
     """dloss * (sigmoid(logits) - 1)."""
     _chk(dloss, "dloss"); _chk(logits, "logits")
-    o = out if out is not None else torch.empty_like(logits)
+    o = _out(out, logits)
     L.call("cgs_bce_ones_bwd", _ptr(dloss), _ptr(logits), _ptr(o), logits.numel(), _stream())
     return o
 
@@ -741,7 +713,7 @@ def sigmoid_rowmean(logits, out=None):
     """Per-sample discriminator score: the mean over a sample's logits of sigmoid(logit), [B, 1]   (fake_sigmoids, nsgan/GAN.py:154-155)."""
     _chk(logits, "logits")
     B = logits.shape[0]
-    o = out if out is not None else torch.empty((B, 1), dtype=torch.float32, device=logits.device)
+    o = _out(out, (B, 1), logits.device)
     L.call("cgs_sigmoid_rowmean", _ptr(logits), _ptr(o), B, logits.numel() // B, _stream())
     return o
 
@@ -749,7 +721,7 @@ def sigmoid_rowmean(logits, out=None):
 def clip(x, vmin, vmax, out=None):
     """tf.clip_by_value (sampling/collaborator.py:69-70)."""
     _chk(x, "x")
-    o = out if out is not None else torch.empty_like(x)
+    o = _out(out, x)
     L.call("cgs_clip", _ptr(x), float(vmin), float(vmax), _ptr(o), x.numel(), _stream())
     return o
 
@@ -757,11 +729,9 @@ def clip(x, vmin, vmax, out=None):
 def refine_update(theta, m, g, rate, alpha, first, vmin=None, vmax=None):
     """In-place momentum / sgd step on theta (+ optional clip).  policy.py:27-37, collaborator.py:66-70."""
     use_clip = 1 if (vmin and vmax) else 0          # the reference's truthiness test (quirk Q5)
-    pr = _Prof(0.0, "", _nb(theta, theta, m, g) + (0.0 if first else _nb(m)), op="refine_update") if PROFILE is not None else None
-    L.call("cgs_refine_update", _ptr(theta), _ptr(m), _ptr(g), rate, alpha, 1 if first else 0, use_clip,
-           float(vmin or 0.0), float(vmax or 0.0), theta.numel(), _stream())
-    if pr is not None:
-        pr.done()
+    _launch(lambda: (0.0, _nb(theta, theta, m, g) + (0.0 if first else _nb(m)), "refine_update", ""),
+            "cgs_refine_update", _ptr(theta), _ptr(m), _ptr(g), rate, alpha, 1 if first else 0, use_clip,
+            float(vmin or 0.0), float(vmax or 0.0), theta.numel(), _stream())
 
 
 def refine_select(theta, logit, forced, step_index, best_theta, best_logit, best_step):
@@ -785,10 +755,8 @@ def linear_out1_bce(x, w, bias, logits, dlogits, logit_mean):
     """The one-logit head of D + the loss seed (linear_fwd(N = 1) then bce_ones_grad_rowmean) in one launch."""
     _chk(x, "x"); _chk(w, "w")
     B, K = x.shape
-    pr = _Prof(2.0 * B * K, "", _nb(x, w, logits), op="linear_out1_fwd") if PROFILE is not None else None
-    L.call("cgs_linear_out1_bce", _ptr(x), _ptr(w), _ptr(bias), _ptr(logits), _ptr(dlogits), _ptr(logit_mean), B, K, _stream())
-    if pr is not None:
-        pr.done()
+    _launch(lambda: (2.0 * B * K, _nb(x, w, logits), "linear_out1_fwd", ""),
+            "cgs_linear_out1_bce", _ptr(x), _ptr(w), _ptr(bias), _ptr(logits), _ptr(dlogits), _ptr(logit_mean), B, K, _stream())
     return logits
 
 
@@ -817,7 +785,6 @@ class LadamState:
             self.s_real.fill_(float(value))
 
     def arg(self, first):
-        import ctypes
         return ctypes.byref(L.LadamSeed(_ptr(self.s_real), _ptr(self.loss_avg), _ptr(self.gain), 1 if first else 0))
 
 
@@ -826,8 +793,8 @@ def refine_loss_seed(logits, kind, dlogits=None, logit_mean=None, ladam=None, fi
     mean logit, which is that of ``bce_ones_grad_rowmean`` bit for bit.  ``ladam``: a ``LadamState`` this launch advances by one step."""
     _chk(logits, "logits")
     B = logits.shape[0]
-    dl = dlogits if dlogits is not None else torch.empty_like(logits)
-    lm = logit_mean if logit_mean is not None else torch.empty(B, dtype=torch.float32, device=logits.device)
+    dl = _out(dlogits, logits)
+    lm = _out(logit_mean, B, logits.device)
     L.call("cgs_refine_loss_seed", _ptr(logits), _loss_kind(kind, ("bce", "lsq", "linear")), _ptr(dl), _ptr(lm), B, logits.numel() // B,
            None if ladam is None else ladam.arg(first), _stream())
     return dl, lm
@@ -837,11 +804,9 @@ def linear_out1_seed(x, w, bias, logits, dlogits, logit_mean, kind, ladam=None, 
     """``linear_out1_bce`` for any refinement loss: linear_fwd(N = 1) then ``refine_loss_seed`` in one launch."""
     _chk(x, "x"); _chk(w, "w")
     B, K = x.shape
-    pr = _Prof(2.0 * B * K, "", _nb(x, w, logits), op="linear_out1_fwd") if PROFILE is not None else None
-    L.call("cgs_linear_out1_seed", _ptr(x), _ptr(w), _ptr(bias), _ptr(logits), _ptr(dlogits), _ptr(logit_mean), B, K,
-           _loss_kind(kind, ("bce", "lsq", "linear")), None if ladam is None else ladam.arg(first), _stream())
-    if pr is not None:
-        pr.done()
+    _launch(lambda: (2.0 * B * K, _nb(x, w, logits), "linear_out1_fwd", ""),
+            "cgs_linear_out1_seed", _ptr(x), _ptr(w), _ptr(bias), _ptr(logits), _ptr(dlogits), _ptr(logit_mean), B, K,
+            _loss_kind(kind, ("bce", "lsq", "linear")), None if ladam is None else ladam.arg(first), _stream())
     return logits
 
 
@@ -864,11 +829,9 @@ def refine_update_ladam(theta, m, v, g, gain, rate, first, vmin=None, vmax=None)
     if m.numel() != theta.numel() or v.numel() != theta.numel() or g.numel() != theta.numel() or gain.numel() < B:
         raise L.CgsError("refine_update_ladam: theta, m, v and g must have one size, gain at least B elements")
     use_clip = 1 if (vmin and vmax) else 0          # the reference's truthiness test (quirk Q5)
-    pr = _Prof(0.0, "", _nb(theta, theta, m, v, g) + (0.0 if first else _nb(m, v)), op="refine_update_ladam") if PROFILE is not None else None
-    L.call("cgs_refine_update_ladam", _ptr(theta), _ptr(m), _ptr(v), _ptr(g), _ptr(gain), float(rate), 1 if first else 0, use_clip,
-           float(vmin or 0.0), float(vmax or 0.0), B, theta.numel() // B, _stream())
-    if pr is not None:
-        pr.done()
+    _launch(lambda: (0.0, _nb(theta, theta, m, v, g) + (0.0 if first else _nb(m, v)), "refine_update_ladam", ""),
+            "cgs_refine_update_ladam", _ptr(theta), _ptr(m), _ptr(v), _ptr(g), _ptr(gain), float(rate), 1 if first else 0, use_clip,
+            float(vmin or 0.0), float(vmax or 0.0), B, theta.numel() // B, _stream())
 
 
 def refine_select_rows(src, logit, forced, step_index, dst, best_logit):
@@ -880,31 +843,17 @@ def refine_select_rows(src, logit, forced, step_index, dst, best_logit):
 
 
 # ----------------------------------------------------------------------------- D shaping step (weight gradients, Adam)
-_wgrad_ws = {}
-
-
-def _wgrad_workspace(nbytes, device):
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _wgrad_ws.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = torch.empty(max(nbytes, 16) // 4 + 4, dtype=torch.float32, device=device)
-        _wgrad_ws[key] = ws
-    return ws
-
-
 def conv2d_bwd_weight(x, dy, kh, kw, sh=2, sw=2, out=None, accumulate=False):
     """dw[kh,kw,Cin,Cout] (+)= weight gradient of conv2d_fwd (Conv2DBackpropFilter)."""
     _chk(x, "x"); _chk(dy, "dy")
     B, H, W, Cin = x.shape
     Cout = dy.shape[3]
-    dw = out if out is not None else torch.empty((kh, kw, Cin, Cout), dtype=torch.float32, device=x.device)
-    ws = _wgrad_workspace(int(L.load().cgs_conv_wgrad_ws_bytes(B, H, W, Cin, Cout, kh, kw, sh, sw)), x.device)
+    dw = _out(out, (kh, kw, Cin, Cout), x.device)
+    ws = _wgrad_ws.get(int(L.load().cgs_conv_wgrad_ws_bytes(B, H, W, Cin, Cout, kh, kw, sh, sw)), x.device)
     # (the weight-gradient GEMM multiplies the zero-padding taps too: issued = nominal flops; the slab reduce rides in the same record)
-    pr = _Prof(2.0 * B * dy.shape[1] * dy.shape[2] * Cout * kh * kw * Cin, "", _nb(x, dy, dw), op="wgrad_kernel") if PROFILE is not None else None
-    L.call("cgs_conv2d_nhwc_bwd_weight", _ptr(x), _ptr(dy), _ptr(dw), B, H, W, Cin, Cout, kh, kw, sh, sw,
-           1 if accumulate else 0, _ptr(ws), ws.numel() * 4, _stream())
-    if pr is not None:
-        pr.done()
+    _launch(lambda: (2.0 * B * dy.shape[1] * dy.shape[2] * Cout * kh * kw * Cin, _nb(x, dy, dw), "wgrad_kernel", ""),
+            "cgs_conv2d_nhwc_bwd_weight", _ptr(x), _ptr(dy), _ptr(dw), B, H, W, Cin, Cout, kh, kw, sh, sw,
+            1 if accumulate else 0, _ptr(ws), ws.numel() * 4, _stream())
     return dw
 
 
@@ -921,13 +870,11 @@ def conv2d_bwd_weight_cout1(x, dy, kh, kw, sh=2, sw=2, out=None, accumulate=Fals
     B, H, W, Cin = x.shape
     if dy.shape[3] != 1:
         raise L.CgsError(f"conv2d_bwd_weight_cout1: dy has {dy.shape[3]} channels")
-    dw = out if out is not None else torch.empty((kh, kw, Cin, 1), dtype=torch.float32, device=x.device)
-    ws = _wgrad_workspace(int(L.load().cgs_conv_wgrad_cout1_ws_bytes(B, H, W, Cin, kh, kw, sh, sw)), x.device)
-    pr = _Prof(2.0 * B * dy.shape[1] * dy.shape[2] * kh * kw * Cin, "", _nb(x, dy, dw), op="wgrad_cout1_kernel") if PROFILE is not None else None
-    L.call("cgs_conv2d_nhwc_bwd_weight_cout1", _ptr(x), _ptr(dy), _ptr(dw), B, H, W, Cin, kh, kw, sh, sw,
-           1 if accumulate else 0, _ptr(ws), ws.numel() * 4, _stream())
-    if pr is not None:
-        pr.done()
+    dw = _out(out, (kh, kw, Cin, 1), x.device)
+    ws = _wgrad_ws.get(int(L.load().cgs_conv_wgrad_cout1_ws_bytes(B, H, W, Cin, kh, kw, sh, sw)), x.device)
+    _launch(lambda: (2.0 * B * dy.shape[1] * dy.shape[2] * kh * kw * Cin, _nb(x, dy, dw), "wgrad_cout1_kernel", ""),
+            "cgs_conv2d_nhwc_bwd_weight_cout1", _ptr(x), _ptr(dy), _ptr(dw), B, H, W, Cin, kh, kw, sh, sw,
+            1 if accumulate else 0, _ptr(ws), ws.numel() * 4, _stream())
     return dw
 
 
@@ -936,14 +883,11 @@ def deconv2d_bwd_weight(x, dy, kh, kw, sh=2, sw=2, out=None, accumulate=False):
     _chk(x, "x"); _chk(dy, "dy")
     B, H, W, Cin = x.shape
     _, Ho, Wo, Cout = dy.shape
-    dw = out if out is not None else torch.empty((kh, kw, Cout, Cin), dtype=torch.float32, device=x.device)
-    need = int(L.load().cgs_deconv_wgrad_ws_bytes(B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw))
-    ws = _wgrad_workspace(need, x.device)
-    pr = _Prof(2.0 * B * H * W * Cin * kh * kw * Cout, "", _nb(x, dy, dw), op="wgrad_kernel") if PROFILE is not None else None
-    L.call("cgs_deconv2d_nhwc_bwd_weight", _ptr(x), _ptr(dy), _ptr(dw), B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw,
-           1 if accumulate else 0, _ptr(ws), ws.numel() * 4, _stream())
-    if pr is not None:
-        pr.done()
+    dw = _out(out, (kh, kw, Cout, Cin), x.device)
+    ws = _wgrad_ws.get(int(L.load().cgs_deconv_wgrad_ws_bytes(B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw)), x.device)
+    _launch(lambda: (2.0 * B * H * W * Cin * kh * kw * Cout, _nb(x, dy, dw), "wgrad_kernel", ""),
+            "cgs_deconv2d_nhwc_bwd_weight", _ptr(x), _ptr(dy), _ptr(dw), B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw,
+            1 if accumulate else 0, _ptr(ws), ws.numel() * 4, _stream())
     return dw
 
 
@@ -952,12 +896,10 @@ def linear_bwd_weight(x, dy, out=None, accumulate=False):
     _chk(x, "x"); _chk(dy, "dy")
     B, K = x.shape
     N = dy.shape[1]
-    dw = out if out is not None else torch.empty((K, N), dtype=torch.float32, device=x.device)
-    ws = _wgrad_workspace(int(L.load().cgs_conv_wgrad_ws_bytes(B, 1, 1, K, N, 1, 1, 1, 1)), x.device)
-    pr = _Prof(2.0 * B * K * N, "", _nb(x, dy, dw), op="wgrad_kernel") if PROFILE is not None else None
-    L.call("cgs_linear_bwd_weight", _ptr(x), _ptr(dy), _ptr(dw), B, K, N, 1 if accumulate else 0, _ptr(ws), ws.numel() * 4, _stream())
-    if pr is not None:
-        pr.done()
+    dw = _out(out, (K, N), x.device)
+    ws = _wgrad_ws.get(int(L.load().cgs_conv_wgrad_ws_bytes(B, 1, 1, K, N, 1, 1, 1, 1)), x.device)
+    _launch(lambda: (2.0 * B * K * N, _nb(x, dy, dw), "wgrad_kernel", ""),
+            "cgs_linear_bwd_weight", _ptr(x), _ptr(dy), _ptr(dw), B, K, N, 1 if accumulate else 0, _ptr(ws), ws.numel() * 4, _stream())
     return dw
 
 
@@ -966,7 +908,7 @@ def bias_grad(dy, out=None, accumulate=False):
     _chk(dy, "dy")
     C = dy.shape[-1]
     M = dy.numel() // C
-    db = out if out is not None else torch.empty(C, dtype=torch.float32, device=dy.device)
+    db = _out(out, C, dy.device)
     if C % 4 != 0:                                   # the single-logit head: a B-element sum
         s = dy.reshape(M, C).sum(0)
         db.copy_(db + s if accumulate else s)
@@ -996,7 +938,7 @@ def instnorm_param_grads(x, dscale, doffset, accumulate=False):
 def bce_logits_grad(logits, target, scale, dlogits=None, loss=None):
     """dlogits = scale*(sigmoid(l) - target); loss[0] = scale * sum BCE(l, target)."""
     _chk(logits, "logits")
-    dl = dlogits if dlogits is not None else torch.empty_like(logits)
+    dl = _out(dlogits, logits)
     L.call("cgs_bce_logits_grad", _ptr(logits), float(target), float(scale), _ptr(dl), _ptr(loss), logits.numel(), _stream())
     return dl
 
@@ -1005,7 +947,7 @@ def gan_logits_grad(logits, kind, target, scale, dlogits=None, loss=None):
     """``bce_logits_grad`` for the GAN training loss ``kind``: "bce"; "lsq" (l - target)^2; "hinge" relu(1 - l) on real (target 1),
     relu(1 + l) on fake (target 0); "linear" -l (the generator's side of hinge).  dlogits = scale * d loss, loss[0] = scale * sum loss."""
     _chk(logits, "logits")
-    dl = dlogits if dlogits is not None else torch.empty_like(logits)
+    dl = _out(dlogits, logits)
     L.call("cgs_gan_logits_grad", _ptr(logits), _loss_kind(kind, ("bce", "lsq", "linear", "hinge")), float(target), float(scale), _ptr(dl), _ptr(loss),
            logits.numel(), _stream())
     return dl
@@ -1017,7 +959,7 @@ def gan_loss(logits, kind, target, dloss=None, out=None):
     _chk(logits, "logits")
     if dloss is not None:
         _chk(dloss, "dloss")
-    o = out if out is not None else torch.empty_like(logits)
+    o = _out(out, logits)
     L.call("cgs_gan_loss", _ptr(logits), _loss_kind(kind, ("lsq", "linear", "hinge")), float(target), _ptr(dloss), _ptr(o), logits.numel(), _stream())
     return o
 
@@ -1049,7 +991,6 @@ class AdamTable:
     device memory and built once.  Holds the tensors, so the raw addresses in the table stay valid as long as the table lives."""
 
     def __init__(self, slots):
-        import numpy as np
         self.slots = [tuple(s) for s in slots]
         if not self.slots:
             raise L.CgsError("AdamTable: no slots")
@@ -1092,16 +1033,16 @@ def bn_moving_update(mean, invstd, moving_mean, moving_var, decay, eps=BN_EPS):
 
 
 # ----------------------------------------------------------------------------- pool statistics (csrc/moments.hip)
-_mom_ws = {}
-
-
-def _moments_workspace(nbytes, device):
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)         # one scratch area per stream
-    ws = _mom_ws.get(key)
-    if ws is None or ws.numel() * 8 < nbytes:
-        ws = torch.empty(max(nbytes, 8) // 8 + 1, dtype=torch.float64, device=device)
-        _mom_ws[key] = ws
-    return ws
+def _state_call(device, query, refusal, name, *args):
+    """A launch that works in the stream's float64 scratch: under ``device``, ask ``query`` = (a ``*_ws_bytes`` entry, its arguments)
+    for the size -- 0: the library does not serve the call, ``refusal`` says so; no query: the smallest area -- take the scratch and
+    call ``name(*args, scratch, its bytes, stream)``."""
+    with torch.cuda.device(device):
+        need = int(getattr(L.load(), query[0])(*query[1:])) if query else 8
+        if need == 0:
+            raise L.CgsError(refusal)
+        ws = _mom_ws.get(need, device)
+        L.call(name, *args, _ptr(ws), ws.numel() * 8, _stream())
 
 
 def pool_moments(x, sum, gram, shift=None, rows=None):
@@ -1113,17 +1054,14 @@ def pool_moments(x, sum, gram, shift=None, rows=None):
     if x.dim() != 2:
         raise L.CgsError(f"pool_moments: x must be [n, d], got {tuple(x.shape)}")
     n, d = x.shape
-    for t, name, shape in ((sum, "sum", (d,)), (gram, "gram", (d, d))):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
-                and t.device == x.device):
-            raise L.CgsError(f"pool_moments: {name} must be a contiguous float64 {shape} tensor on {x.device}")
+    _typed(sum, "pool_moments", "sum", torch.float64, (d,), x.device)
+    _typed(gram, "pool_moments", "gram", torch.float64, (d, d), x.device)
     if shift is not None:
         _chk(shift, "shift")
         if tuple(shift.shape) != (d,) or shift.device != x.device:
             raise L.CgsError(f"pool_moments: shift must be [{d}] on {x.device}")
     m, rows_dev = n, None
     if rows is not None:
-        import numpy as np
         r = np.asarray(rows)
         if r.ndim != 1 or (r.size and r.dtype.kind not in "iu"):
             raise L.CgsError("pool_moments: rows must be a 1-D host array of integers")
@@ -1135,43 +1073,30 @@ def pool_moments(x, sum, gram, shift=None, rows=None):
         rows_dev = torch.from_numpy(np.ascontiguousarray(r, dtype=np.int32)).to(x.device)
     if m == 0:
         return
-    with torch.cuda.device(x.device):
-        need = int(L.load().cgs_pool_moments_ws_bytes(m, d))
-        if need == 0:
-            raise L.CgsError(f"pool_moments: unsupported shape (m={m}, d={d}): 1 <= d <= 2048")
-        ws = _moments_workspace(need, x.device)
-        L.call("cgs_pool_moments_accumulate", _ptr(x), n, d, _ptr(rows_dev), m, _ptr(shift), _ptr(sum), _ptr(gram), _ptr(ws), ws.numel() * 8,
-               _stream())
+    _state_call(x.device, ("cgs_pool_moments_ws_bytes", m, d), f"pool_moments: unsupported shape (m={m}, d={d}): 1 <= d <= 2048",
+                "cgs_pool_moments_accumulate", _ptr(x), n, d, _ptr(rows_dev), m, _ptr(shift), _ptr(sum), _ptr(gram))
 
 
 def spatial_mean(x, out=None):
     """[B, ..., C] -> [B, C]: the mean over every axis between the first and the last (a conv discriminator's feature map per sample)."""
     _chk(x, "x")
     B, C = x.shape[0], x.shape[-1]
-    o = out if out is not None else torch.empty((B, C), dtype=torch.float32, device=x.device)
+    o = _out(out, (B, C), x.device)
     L.call("cgs_spatial_mean", _ptr(x), _ptr(o), B, x.numel() // (B * C), C, _stream())
     return o
 
 
 # ----------------------------------------------------------------------------- the Frechet distance from two states (csrc/frechet.hip)
-def _chk_f64(t, name, shape, device=None):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == tuple(shape)
-            and (device is None or t.device == device)):
-        raise L.CgsError(f"{name}: expected a contiguous float64 {tuple(shape)} tensor on {device or 'the GPU'}, got "
-                         f"{type(t).__name__} {getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))} {getattr(t, 'device', None)}")
-    return t
-
-
 def f64_matmul(a, b, out=None, alpha=1.0, diag=0.0):
     """out = alpha * a @ b + diag * I for square float64 matrices on the GPU (d <= 2048), in double on the float64 MFMA; ``out`` must not
     be ``a`` or ``b``."""
     if not (isinstance(a, torch.Tensor) and a.dim() == 2 and a.shape[0] == a.shape[1]):
         raise L.CgsError("f64_matmul: a must be a square matrix")
     d = a.shape[0]
-    _chk_f64(a, "f64_matmul: a", (d, d))
-    _chk_f64(b, "f64_matmul: b", (d, d), a.device)
-    o = out if out is not None else torch.empty((d, d), dtype=torch.float64, device=a.device)
-    _chk_f64(o, "f64_matmul: out", (d, d), a.device)
+    _typed(a, "f64_matmul", "a", torch.float64, (d, d))
+    _typed(b, "f64_matmul", "b", torch.float64, (d, d), a.device)
+    o = _out(out, (d, d), a.device, torch.float64)
+    _typed(o, "f64_matmul", "out", torch.float64, (d, d), a.device)
     with torch.cuda.device(a.device):
         L.call("cgs_f64_matmul", _ptr(a), _ptr(b), _ptr(o), d, float(alpha), float(diag), _stream())
     return o
@@ -1185,32 +1110,22 @@ def frechet_from_moments(sum_r, gram_r, shift_r, n_r, sum_f, gram_f, shift_f, n_
         raise L.CgsError("frechet_from_moments: sum_r must be a [d] tensor")
     d, dev = sum_r.shape[0], sum_r.device
     for t, name, shape in ((sum_r, "sum_r", (d,)), (gram_r, "gram_r", (d, d)), (sum_f, "sum_f", (d,)), (gram_f, "gram_f", (d, d))):
-        _chk_f64(t, f"frechet_from_moments: {name}", shape, dev)
+        _typed(t, "frechet_from_moments", name, torch.float64, shape, dev)
     for t, name in ((shift_r, "shift_r"), (shift_f, "shift_f")):
         if t is not None:
             _chk(t, name)
             if tuple(t.shape) != (d,) or t.device != dev:
                 raise L.CgsError(f"frechet_from_moments: {name} must be [{d}] on {dev}")
-    o = out if out is not None else torch.empty(8, dtype=torch.float64, device=dev)
-    _chk_f64(o, "frechet_from_moments: out", (8,), dev)
-    with torch.cuda.device(dev):
-        need = int(L.load().cgs_frechet_ws_bytes(d))
-        if need == 0:
-            raise L.CgsError(f"frechet_from_moments: unsupported width d={d}: 1 <= d <= 2048")
-        ws = _moments_workspace(need, dev)
-        L.call("cgs_frechet_from_moments", _ptr(sum_r), _ptr(gram_r), _ptr(shift_r), int(n_r), _ptr(sum_f), _ptr(gram_f), _ptr(shift_f), int(n_f),
-               d, int(ddof), int(max_iters), _ptr(o), _ptr(ws), ws.numel() * 8, _stream())
+    o = _out(out, 8, dev, torch.float64)
+    _typed(o, "frechet_from_moments", "out", torch.float64, (8,), dev)
+    _state_call(dev, ("cgs_frechet_ws_bytes", d), f"frechet_from_moments: unsupported width d={d}: 1 <= d <= 2048",
+                "cgs_frechet_from_moments", _ptr(sum_r), _ptr(gram_r), _ptr(shift_r), int(n_r), _ptr(sum_f), _ptr(gram_f), _ptr(shift_f), int(n_f),
+                d, int(ddof), int(max_iters), _ptr(o))
     return o
 
 
 # ----------------------------------------------------------------------------- calibration / mode statistics (csrc/diagnostics.hip)
 CAL_MAX_BINS, MODE_MAX_K = 64, 64
-
-
-def _f64_dev(t, name, shape, device, who):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
-            and t.device == device):
-        raise L.CgsError(f"{who}: {name} must be a contiguous float64 {shape} tensor on {device}")
 
 
 def calibration_accumulate(p, label, edges, state):
@@ -1231,17 +1146,13 @@ def calibration_accumulate(p, label, edges, state):
     n_bins = edges.shape[0] - 1
     if not 1 <= n_bins <= CAL_MAX_BINS:
         raise L.CgsError(f"calibration_accumulate: n_bins = {n_bins} outside 1..{CAL_MAX_BINS}")
-    _f64_dev(edges, "edges", (n_bins + 1,), p.device, "calibration_accumulate")
-    _f64_dev(state, "state", (3 * (n_bins + 1) + 11,), p.device, "calibration_accumulate")
+    _typed(edges, "calibration_accumulate", "edges", torch.float64, (n_bins + 1,), p.device)
+    _typed(state, "calibration_accumulate", "state", torch.float64, (3 * (n_bins + 1) + 11,), p.device)
     n = p.shape[0]
     if n == 0:
         return
-    with torch.cuda.device(p.device):
-        need = int(L.load().cgs_calibration_ws_bytes(n, n_bins))
-        if need == 0:
-            raise L.CgsError(f"calibration_accumulate: unsupported size (n={n}, n_bins={n_bins})")
-        ws = _moments_workspace(need, p.device)
-        L.call("cgs_calibration_accumulate", _ptr(p), n, label, _ptr(edges), n_bins, _ptr(state), _ptr(ws), ws.numel() * 8, _stream())
+    _state_call(p.device, ("cgs_calibration_ws_bytes", n, n_bins), f"calibration_accumulate: unsupported size (n={n}, n_bins={n_bins})",
+                "cgs_calibration_accumulate", _ptr(p), n, label, _ptr(edges), n_bins, _ptr(state))
 
 
 def mode_stats_accumulate(x, centeroids, thres, state):
@@ -1256,17 +1167,13 @@ def mode_stats_accumulate(x, centeroids, thres, state):
     k = centeroids.shape[0]
     if not 1 <= k <= MODE_MAX_K:
         raise L.CgsError(f"mode_stats_accumulate: k = {k} outside 1..{MODE_MAX_K}")
-    _f64_dev(centeroids, "centeroids", (k, 2), x.device, "mode_stats_accumulate")
-    _f64_dev(state, "state", (k + 3,), x.device, "mode_stats_accumulate")
+    _typed(centeroids, "mode_stats_accumulate", "centeroids", torch.float64, (k, 2), x.device)
+    _typed(state, "mode_stats_accumulate", "state", torch.float64, (k + 3,), x.device)
     n = x.shape[0]
     if n == 0:
         return
-    with torch.cuda.device(x.device):
-        need = int(L.load().cgs_mode_stats_ws_bytes(n, k))
-        if need == 0:
-            raise L.CgsError(f"mode_stats_accumulate: unsupported size (n={n}, k={k})")
-        ws = _moments_workspace(need, x.device)
-        L.call("cgs_mode_stats_accumulate", _ptr(x), n, _ptr(centeroids), k, float(thres), _ptr(state), _ptr(ws), ws.numel() * 8, _stream())
+    _state_call(x.device, ("cgs_mode_stats_ws_bytes", n, k), f"mode_stats_accumulate: unsupported size (n={n}, k={k})",
+                "cgs_mode_stats_accumulate", _ptr(x), n, _ptr(centeroids), k, float(thres), _ptr(state))
 
 
 # ----------------------------------------------------------------------------- density map of a 2-D pool (csrc/kde2d.hip)
@@ -1288,30 +1195,21 @@ def kde2d_accumulate(x, axis_x, axis_y, whiten, state):
     gx, gy = axis_x.shape[0], axis_y.shape[0]
     if gx < 1 or gy < 1 or gx * gy > KDE_MAX_CELLS:
         raise L.CgsError(f"kde2d_accumulate: grid {gx} x {gy} outside 1 <= gx, gy, gx * gy <= 2^20")
-    _f64_dev(whiten, "whiten", (3,), x.device, "kde2d_accumulate")
-    _f64_dev(state, "state", (gx * gy + 1,), x.device, "kde2d_accumulate")
+    _typed(whiten, "kde2d_accumulate", "whiten", torch.float64, (3,), x.device)
+    _typed(state, "kde2d_accumulate", "state", torch.float64, (gx * gy + 1,), x.device)
     n = x.shape[0]
     if n == 0:
         return
-    with torch.cuda.device(x.device):
-        need = int(L.load().cgs_kde2d_ws_bytes(n, gx, gy))
-        if need == 0:
-            raise L.CgsError(f"kde2d_accumulate: unsupported size (n={n}, grid {gx} x {gy})")
-        ws = _moments_workspace(need, x.device)
-        L.call("cgs_kde2d_accumulate", _ptr(x), n, _ptr(axis_x), gx, _ptr(axis_y), gy, _ptr(whiten), _ptr(state), _ptr(ws), ws.numel() * 8, _stream())
+    _state_call(x.device, ("cgs_kde2d_ws_bytes", n, gx, gy), f"kde2d_accumulate: unsupported size (n={n}, grid {gx} x {gy})",
+                "cgs_kde2d_accumulate", _ptr(x), n, _ptr(axis_x), gx, _ptr(axis_y), gy, _ptr(whiten), _ptr(state))
 
 
 # ----------------------------------------------------------------------------- rejection sampling (csrc/drs.hip)
-def _dev_typed(t, name, dtype, shape, device, who):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape and t.device == device):
-        raise L.CgsError(f"{who}: {name} must be a contiguous {dtype} {shape} tensor on {device}")
-
-
 def drs_set_max(sig, state):
     """state[0] = logit(clip(max sig, 1e-14, 1 - 1e-14)): ``Rejector.set_score_max(np.amax(sig))`` on device scores (fp32, any shape, at
     least one).  ``state``: float64 [1] on the same device."""
     _chk(sig, "sig")
-    _f64_dev(state, "state", (1,), sig.device, "drs_set_max")
+    _typed(state, "drs_set_max", "state", torch.float64, (1,), sig.device)
     if sig.numel() < 1:
         raise L.CgsError("drs_set_max: no score")
     with torch.cuda.device(sig.device):
@@ -1338,20 +1236,15 @@ def drs_decide(sig, uniforms, state, groups=1, shift_percent=60.0, epsilon=1e-8,
         raise L.CgsError(f"drs_decide: shift_percent = {shift_percent} outside [0, 100]")
     if not float(epsilon) > 0.0:
         raise L.CgsError(f"drs_decide: epsilon = {epsilon} must be positive")
-    _f64_dev(uniforms, "uniforms", (n,), dev, "drs_decide")
-    _f64_dev(state, "state", (1,), dev, "drs_decide")
+    _typed(uniforms, "drs_decide", "uniforms", torch.float64, (n,), dev)
+    _typed(state, "drs_decide", "state", torch.float64, (1,), dev)
     mask = torch.empty(n, dtype=torch.uint8, device=dev)
     counts = torch.empty(groups, dtype=torch.int32, device=dev)
     P = torch.empty(n, dtype=torch.float64, device=dev) if want_p else None
     bounds = torch.empty(groups, dtype=torch.float64, device=dev) if want_bounds else None
     b = n // groups
-    with torch.cuda.device(dev):
-        need = int(L.load().cgs_drs_ws_bytes(b, groups))
-        if need == 0:
-            raise L.CgsError(f"drs_decide: unsupported size (b={b}, groups={groups})")
-        ws = _moments_workspace(need, dev)
-        L.call("cgs_drs_decide", _ptr(sig), b, groups, _ptr(uniforms), float(epsilon), q, _ptr(state), _ptr(bounds), _ptr(P), _ptr(mask), _ptr(counts),
-               _ptr(ws), ws.numel() * 8, _stream())
+    _state_call(dev, ("cgs_drs_ws_bytes", b, groups), f"drs_decide: unsupported size (b={b}, groups={groups})",
+                "cgs_drs_decide", _ptr(sig), b, groups, _ptr(uniforms), float(epsilon), q, _ptr(state), _ptr(bounds), _ptr(P), _ptr(mask), _ptr(counts))
     return mask, counts, P, bounds
 
 
@@ -1368,13 +1261,13 @@ def compact_rows(src, mask, dst, offset, take_all=None, total=None):
     row = src.numel() // n if n else max(dst.numel() // max(dst.shape[0], 1), 1)
     if n and row < 1:
         raise L.CgsError("compact_rows: empty rows")
-    _dev_typed(mask, "mask", torch.uint8, (n,), dev, "compact_rows")
+    _typed(mask, "compact_rows", "mask", torch.uint8, (n,), dev)
     groups = 1
     if take_all is not None:
         if not (isinstance(take_all, torch.Tensor) and take_all.dim() == 1 and take_all.shape[0] >= 1):
             raise L.CgsError("compact_rows: take_all must be a 1-D uint8 device tensor, one flag per group")
         groups = take_all.shape[0]
-        _dev_typed(take_all, "take_all", torch.uint8, (groups,), dev, "compact_rows")
+        _typed(take_all, "compact_rows", "take_all", torch.uint8, (groups,), dev)
         if n % groups:
             raise L.CgsError(f"compact_rows: {n} rows are not {groups} whole groups")
     offset = operator.index(offset)
@@ -1383,14 +1276,9 @@ def compact_rows(src, mask, dst, offset, take_all=None, total=None):
     if total is None:
         total = torch.empty(1, dtype=torch.int32, device=dev)
     else:
-        _dev_typed(total, "total", torch.int32, (1,), dev, "compact_rows")
-    with torch.cuda.device(dev):
-        need = int(L.load().cgs_compact_rows_ws_bytes(n)) if n else 0
-        if n and need == 0:
-            raise L.CgsError(f"compact_rows: unsupported size (n={n})")
-        ws = _moments_workspace(max(need, 8), dev)
-        L.call("cgs_compact_rows", _ptr(src), n, row, _ptr(mask), _ptr(take_all), groups, _ptr(dst), offset, dst.shape[0], _ptr(total), _ptr(ws),
-               ws.numel() * 8, _stream())
+        _typed(total, "compact_rows", "total", torch.int32, (1,), dev)
+    _state_call(dev, ("cgs_compact_rows_ws_bytes", n) if n else None, f"compact_rows: unsupported size (n={n})",
+                "cgs_compact_rows", _ptr(src), n, row, _ptr(mask), _ptr(take_all), groups, _ptr(dst), offset, dst.shape[0], _ptr(total))
     return total
 
 
@@ -1418,16 +1306,16 @@ def mh_walk(sig, uniforms, state, T, B=0, groups=1, take_all=None, fill=None, ca
         raise L.CgsError(f"mh_walk: {n} scores are not {groups} whole batches")
     if T < 0 or B < 0 or T >= 1 << 31 or B >= 1 << 31:
         raise L.CgsError(f"mh_walk: T = {T} and B = {B} must be in [0, 2^31)")
-    _f64_dev(uniforms, "uniforms", (n,), dev, "mh_walk")
-    _f64_dev(state, "state", (2,), dev, "mh_walk")
+    _typed(uniforms, "mh_walk", "uniforms", torch.float64, (n,), dev)
+    _typed(state, "mh_walk", "state", torch.float64, (2,), dev)
     if take_all is not None:
-        _dev_typed(take_all, "take_all", torch.uint8, (groups,), dev, "mh_walk")
+        _typed(take_all, "mh_walk", "take_all", torch.uint8, (groups,), dev)
     if (fill is None) != (capacity is None):
         raise L.CgsError("mh_walk: fill and capacity come together")
     if fill is None:
         fill, capacity = torch.zeros(1, dtype=torch.int64, device=dev), MH_NO_CAPACITY
     else:
-        _dev_typed(fill, "fill", torch.int64, (1,), dev, "mh_walk")
+        _typed(fill, "mh_walk", "fill", torch.int64, (1,), dev)
         capacity = operator.index(capacity)
         if capacity < 0:
             raise L.CgsError(f"mh_walk: capacity = {capacity} is negative")
@@ -1435,13 +1323,9 @@ def mh_walk(sig, uniforms, state, T, B=0, groups=1, take_all=None, fill=None, ca
     counts = torch.empty(groups, dtype=torch.int32, device=dev)
     span = torch.empty(2, dtype=torch.int64, device=dev)
     b = n // groups
-    with torch.cuda.device(dev):
-        need = int(L.load().cgs_mh_ws_bytes(b, groups))
-        if need == 0:
-            raise L.CgsError(f"mh_walk: unsupported size (b={b}, groups={groups})")
-        ws = _moments_workspace(need, dev)
-        L.call("cgs_mh_walk", _ptr(sig), b, groups, _ptr(uniforms), T, B, _ptr(take_all), _ptr(state), _ptr(fill), capacity, _ptr(rows), _ptr(counts),
-               _ptr(span), _ptr(ws), ws.numel() * 8, _stream())
+    _state_call(dev, ("cgs_mh_ws_bytes", b, groups), f"mh_walk: unsupported size (b={b}, groups={groups})",
+                "cgs_mh_walk", _ptr(sig), b, groups, _ptr(uniforms), T, B, _ptr(take_all), _ptr(state), _ptr(fill), capacity, _ptr(rows), _ptr(counts),
+                _ptr(span))
     return rows, counts, span
 
 
@@ -1456,8 +1340,8 @@ def gather_rows(src, rows, span, dst):
     n, dev = src.shape[0], src.device
     if not (isinstance(rows, torch.Tensor) and rows.dim() == 1):
         raise L.CgsError("gather_rows: rows must be a 1-D int32 device tensor")
-    _dev_typed(rows, "rows", torch.int32, (rows.shape[0],), dev, "gather_rows")
-    _dev_typed(span, "span", torch.int64, (2,), dev, "gather_rows")
+    _typed(rows, "gather_rows", "rows", torch.int32, (rows.shape[0],), dev)
+    _typed(span, "gather_rows", "span", torch.int64, (2,), dev)
     if n == 0 or rows.shape[0] == 0 or dst.shape[0] == 0:
         return
     row = src.numel() // n

@@ -30,6 +30,7 @@ import torch
 from . import checkpoint as CK
 from . import lib as L
 from .datasets import NoiseDataset
+from .kernels import _Scratch
 
 _METHODS = {"sgd": 0, "momentum": 1, "ladam": 2}
 
@@ -216,16 +217,14 @@ class DShaper:
         n = discriminator.nlayers
         self._gwp = (C.c_void_p * n)(*[t.data_ptr() for t in self.gw])
         self._gbp = (C.c_void_p * n)(*[t.data_ptr() for t in self.gb])
-        self._ws = None
+        self._ws = _Scratch(pad=4)
 
     def _run(self, real, refined, lr):
         D = self.D
         xr, xf = D._x(real), D._x(refined)
-        need = self._ws_bytes(xr.shape[0] + xf.shape[0])
-        if self._ws is None or self._ws.numel() * 4 < need:
-            self._ws = torch.empty(need // 4 + 4, dtype=torch.float32, device=D.dev)
+        ws = self._ws.get(self._ws_bytes(xr.shape[0] + xf.shape[0]), D.dev)
         L.call(self._entry, D._wp, D._bp, D.nlayers, D.nhidden, xr.data_ptr(), xr.shape[0], xf.data_ptr(), xf.shape[0],
-               float(lr), self._gwp, self._gbp, self.loss.data_ptr(), self._ws.data_ptr(), self._ws.numel() * 4,
+               float(lr), self._gwp, self._gbp, self.loss.data_ptr(), ws.data_ptr(), ws.numel() * 4,
                torch.cuda.current_stream(D.dev).cuda_stream)
         return self.loss
 
@@ -511,7 +510,7 @@ class MLPGenerator:
         self._wp, self._bp = ptrs(self.w), ptrs(self.b)
         self._gp, self._betap = ptrs(self.gamma), ptrs(self.beta)
         self._mmp, self._mvp = ptrs(self.moving_mean), ptrs(self.moving_variance)
-        self._ws = None
+        self._ws = _Scratch(pad=4)
 
     def _shape_ok(self):
         return self.w[0].shape[0] == 2 and self.w[-1].shape[1] == 2 and 2 <= self.nlayers <= 6
@@ -551,10 +550,7 @@ class MLPGenerator:
         return P
 
     def _workspace(self, B, with_backward):
-        need = self._ws_bytes(B, with_backward)
-        if self._ws is None or self._ws.numel() * 4 < need:
-            self._ws = torch.empty(need // 4 + 4, dtype=torch.float32, device=self.dev)
-        return self._ws
+        return self._ws.get(self._ws_bytes(B, with_backward), self.dev)
 
     def _ws_bytes(self, B, with_backward):
         return int(L.load().cgs_mlp2d_gen_ws_bytes(B, self.nlayers, int(with_backward)))
@@ -663,14 +659,11 @@ class WideGStep(GStep):
             raise L.CgsError(f"WideGStep: generator has {generator.nhidden} hidden units; up to 64 units the G step is GStep "
                              "(g_stepper() picks the class by width)")
         super().__init__(generator, lrg)
-        self._ws = None
+        self._ws = _Scratch(pad=4)
 
     def _workspace(self, B):
         G = self.G
-        need = int(L.load().cgs_mlp2d_wide_g_step_ws_bytes(B, G.nlayers, G.nhidden))
-        if self._ws is None or self._ws.numel() * 4 < need:
-            self._ws = torch.empty(need // 4 + 4, dtype=torch.float32, device=G.dev)
-        return self._ws
+        return self._ws.get(int(L.load().cgs_mlp2d_wide_g_step_ws_bytes(B, G.nlayers, G.nhidden)), G.dev)
 
 
 def g_stepper(generator, lrg=5e-3):
