@@ -39,14 +39,14 @@ CONV_CASES = [  # B,H,W,Cin,Cout,k,s
     (130, 8, 8, 64, 128, 5, 2),      # B >= 128, 4x4 grid: pixel-major rows + zero-tap skipping, tiles straddling 2 pixels
     (256, 16, 16, 32, 64, 5, 2),     # pixel-major, 8x8 grid, whole tiles per pixel
     (128, 6, 6, 32, 64, 4, 2),       # pixel-major with 4x4 kernels
-    (3, 64, 64, 3, 64, 5, 2),        # dcgan64 d_h0: bwd-data = LDS-patch quad kernel (32x32 quads)
+    (3, 64, 64, 3, 64, 5, 2),        # dcgan64 d_h0: bwd-data = rows form of the quad family (32x32 quads, kw * N <= 16)
     (8, 128, 128, 64, 3, 7, 1),      # c7s1-3 RGB head: stride-1 small-N VALU kernel (>= 512 tiles)
     (2, 256, 256, 16, 1, 3, 1),      # same kernel, N=1, 3x3, one channel chunk
     (32, 64, 64, 32, 4, 5, 1),       # same kernel, N=4
     (2, 32, 32, 64, 3, 7, 1),        # too few tiles for the VALU head kernel; its backward-data = LDS-patch kernel, transposed stride-1 form
     (2, 16, 32, 3, 64, 7, 1),        # c7s1-64 from RGB: LDS-patch kernel at stride 1 (K = 147)
     (3, 8, 16, 4, 32, 3, 1),         # LDS-patch, stride 1, 4 input channels
-    (2, 64, 32, 1, 32, 4, 2),        # 1 channel, 4x4 kernel, 32x16 quads -> global-load quad kernel (Ws % 32 != 0)
+    (2, 64, 32, 1, 32, 4, 2),        # 1 channel, 4x4 kernel, 32x16 quads: forward = conv_taps_kernel, bwd-data = convt_taps_kernel<2> (Ws <= 16)
     (2, 16, 64, 2, 16, 5, 2),        # 2 channels, 8x32 quads: LDS-patch kernel with a single 16-channel chunk
     (9, 16, 16, 128, 256, 5, 2),     # N = 256 (split-bf16: 128 x 256 tiles, ragged last tile), both directions eligible
     (256, 8, 8, 128, 256, 5, 2),     # the same pixel-major: whole one-pixel tiles, zero-tap skipping, heaviest-first order
