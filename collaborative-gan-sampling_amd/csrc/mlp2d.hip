@@ -8,6 +8,8 @@
 //   backward g_in[k]  = sum_j g_out[j] * W[k][j]               : lane k walks row k of the TRANSPOSED copy W^T[j][k]
 // Both LDS walks are stride-1 across lanes (conflict free).  All layers' weights (and transposes) live in LDS.
 #include "cgs_internal.h"
+#include "mlp2d_check.h"
+#include <climits>
 
 #define MLP_MAX_LAYERS 6      // all layers (and their transposes) LDS-resident: 6 layers = 133 KB of 160 KB
 #define MLP_WIDE_MAX 256      // D only (sigmoid / saliency / refiner, and the D step under its own name): 65 .. 256 units go to the sample-tile kernels of mlp2d_wide*.hip
@@ -293,12 +295,9 @@ __global__ __launch_bounds__(1024) void mlp_train_grad_kernel(MlpTrainPtrs q, in
 // max_nh: 64 for the kernels of this file; MLP_WIDE_MAX for the entry points that mlp2d_wide.hip serves past 64.  min_nh: 65 for the
 // entry point that only mlp2d_wide_train.hip serves
 static int mlp_fill(MlpParams& p, const float* const* w, const float* const* b, int nlayers, int nh, int max_nh, const char* who, int min_nh = 1) {
-    if (nlayers < 2 || nlayers > MLP_MAX_LAYERS || nh < min_nh || nh > max_nh) return cgs_set_error(CGS_EINVAL, "%s: nlayers=%d nhidden=%d (need 2..6, %d..%d)", who, nlayers, nh, min_nh, max_nh);
-    if (!w || !b) return cgs_set_error(CGS_EINVAL, "%s: null weight array", who);
-    for (int l = 0; l < nlayers; ++l) {
-        if (!w[l] || !b[l]) return cgs_set_error(CGS_EINVAL, "%s: null weight", who);
-        p.w[l] = w[l]; p.b[l] = b[l];
-    }
+    const int rc = mlp2d_check_net(who, w, b, nlayers, nh, min_nh, max_nh);
+    if (rc) return rc;
+    for (int l = 0; l < nlayers; ++l) { p.w[l] = w[l]; p.b[l] = b[l]; }
     p.nlayers = nlayers; p.nh = nh;
     return CGS_OK;
 }
@@ -690,16 +689,6 @@ static size_t gen_ws_floats(int B, int nlayers, int with_backward) {
     return H * (size_t)B * 64 * (with_backward ? 2 : 1) + H * GEN_WMAX * 128 + H * 128;
 }
 
-static int gen_check(const char* who, const float* const* gamma, const float* const* beta, float* const* mm, float* const* mv, int nlayers,
-                     const float* z, int B, int train, float eps, size_t need, void* ws, size_t ws_bytes) {
-    if (!gamma || !beta || !mm || !mv) return cgs_set_error(CGS_EINVAL, "%s: null batch-norm array", who);
-    for (int l = 0; l < nlayers - 1; ++l)
-        if (!gamma[l] || !beta[l] || !mm[l] || !mv[l]) return cgs_set_error(CGS_EINVAL, "%s: null batch-norm variable", who);
-    if (!z || B < (train ? 2 : 1) || !(eps > 0.f)) return cgs_set_error(CGS_EINVAL, "%s: bad argument (B=%d, training=%d)", who, B, train);
-    if (!ws || ws_bytes < need) return cgs_set_error(CGS_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
-    return CGS_OK;
-}
-
 static int gen_forward(const MlpParams& p, const float* const* gamma, const float* const* beta, float* const* mm, float* const* mv,
                        const float* z, float* x, int B, int train, float eps, float* bstat, float* ws, hipStream_t st) {
     const int nl = p.nlayers, H = nl - 1;
@@ -742,8 +731,8 @@ int cgs_mlp2d_gen_fwd(const float* const* w, const float* const* b, const float*
     int rc = mlp_fill(p, w, b, nlayers, nhidden, 64, "mlp2d_gen_fwd");
     if (rc) return rc;
     if (!x) return cgs_set_error(CGS_EINVAL, "mlp2d_gen_fwd: null output");
-    rc = gen_check("mlp2d_gen_fwd", gamma, beta, moving_mean, moving_variance, nlayers, z, B, is_training != 0, eps,
-                   gen_ws_floats(B, nlayers, 0) * sizeof(float), ws, ws_bytes);
+    rc = mlp2d_check_gen("mlp2d_gen_fwd", gamma, beta, moving_mean, moving_variance, nlayers, z, B, INT_MAX, is_training != 0, eps,
+                         gen_ws_floats(B, nlayers, 0) * sizeof(float), ws, ws_bytes);
     if (rc) return rc;
     return gen_forward(p, gamma, beta, moving_mean, moving_variance, z, x, B, is_training != 0, eps, is_training ? batch_stats : nullptr,
                        (float*)ws, (hipStream_t)stream);
@@ -756,8 +745,8 @@ int cgs_mlp2d_g_step(float* const* w, float* const* b, const float* const* gamma
     int rc = mlp_fill(p, (const float* const*)w, (const float* const*)b, nlayers, nhidden, 64, "mlp2d_g_step");
     if (rc) return rc;
     if (!grad_plugin) return cgs_set_error(CGS_EINVAL, "mlp2d_g_step: null grad_plugin");
-    rc = gen_check("mlp2d_g_step", gamma, beta, moving_mean, moving_variance, nlayers, z, B, 1, eps,
-                   gen_ws_floats(B, nlayers, 1) * sizeof(float), ws, ws_bytes);
+    rc = mlp2d_check_gen("mlp2d_g_step", gamma, beta, moving_mean, moving_variance, nlayers, z, B, INT_MAX, 1, eps,
+                         gen_ws_floats(B, nlayers, 1) * sizeof(float), ws, ws_bytes);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     rc = gen_forward(p, gamma, beta, moving_mean, moving_variance, z, x, B, 1, eps, nullptr, (float*)ws, st);

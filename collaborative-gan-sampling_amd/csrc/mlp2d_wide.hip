@@ -97,33 +97,14 @@ __global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void refine2d_wide_k
     if (lead) { best_x[2 * s] = bx0; best_x[2 * s + 1] = bx1; best_step[s] = bs; }
 }
 
-template <int T>
-static int mlpw_saliency_launch(const MlpWParams& p, const float* x, float* sig, float* sal, int B, float inv_batch, hipStream_t st) {
-    const size_t smem = mlpw_smem(T, p.nlayers, p.nhp);
-    CGS_SMEM_ATTR(160 * 1024, "mlp2d_sigmoid_saliency", mlp_saliency_wide_kernel<T>);
-    hipLaunchKernelGGL(mlp_saliency_wide_kernel<T>, dim3(cgs_ceil_div(B, T)), dim3(MLPW_THREADS), smem, st, p, x, sig, sal, B, inv_batch);
-    CGS_CHECK_LAUNCH("mlp2d_sigmoid_saliency");
-    return CGS_OK;
-}
-
-template <int T>
-static int mlpw_refine_launch(const MlpWParams& p, const float* x, float mean_host, const float* mean_dev, float inv_batch, int steps,
-                              float rate, int method, float* best_x, float* best_step, float* traj, int B, hipStream_t st) {
-    const size_t smem = mlpw_smem(T, p.nlayers, p.nhp);
-    CGS_SMEM_ATTR(160 * 1024, "refine2d", refine2d_wide_kernel<T>);
-    hipLaunchKernelGGL(refine2d_wide_kernel<T>, dim3(cgs_ceil_div(B, T)), dim3(MLPW_THREADS), smem, st, p, x, mean_host, mean_dev, inv_batch,
-                       steps, rate, method, best_x, best_step, traj, B);
-    CGS_CHECK_LAUNCH("refine2d");
-    return CGS_OK;
-}
-
 // the callers (mlp2d.hip) have checked every argument; 64 < nh <= 256
 int cgs_mlp2d_wide_saliency(const float* const* w, const float* const* b, int nlayers, int nh, const float* x, float* sig, float* sal, int B,
                             float inv_batch, hipStream_t st) {
     MlpWParams p;
     mlpw_fill(p, w, b, nlayers, nh);
-    return mlpw_tile(B) == 32 ? mlpw_saliency_launch<32>(p, x, sig, sal, B, inv_batch, st)
-                              : mlpw_saliency_launch<64>(p, x, sig, sal, B, inv_batch, st);
+    const int T = mlpw_tile(B);
+    return mlpw_launch_tile<mlp_saliency_wide_kernel<32>, mlp_saliency_wide_kernel<64>>(
+        T, B, mlpw_smem(T, nlayers, p.nhp), "mlp2d_sigmoid_saliency", "mlp2d_sigmoid_saliency", st, p, x, sig, sal, B, inv_batch);
 }
 
 int cgs_refine2d_wide(const float* const* w, const float* const* b, int nlayers, int nh, const float* x, float mean_host,
@@ -131,7 +112,8 @@ int cgs_refine2d_wide(const float* const* w, const float* const* b, int nlayers,
                       float* traj, int B, hipStream_t st) {
     MlpWParams p;
     mlpw_fill(p, w, b, nlayers, nh);
-    return mlpw_tile(B) == 32
-               ? mlpw_refine_launch<32>(p, x, mean_host, mean_dev, inv_batch, steps, rate, method, best_x, best_step, traj, B, st)
-               : mlpw_refine_launch<64>(p, x, mean_host, mean_dev, inv_batch, steps, rate, method, best_x, best_step, traj, B, st);
+    const int T = mlpw_tile(B);
+    return mlpw_launch_tile<refine2d_wide_kernel<32>, refine2d_wide_kernel<64>>(T, B, mlpw_smem(T, nlayers, p.nhp), "refine2d", "refine2d", st, p, x,
+                                                                                mean_host, mean_dev, inv_batch, steps, rate, method, best_x,
+                                                                                best_step, traj, B);
 }

@@ -5,14 +5,14 @@
 // Training mode.  The batch couples every sample at every BN layer, so a launch per dense layer is the grid-wide barrier (as in mlp2d.hip):
 //   launch 0            a_0 = z W_0 + b_0                                              VALU
 //   launch l = 1..nl-2  a_l = relu(BN_{l-1}(a_{l-1})) W_l + b_l                        mlpw_pass<T, false, true>: v_mfma_f32_32x32x2_f32, W_l streamed from L2
-//   launch nl-1         x   = relu(BN_{nl-2}(a_{nl-2})) W_last + b_last                VALU, 4 lanes per row (as mlpw_eval's logit)
+//   launch nl-1         x   = relu(BN_{nl-2}(a_{nl-2})) W_last + b_last                VALU, 4 lanes per row (mlpw_rowdot)
 // One workgroup of 4 waves per tile of T = mlpw_tile(B) samples.  Launch l >= 1 first turns the partial statistics of a_{l-1} into (mean,
 // rstd), fills H [T][nhp + 4] in LDS from the stored a_{l-1} through relu(gamma (a - mean) rstd + beta) -- padded units nh <= j < nhp and
 // rows past B enter as 0 -- and contracts.  The accumulators start at the bias and go to H as they are: no ReLU, no mask.  From H the rows
 // below B go to the workspace, and every group of 32 consecutive rows leaves (mean, M2) per unit, summed over its rows in ascending order.
 //
 // Determinism: a partial belongs to rows [32 g, min(B, 32 g + 32)), whatever T is (a T = 64 tile writes two); the consumer combines the
-// ceil(B / 32) partials in ascending g with Chan's update (gen_combine's statements).  A row's pre-activation is a k-ascending fmaf chain
+// ceil(B / 32) partials in ascending g (mlpw_walk_partials) with Chan's update (gen_combine's statements).  A row's pre-activation is a k-ascending fmaf chain
 // from the bias.  So every output is a function of the inputs and B alone, not of T or of the CU count.  No atomics.
 // Every workgroup of launch l repeats the combine (one unit per thread, ceil(B / 32) steps); workgroup 0 also writes what a call writes
 // once: the layer's (mean, rstd) row, batch_stats, and the moving averages v -= (v - value) * 0.1f (two roundings), value = the batch mean /
@@ -28,8 +28,6 @@
 //   stats [H][2][nhp]     (mean, rstd) of the batch, padded units 0
 //   bytes = 4 H nhp (B + 2 G + 2)
 #include "mlp2d_wide.h"
-
-#define GENW_PBATCH 16          // partials fetched per round trip: the combine is a serial chain, its loads need not be
 
 struct GenWLayer {
     const float* w; const float* b;                    // the dense layer of this launch: [din][dout], [dout]
@@ -54,10 +52,8 @@ struct GenWNet {                                       // inference mode: the wh
     float eps;
 };
 
-struct GenWLds {
-    float* H;          // [T][nhp + 4], unit j at position hpos(j)
-    float* slab;       // [2][nhp][T/2], mlpw_pass's
-    float* bn;         // [4][nhp]: mean, rstd, gamma, beta of the BN layer being applied, unit j at index j
+struct GenWLds : MlpWTileLds {       // slab: mlpw_pass's
+    float* bn;         // [4][nhp]: mean, rstd, gamma, beta of the BN layer being applied (mlpw_bn_row)
     float* wl;         // [2][nhp]: the two columns of the last layer in position order
     float* zs;         // [T][2]: the tile's z
 };
@@ -65,52 +61,33 @@ struct GenWLds {
 template <int T>
 __device__ __forceinline__ GenWLds genw_lds(float* smem, int nhp) {
     GenWLds L;
-    L.H = smem;
-    L.slab = L.H + T * (nhp + 4);
-    L.bn = L.slab + 2 * nhp * (T / 2);
+    L.bn = mlpw_tile_lds<T>(L, smem, nhp);
     L.wl = L.bn + 4 * nhp;
     L.zs = L.wl + 2 * nhp;
     return L;
 }
 
 // nh = 256: T = 64: 135.5 KiB (one block per CU); T = 32: 70.8 KiB (two)
-static size_t genw_smem(int T, int nhp) { return (size_t)(T * (nhp + 4) + 2 * nhp * (T / 2) + 6 * nhp + 2 * T) * sizeof(float); }
-
-__device__ __forceinline__ float genw_bn_relu(float a, const float* bn, int nhp, int j) {
-    return fmaxf(fmaf((a - bn[j]) * bn[nhp + j], bn[2 * nhp + j], bn[3 * nhp + j]), 0.f);
-}
+static size_t genw_smem(int T, int nhp) { return (mlpw_tile_floats(T, nhp) + 6 * nhp + 2 * T) * sizeof(float); }
 
 // Thread j < nhp: (mean, rstd, gamma, beta) of unit j of the BN layer below into L.bn, from the partials of its row groups in ascending
 // order.  Workgroup 0 writes the layer's statistics row, batch_stats and the moving averages.
 __device__ __forceinline__ void genw_bn_train(const GenWLayer& a, float* bn) {
     const int j = threadIdx.x, nh = a.nh, nhp = a.nhp;
     if (j >= nhp) return;
-    float mean = 0.f, rstd = 0.f, gam = 0.f, bet = 0.f;
+    float mean = 0.f, rstd = 0.f;
     if (j < nh) {
-        const int G = (a.B + 31) >> 5;
         float n = 0.f, m = 0.f, M2 = 0.f;
-        for (int p0 = 0; p0 < G; p0 += GENW_PBATCH) {
-            float pm[GENW_PBATCH], pM[GENW_PBATCH];
-#pragma unroll
-            for (int q = 0; q < GENW_PBATCH; ++q) {
-                const bool in = p0 + q < G;
-                pm[q] = in ? a.part_in[(size_t)(p0 + q) * 2 * nhp + j] : 0.f;
-                pM[q] = in ? a.part_in[(size_t)(p0 + q) * 2 * nhp + nhp + j] : 0.f;
-            }
-#pragma unroll
-            for (int q = 0; q < GENW_PBATCH; ++q) {
-                if (p0 + q >= G) break;
-                const float nb = (float)min(32, a.B - (p0 + q) * 32);
-                const float nab = n + nb, d = pm[q] - m;
-                m = m + d * (nb / nab);
-                M2 = M2 + pM[q] + d * d * (n * nb / nab);
-                n = nab;
-            }
-        }
+        mlpw_walk_partials<2>(a.part_in, (a.B + 31) >> 5, nhp, j, [&](int g, const float (&p)[2]) {       // Chan's update, p = (mean, M2) of group g
+            const float nb = (float)min(32, a.B - g * 32);
+            const float nab = n + nb, d = p[0] - m;
+            m = m + d * (nb / nab);
+            M2 = M2 + p[1] + d * d * (n * nb / nab);
+            n = nab;
+        });
         mean = m;
         const float var = M2 / (float)a.B;
         rstd = 1.f / sqrtf(var + a.eps);
-        gam = a.gamma[j]; bet = a.beta[j];
         if (blockIdx.x == 0) {
 #pragma clang fp contract(off)      // assign_moving_average: v -= (v - value) * (1 - decay), decay 0.9 -> 0.1f; moving_variance takes the
                                     // Bessel-corrected batch variance of the fused kernel
@@ -121,7 +98,7 @@ __device__ __forceinline__ void genw_bn_train(const GenWLayer& a, float* bn) {
         }
     }
     if (blockIdx.x == 0) { a.stats_in[j] = mean; a.stats_in[nhp + j] = rstd; }
-    bn[j] = mean; bn[nhp + j] = rstd; bn[2 * nhp + j] = gam; bn[3 * nhp + j] = bet;
+    mlpw_bn_row(bn, nh, nhp, j, mean, rstd, a.gamma, a.beta);
 }
 
 // H <- relu(BN(a_{l-1})) of the tile's rows; rows past B and padded units (variance 0, no gamma / beta) enter as 0
@@ -131,7 +108,7 @@ __device__ __forceinline__ void genw_fill(const GenWLayer& a, const GenWLds& L, 
     for (int e = threadIdx.x; e < T * nhp; e += MLPW_THREADS) {
         const int row = e / nhp, j = e - row * nhp;
         float h = 0.f;
-        if (row < rows && j < nh) h = genw_bn_relu(a.pre_in[(size_t)(row0 + row) * nhp + j], L.bn, nhp, j);
+        if (row < rows && j < nh) h = mlpw_bn_apply(a.pre_in[(size_t)(row0 + row) * nhp + j], L.bn, nhp, j);
         L.H[row * HS + hpos(j)] = h;
     }
 }
@@ -140,10 +117,7 @@ __device__ __forceinline__ void genw_fill(const GenWLayer& a, const GenWLds& L, 
 template <int T>
 __device__ __forceinline__ void genw_emit(const GenWLayer& a, const GenWLds& L, int row0, int rows) {
     const int nhp = a.nhp, HS = nhp + 4;
-    for (int e = threadIdx.x; e < T * nhp; e += MLPW_THREADS) {
-        const int row = e / nhp, j = e - row * nhp;
-        if (row < rows) a.pre_out[(size_t)(row0 + row) * nhp + j] = L.H[row * HS + hpos(j)];
-    }
+    mlpw_store_h<T>(L, nhp, a.pre_out + (size_t)row0 * nhp, rows);
     for (int t = threadIdx.x; t < (T / 32) * nhp; t += MLPW_THREADS) {
         const int g = t / nhp, j = t - g * nhp, n = min(32, rows - 32 * g);
         if (n <= 0) continue;
@@ -158,18 +132,6 @@ __device__ __forceinline__ void genw_emit(const GenWLayer& a, const GenWLds& L, 
     }
 }
 
-// H <- a_0 = z W_0 + b_0 for the tile's z in L.zs (padded units 0)
-template <int T>
-__device__ __forceinline__ void genw_first(const float* __restrict__ w, const float* __restrict__ b, const GenWLds& L, int nh, int nhp) {
-    const int HS = nhp + 4;
-    for (int e = threadIdx.x; e < T * nhp; e += MLPW_THREADS) {
-        const int row = e / nhp, j = e - row * nhp;
-        float v = 0.f;
-        if (j < nh) v = fmaf(L.zs[2 * row + 1], w[nh + j], fmaf(L.zs[2 * row], w[j], b[j]));
-        L.H[row * HS + hpos(j)] = v;
-    }
-}
-
 __device__ __forceinline__ void genw_load_last(const float* __restrict__ w, float* wl, int nh, int nhp) {
     for (int j = threadIdx.x; j < nhp; j += MLPW_THREADS) {
         const int q = hpos(j);
@@ -178,20 +140,14 @@ __device__ __forceinline__ void genw_load_last(const float* __restrict__ w, floa
     }
 }
 
-// x = H W_last + b_last: 4 lanes per row walk the positions in the same order for every T
+// x = H W_last + b_last by mlpw_rowdot
 template <int T>
 __device__ __forceinline__ void genw_out(const GenWLds& L, const float* __restrict__ b, float* __restrict__ x, int nhp, int row0, int rows) {
-    const int tid = threadIdx.x, row = tid >> 2, q4 = tid & 3, HS = nhp + 4;
+    const int tid = threadIdx.x, row = tid >> 2;
     if (tid >= 4 * T) return;                          // whole waves
-    float p0 = 0.f, p1 = 0.f;
-    for (int q = q4; q < nhp; q += 4) {
-        const float h = L.H[row * HS + q];
-        p0 = fmaf(h, L.wl[q], p0);
-        p1 = fmaf(h, L.wl[nhp + q], p1);
-    }
-    p0 += __shfl_xor(p0, 1, 64); p1 += __shfl_xor(p1, 1, 64);
-    p0 += __shfl_xor(p0, 2, 64); p1 += __shfl_xor(p1, 2, 64);
-    if (q4 == 0 && row < rows) { x[2 * (size_t)(row0 + row)] = p0 + b[0]; x[2 * (size_t)(row0 + row) + 1] = p1 + b[1]; }
+    float p[2];
+    mlpw_rowdot<2>(L, L.wl, nhp, p);
+    if ((tid & 3) == 0 && row < rows) { x[2 * (size_t)(row0 + row)] = p[0] + b[0]; x[2 * (size_t)(row0 + row) + 1] = p[1] + b[1]; }
 }
 
 template <int T>
@@ -207,7 +163,7 @@ __global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void genw_first_kern
     const int row0 = blockIdx.x * T, rows = min(T, a.B - row0);
     genw_load_z<T>(a.z, L.zs, row0, rows);
     __syncthreads();
-    genw_first<T>(a.w, a.b, L, a.nh, a.nhp);
+    mlpw_first<T, false>(L, L.zs, a.w, a.b, a.nh, a.nhp);
     __syncthreads();
     genw_emit<T>(a, L, row0, rows);
 }
@@ -221,11 +177,7 @@ __global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void genw_hidden_ker
     __syncthreads();
     genw_fill<T>(a, L, row0, rows);
     __syncthreads();
-    MlpWParams p = {};
-    p.nh = a.nh; p.nhp = a.nhp;
-    MlpWLds M = {};
-    M.H = L.H; M.slab = L.slab;
-    mlpw_pass<T, false, true>(p, M, a.w, a.b, 0);
+    mlpw_pass<T, false, true>(L, a.nh, a.nhp, a.w, a.b);
     genw_emit<T>(a, L, row0, rows);
 }
 
@@ -250,71 +202,41 @@ __global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void genw_infer_kern
     const int row0 = blockIdx.x * T, rows = min(T, a.B - row0);
     genw_load_z<T>(a.z, L.zs, row0, rows);
     genw_load_last(a.w[nl - 1], L.wl, nh, nhp);
-    MlpWParams p = {};
-    p.nh = nh; p.nhp = nhp;
-    MlpWLds M = {};
-    M.H = L.H; M.slab = L.slab;
     __syncthreads();
     for (int l = 0; l < nl - 1; ++l) {
         if (l == 0) {
-            genw_first<T>(a.w[0], a.b[0], L, nh, nhp);
+            mlpw_first<T, false>(L, L.zs, a.w[0], a.b[0], nh, nhp);
         } else {
-            mlpw_pass<T, false, true>(p, M, a.w[l], a.b[l], 0);
+            mlpw_pass<T, false, true>(L, nh, nhp, a.w[l], a.b[l]);
         }
         if (tid < nhp) {
             const bool in = tid < nh;
-            L.bn[tid] = in ? a.mmean[l][tid] : 0.f;
-            L.bn[nhp + tid] = in ? 1.f / sqrtf(a.mvar[l][tid] + a.eps) : 0.f;
-            L.bn[2 * nhp + tid] = in ? a.gamma[l][tid] : 0.f;
-            L.bn[3 * nhp + tid] = in ? a.beta[l][tid] : 0.f;
+            mlpw_bn_row(L.bn, nh, nhp, tid, in ? a.mmean[l][tid] : 0.f, in ? 1.f / sqrtf(a.mvar[l][tid] + a.eps) : 0.f, a.gamma[l], a.beta[l]);
         }
         __syncthreads();
         for (int e = tid; e < T * nhp; e += MLPW_THREADS) {
             const int row = e / nhp, j = e - row * nhp;
             float* hp = &L.H[row * HS + hpos(j)];
-            *hp = j < nh ? genw_bn_relu(*hp, L.bn, nhp, j) : 0.f;
+            *hp = j < nh ? mlpw_bn_apply(*hp, L.bn, nhp, j) : 0.f;
         }
         __syncthreads();
     }
     genw_out<T>(L, a.b[nl - 1], a.x, nhp, row0, rows);
 }
 
-static size_t genw_ws_floats(int B, int nlayers, int nhp) {
-    return (size_t)(nlayers - 1) * nhp * ((size_t)B + 2 * (size_t)cgs_ceil_div(B, 32) + 2);
-}
-
-template <int T>
-static int genw_train_launch(GenWLayer a, int l, int nlayers, hipStream_t st) {
+// launch l of the training forward
+static int genw_train_launch(int T, const GenWLayer& a, int l, int nlayers, hipStream_t st) {
+    const char* who = "mlp2d_wide_gen_fwd";
     const size_t smem = genw_smem(T, a.nhp);
-    const dim3 grid(cgs_ceil_div(a.B, T)), block(MLPW_THREADS);
-    if (l == 0) {
-        CGS_SMEM_ATTR(160 * 1024, "mlp2d_wide_gen_fwd", genw_first_kernel<T>);
-        hipLaunchKernelGGL(genw_first_kernel<T>, grid, block, smem, st, a);
-    } else if (l < nlayers - 1) {
-        CGS_SMEM_ATTR(160 * 1024, "mlp2d_wide_gen_fwd", genw_hidden_kernel<T>);
-        hipLaunchKernelGGL(genw_hidden_kernel<T>, grid, block, smem, st, a);
-    } else {
-        CGS_SMEM_ATTR(160 * 1024, "mlp2d_wide_gen_fwd", genw_last_kernel<T>);
-        hipLaunchKernelGGL(genw_last_kernel<T>, grid, block, smem, st, a);
-    }
-    CGS_CHECK_LAUNCH("mlp2d_wide_gen_fwd");
-    return CGS_OK;
+    if (l == 0) return mlpw_launch_tile<genw_first_kernel<32>, genw_first_kernel<64>>(T, a.B, smem, who, who, st, a);
+    if (l < nlayers - 1) return mlpw_launch_tile<genw_hidden_kernel<32>, genw_hidden_kernel<64>>(T, a.B, smem, who, who, st, a);
+    return mlpw_launch_tile<genw_last_kernel<32>, genw_last_kernel<64>>(T, a.B, smem, who, who, st, a);
 }
-
-template <int T>
-static int genw_infer_launch(const GenWNet& a, hipStream_t st) {
-    CGS_SMEM_ATTR(160 * 1024, "mlp2d_wide_gen_fwd", genw_infer_kernel<T>);
-    hipLaunchKernelGGL(genw_infer_kernel<T>, dim3(cgs_ceil_div(a.B, T)), dim3(MLPW_THREADS), genw_smem(T, a.nhp), st, a);
-    CGS_CHECK_LAUNCH("mlp2d_wide_gen_fwd");
-    return CGS_OK;
-}
-
-static bool genw_shape_ok(int nlayers, int nhidden) { return nlayers >= 2 && nlayers <= MLPW_MAX_LAYERS && nhidden >= 65 && nhidden <= 256; }
 
 extern "C" {
 
 size_t cgs_mlp2d_wide_gen_ws_bytes(int B, int nlayers, int nhidden) {
-    if (B <= 0 || B > (1 << 24) || !genw_shape_ok(nlayers, nhidden)) return 0;
+    if (B <= 0 || B > (1 << 24) || !mlpw_gen_shape_ok(nlayers, nhidden)) return 0;
     return genw_ws_floats(B, nlayers, cgs_round_up(nhidden, 32)) * sizeof(float);
 }
 
@@ -322,21 +244,14 @@ int cgs_mlp2d_wide_gen_fwd(const float* const* w, const float* const* b, const f
                            float* const* moving_mean, float* const* moving_variance, int nlayers, int nhidden, const float* z, float* x,
                            int B, int is_training, float eps, float* batch_stats, void* ws, size_t ws_bytes, void* stream) {
     const char* who = "mlp2d_wide_gen_fwd";
-    // the checks of cgs_mlp2d_gen_fwd, in its order: shape, weights, output, batch-norm variables, batch, workspace
-    if (!genw_shape_ok(nlayers, nhidden)) return cgs_set_error(CGS_EINVAL, "%s: nlayers=%d nhidden=%d (need 2..6, 65..256)", who, nlayers, nhidden);
-    if (!w || !b) return cgs_set_error(CGS_EINVAL, "%s: null weight array", who);
-    for (int l = 0; l < nlayers; ++l)
-        if (!w[l] || !b[l]) return cgs_set_error(CGS_EINVAL, "%s: null weight", who);
+    int rc = mlp2d_check_net(who, w, b, nlayers, nhidden, MLPW_MIN_NH, MLPW_MAX_NH);
+    if (rc) return rc;
     if (!x) return cgs_set_error(CGS_EINVAL, "%s: null output", who);
-    if (!gamma || !beta || !moving_mean || !moving_variance) return cgs_set_error(CGS_EINVAL, "%s: null batch-norm array", who);
-    for (int l = 0; l < nlayers - 1; ++l)
-        if (!gamma[l] || !beta[l] || !moving_mean[l] || !moving_variance[l]) return cgs_set_error(CGS_EINVAL, "%s: null batch-norm variable", who);
-    const int train = is_training != 0;
+    const int train = is_training != 0, nhp = cgs_round_up(nhidden, 32), H = nlayers - 1, G = cgs_ceil_div(B, 32);
     // B <= 2^24: the row counts of the combine are floats
-    if (!z || B < (train ? 2 : 1) || B > (1 << 24) || !(eps > 0.f)) return cgs_set_error(CGS_EINVAL, "%s: bad argument (B=%d, training=%d)", who, B, train);
-    const int nhp = cgs_round_up(nhidden, 32), H = nlayers - 1, G = cgs_ceil_div(B, 32);
-    const size_t need = genw_ws_floats(B, nlayers, nhp) * sizeof(float);
-    if (!ws || ws_bytes < need) return cgs_set_error(CGS_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    rc = mlp2d_check_gen(who, gamma, beta, moving_mean, moving_variance, nlayers, z, B, 1 << 24, train, eps,
+                         genw_ws_floats(B, nlayers, nhp) * sizeof(float), ws, ws_bytes);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int T = mlpw_tile(B);
     if (!train) {
@@ -344,7 +259,7 @@ int cgs_mlp2d_wide_gen_fwd(const float* const* w, const float* const* b, const f
         for (int l = 0; l < nlayers; ++l) { a.w[l] = w[l]; a.b[l] = b[l]; }
         for (int l = 0; l < H; ++l) { a.gamma[l] = gamma[l]; a.beta[l] = beta[l]; a.mmean[l] = moving_mean[l]; a.mvar[l] = moving_variance[l]; }
         a.z = z; a.x = x; a.nlayers = nlayers; a.nh = nhidden; a.nhp = nhp; a.B = B; a.eps = eps;
-        return T == 32 ? genw_infer_launch<32>(a, st) : genw_infer_launch<64>(a, st);
+        return mlpw_launch_tile<genw_infer_kernel<32>, genw_infer_kernel<64>>(T, B, genw_smem(T, nhp), who, who, st, a);
     }
     float* pre = (float*)ws;
     float* part = pre + (size_t)H * B * nhp;
@@ -363,7 +278,7 @@ int cgs_mlp2d_wide_gen_fwd(const float* const* w, const float* const* b, const f
         if (l < nlayers - 1) { a.pre_out = pre + (size_t)l * B * nhp; a.part_out = part + (size_t)l * G * 2 * nhp; }
         else a.x = x;
         a.nh = nhidden; a.nhp = nhp; a.B = B; a.eps = eps;
-        const int rc = T == 32 ? genw_train_launch<32>(a, l, nlayers, st) : genw_train_launch<64>(a, l, nlayers, st);
+        rc = genw_train_launch(T, a, l, nlayers, st);
         if (rc) return rc;
     }
     return CGS_OK;

@@ -15,7 +15,7 @@
 // One workgroup of 4 waves per tile of T = mlpw_tile(B) samples in the first three kinds of launch.
 //
 // Epilogue for layer l (H holds dh_l): xhat = (a - mean) rstd and the ReLU decision gamma xhat + beta > 0 are recomputed from pre and stats
-// with genw_bn_relu's own statements, so a mask never disagrees with the forward's; dxhat = decision ? dh gamma : 0 goes to dbuf
+// by mlpw_xhat and mlpw_bn_relu, the forward's own functions, so a mask never disagrees with the forward's; dxhat = decision ? dh gamma : 0 goes to dbuf
 // [nl-1][B][nhp] in natural unit order (padded units: exact zeros; rows past B: not stored), and every group of 32 consecutive rows leaves
 // (sum dxhat, sum dxhat xhat) per unit, one thread per (group, unit) walking the rows in ascending order: the forward's groups.
 // Launch u adds the ceil(B / 32) partials of layer u in ascending group order, one unit per thread, and overwrites dxhat_u with da_u in place.
@@ -27,7 +27,7 @@
 // forward's xhat.
 //
 // h_{l-1} = relu(BN(a_{l-1})) is NOT stored: the weight-gradient launch recomputes it on load from pre and stats (a lane's column is fixed,
-// so mean, rstd, gamma, beta are four registers per column), again with genw_bn_relu's statements.
+// so mean, rstd, gamma, beta are four registers per column: GswBnCol), again by mlpw_xhat and mlpw_bn_relu.
 //
 // Determinism: groups of 32 rows and chunks of mlpw_chunk(B) samples are functions of B alone; every sum walks its terms in ascending
 // order; the MFMA chains are k-ordered.  So every output is a function of the inputs and B alone, not of T or of the CU count.  No atomics.
@@ -38,10 +38,8 @@
 //   bpart [H][G][3][nhp]   (sum dxhat, sum dxhat xhat, sum xhat) of the row groups
 //   xs    [B][2]           G(z) when the caller passes no x
 //   pw    [nl-2][16][nhp][nhp]   partial dW of the hidden -> hidden layers, [layer][chunk]
-//   ps    [16][H nhp (db_l) + 2 nhp (dW_0) + 2 nhp (dW_last, by column) + 4 (db_last, 0, 0)]
+//   ps    [16][mlpw_small_stride at two outputs: H nhp (db_l) + 2 nhp (dW_0) + 2 nhp (dW_last, by column) + 4 (db_last, 0, 0)]
 #include "mlp2d_wide.h"
-
-#define GSW_PBATCH 16           // partials fetched per round trip, as GENW_PBATCH
 
 // Compensated (Kahan) running sum, terms taken in the order given: the order stays ascending, so the result is still a function of the
 // inputs alone, and its rounding error no longer grows with the number of terms.  The sums it is used for cancel in exact arithmetic
@@ -65,10 +63,8 @@ struct GswLayer {
     int nh, nhp, B;
 };
 
-struct GswLds {
-    float* H;          // [T][nhp + 4], unit j at position hpos(j)
-    float* slab;       // [2][nhp][T/2], mlpw_pass's; the epilogue keeps xhat [T][nhp] (natural order) there
-    float* bn;         // [4][nhp]: mean, rstd, gamma, beta of layer l, unit j at index j
+struct GswLds : MlpWTileLds {        // slab: mlpw_pass's; the epilogue keeps xhat [T][nhp] (natural order) there
+    float* bn;         // [4][nhp]: mean, rstd, gamma, beta of layer l (mlpw_bn_row)
     float* up;         // [5][nhp]: mean, rstd, mean(dxhat), mean(dxhat (xhat - e)), e = mean(xhat) of layer u; the top launch: the two
                        // columns of W_last
     float* gp;         // [T][2]: the tile's grad_plugin
@@ -77,26 +73,19 @@ struct GswLds {
 template <int T>
 __device__ __forceinline__ GswLds gsw_lds(float* smem, int nhp) {
     GswLds L;
-    L.H = smem;
-    L.slab = L.H + T * (nhp + 4);
-    L.bn = L.slab + 2 * nhp * (T / 2);
+    L.bn = mlpw_tile_lds<T>(L, smem, nhp);
     L.up = L.bn + 4 * nhp;
     L.gp = L.up + 5 * nhp;
     return L;
 }
 
 // nh = 256: T = 64: 138.5 KiB (one block per CU); T = 32: 73.8 KiB (two)
-static size_t gsw_smem(int T, int nhp) { return (size_t)(T * (nhp + 4) + 2 * nhp * (T / 2) + 9 * nhp + 2 * T) * sizeof(float); }
+static size_t gsw_smem(int T, int nhp) { return (mlpw_tile_floats(T, nhp) + 9 * nhp + 2 * T) * sizeof(float); }
 
-// thread j < nhp: (mean, rstd, gamma, beta) of unit j of layer l; padded units: zeros (there is no gamma or beta to read there)
+// thread j < nhp: (mean, rstd, gamma, beta) of unit j of layer l
 __device__ __forceinline__ void gsw_load_bn(const GswLayer& a, float* bn) {
     const int j = threadIdx.x, nh = a.nh, nhp = a.nhp;
-    if (j >= nhp) return;
-    const bool in = j < nh;
-    bn[j] = in ? a.stats_l[j] : 0.f;
-    bn[nhp + j] = in ? a.stats_l[nhp + j] : 0.f;
-    bn[2 * nhp + j] = in ? a.gamma_l[j] : 0.f;
-    bn[3 * nhp + j] = in ? a.beta_l[j] : 0.f;
+    if (j < nhp) mlpw_bn_row(bn, nh, nhp, j, j < nh ? a.stats_l[j] : 0.f, j < nh ? a.stats_l[nhp + j] : 0.f, a.gamma_l, a.beta_l);
 }
 
 // thread j < nhp: (mean, rstd, mean(dxhat), mean(dxhat (xhat - e)), e) of unit j of layer u, the three batch means from the partials of its
@@ -106,21 +95,8 @@ __device__ __forceinline__ void gsw_load_up(const GswLayer& a, float* up) {
     if (j >= nhp) return;
     float mean = 0.f, rstd = 0.f, c1 = 0.f, c2 = 0.f, ex = 0.f;
     if (j < nh) {
-        const int G = (a.B + 31) >> 5;
         GswSum s1, s2, s3;
-        for (int p0 = 0; p0 < G; p0 += GSW_PBATCH) {
-            float p1[GSW_PBATCH], p2[GSW_PBATCH], p3[GSW_PBATCH];
-#pragma unroll
-            for (int q = 0; q < GSW_PBATCH; ++q) {
-                const bool in = p0 + q < G;
-                p1[q] = in ? a.bpart_u[(size_t)(p0 + q) * 3 * nhp + j] : 0.f;
-                p2[q] = in ? a.bpart_u[(size_t)(p0 + q) * 3 * nhp + nhp + j] : 0.f;
-                p3[q] = in ? a.bpart_u[(size_t)(p0 + q) * 3 * nhp + 2 * nhp + j] : 0.f;
-            }
-#pragma unroll
-            for (int q = 0; q < GSW_PBATCH; ++q)
-                if (p0 + q < G) { s1.add(p1[q]); s2.add(p2[q]); s3.add(p3[q]); }
-        }
+        mlpw_walk_partials<3>(a.bpart_u, (a.B + 31) >> 5, nhp, j, [&](int, const float (&p)[3]) { s1.add(p[0]); s2.add(p[1]); s3.add(p[2]); });
         c1 = s1.s / (float)a.B; ex = s3.s / (float)a.B; c2 = s2.s / (float)a.B - ex * c1;
         mean = a.stats_u[j]; rstd = a.stats_u[nhp + j];
     }
@@ -129,7 +105,7 @@ __device__ __forceinline__ void gsw_load_up(const GswLayer& a, float* up) {
 
 // tf FusedBatchNormGrad, training: da = rstd (dxhat - mean(dxhat) - xhat mean(dxhat xhat)), xhat the forward's, centred (see the top)
 __device__ __forceinline__ float gsw_da(float a, float dx, const float* up, int nhp, int j) {
-    const float ru = up[nhp + j], xh = (a - up[j]) * ru;
+    const float ru = up[nhp + j], xh = mlpw_xhat(a, up[j], ru);
     return ru * (dx - up[2 * nhp + j] - (xh - up[4 * nhp + j]) * up[3 * nhp + j]);
 }
 
@@ -159,8 +135,8 @@ __device__ __forceinline__ void gsw_epilogue(const GswLayer& a, const GswLds& L,
         float* hp = &L.H[row * HS + hpos(j)];
         float dx = 0.f, xh = 0.f;
         if (row < rows && j < nh) {
-            xh = (a.pre_l[(size_t)(row0 + row) * nhp + j] - L.bn[j]) * L.bn[nhp + j];             // genw_bn_relu's statements
-            dx = fmaf(xh, L.bn[2 * nhp + j], L.bn[3 * nhp + j]) > 0.f ? *hp * L.bn[2 * nhp + j] : 0.f;
+            xh = mlpw_bn_xhat(a.pre_l[(size_t)(row0 + row) * nhp + j], L.bn, nhp, j);
+            dx = mlpw_bn_relu(xh, L.bn[2 * nhp + j], L.bn[3 * nhp + j]) > 0.f ? *hp * L.bn[2 * nhp + j] : 0.f;      // the forward's h > 0
         }
         *hp = dx; X[row * nhp + j] = xh;
         if (row < rows) a.dbuf_l[(size_t)(row0 + row) * nhp + j] = dx;
@@ -209,11 +185,7 @@ __global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void gsw_layer_kerne
     __syncthreads();
     gsw_fill_da<T>(a, L, row0, rows);
     __syncthreads();
-    MlpWParams p = {};
-    p.nh = a.nh; p.nhp = a.nhp;
-    MlpWLds M = {};
-    M.H = L.H; M.slab = L.slab;
-    mlpw_pass<T, true, true>(p, M, a.w_up, nullptr, 0);
+    mlpw_pass<T, true, true>(L, a.nh, a.nhp, a.w_up, nullptr);
     gsw_epilogue<T>(a, L, row0, rows);
 }
 
@@ -240,114 +212,55 @@ struct GswGrad {
     int nlayers, nh, nhp, B, chunk, nchunks, sstride;
 };
 
-// blocks [0, nmfma): 4 waves, wave task t = 4 block + wave -> (hidden -> hidden layer, chunk, 64 x 64 block of dW): mlpw_wgrad_kernel's
-// product with the A fragment recomputed, h = relu(BN(a)), from the pre-activations.
+// (mean, rstd, gamma, beta) of column `col` of BN layer l in registers, zeros in a padded column; h(a) = relu(BN(a)) of a pre-activation
+struct GswBnCol {
+    float m, r, g, e;
+    bool in;
+    __device__ __forceinline__ GswBnCol(const GswGrad& q, int l, int col, bool on = true) {
+        const float* S = q.stats + (size_t)l * 2 * q.nhp;
+        in = on && col < q.nh;
+        m = in ? S[col] : 0.f; r = in ? S[q.nhp + col] : 0.f; g = in ? q.gamma[l][col] : 0.f; e = in ? q.beta[l][col] : 0.f;
+    }
+    __device__ __forceinline__ float h(float a) const { return mlpw_bn_relu(mlpw_xhat(a, m, r), g, e); }
+};
+
+// blocks [0, nmfma): mlpw_wgrad_mfma, the A fragment h = relu(BN(a)) recomputed from the pre-activations on load.
 // blocks [nmfma, nmfma + nchunks (nl-1)): (chunk, BN layer l): thread j < nhp sums column j of da_l over the chunk (db_l); l = 0 adds
 // z^T da_0; l = nl-2 adds h_{nl-2}^T grad_plugin and, in threads 0 and 1, the column sums of grad_plugin (db_last).
 __global__ __launch_bounds__(MLPW_THREADS) void gsw_wgrad_kernel(GswGrad q, int nmfma) {
-    const int tid = threadIdx.x, B = q.B, nh = q.nh, nhp = q.nhp, nhid = q.nlayers - 1;
+    const int tid = threadIdx.x, B = q.B, nhp = q.nhp, nhid = q.nlayers - 1;
     const size_t lstride = (size_t)B * nhp;
     if ((int)blockIdx.x < nmfma) {
-        const int NB = nhp >> 5, NB2 = (NB + 1) >> 1, per = NB2 * NB2;
-        const int lane = tid & 63, h = lane >> 5, c31 = lane & 31;
-        const int t = blockIdx.x * 4 + (tid >> 6);
-        if (t >= (q.nlayers - 2) * q.nchunks * per) return;
-        const int lc = t / per, blk = t - lc * per, hl = lc / q.nchunks, c = lc - hl * q.nchunks;       // hl = 0: dW of layer 1
-        const int ti = 2 * (blk / NB2), tj = 2 * (blk % NB2);
-        const bool i1 = ti + 1 < NB, j1 = tj + 1 < NB;
-        const int s0 = c * q.chunk, s1 = min(B, s0 + q.chunk);
-        const int col = ti * 32 + c31;
-        const float* A = q.pre + hl * lstride + col;
-        const float* D = q.dbuf + (hl + 1) * lstride + tj * 32 + c31;
-        const float* S = q.stats + (size_t)hl * 2 * nhp;
-        const bool in0 = col < nh, in1 = i1 && col + 32 < nh;
-        const float m0 = in0 ? S[col] : 0.f, r0 = in0 ? S[nhp + col] : 0.f, g0 = in0 ? q.gamma[hl][col] : 0.f, e0 = in0 ? q.beta[hl][col] : 0.f;
-        const float m1 = in1 ? S[col + 32] : 0.f, r1 = in1 ? S[nhp + col + 32] : 0.f, g1 = in1 ? q.gamma[hl][col + 32] : 0.f,
-                    e1 = in1 ? q.beta[hl][col + 32] : 0.f;
-        mlpw_f16 acc[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-#pragma unroll 1
-        for (int s = s0; s < s1; s += 8) {                                  // 4 MFMA steps of 2 samples; the chunk size is a multiple of 8
-            float a0[4], a1[4], b0[4], b1[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {                                   // rows past the chunk's end (the last chunk's past B) enter as zero
-                const int ss = s + 2 * u + h;
-                const bool ok = ss < s1;
-                const size_t o = (size_t)ss * nhp;
-                a0[u] = (ok && in0) ? fmaxf(fmaf((A[o] - m0) * r0, g0, e0), 0.f) : 0.f;
-                a1[u] = (ok && in1) ? fmaxf(fmaf((A[o + 32] - m1) * r1, g1, e1), 0.f) : 0.f;
-                b0[u] = ok ? D[o] : 0.f; b1[u] = (ok && j1) ? D[o + 32] : 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], b0[u], acc[0][0], 0, 0, 0);
-                if (j1) acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], b1[u], acc[0][1], 0, 0, 0);
-                if (i1) acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], b0[u], acc[1][0], 0, 0, 0);
-                if (i1 && j1) acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], b1[u], acc[1][1], 0, 0, 0);
-            }
-        }
-        float* P = q.pw + (size_t)lc * nhp * nhp;                           // [layer][chunk][nhp][nhp]
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                if ((a && !i1) || (b && !j1)) continue;
-#pragma unroll
-                for (int r = 0; r < 16; ++r)     // accumulator element r of lane (h, c31): row (r & 3) + 8 (r >> 2) + 4 h, column c31
-                    P[(size_t)((ti + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * nhp + (tj + b) * 32 + c31] = acc[a][b][r];
-            }
+        mlpw_wgrad_mfma(q.nlayers, nhp, B, q.chunk, q.nchunks, q.dbuf, q.pw, [&](int hl, int col, bool i1) {
+            return [A = q.pre + hl * lstride + col, c0 = GswBnCol(q, hl, col), c1 = GswBnCol(q, hl, col + 32, i1)](size_t o, bool ok, float& a0, float& a1) {
+                a0 = (ok && c0.in) ? c0.h(A[o]) : 0.f; a1 = (ok && c1.in) ? c1.h(A[o + 32]) : 0.f;
+            };
+        });
         return;
     }
     const int sb = blockIdx.x - nmfma, c = sb / nhid, l = sb - c * nhid;
     const int s0 = c * q.chunk, s1 = min(B, s0 + q.chunk);
     float* S = q.ps + (size_t)c * q.sstride;
     if (tid < nhp) {
-        // 16 samples' loads in flight, then their terms added in ascending sample order (the chunk size is a multiple of 16; rows past the
-        // chunk's end add an exact zero)
         const float* D = q.dbuf + l * lstride + tid;
         GswSum db;
         float g0 = 0.f, g1 = 0.f;
-#pragma unroll 1
-        for (int s = s0; s < s1; s += 16) {
-            float d[16], x0[16], x1[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const int ss = s + u;
-                const bool ok = ss < s1;
-                d[u] = ok ? D[(size_t)ss * nhp] : 0.f;
-                x0[u] = x1[u] = 0.f;
-                if (ok && l == 0) { x0[u] = q.z[2 * (size_t)ss]; x1[u] = q.z[2 * (size_t)ss + 1]; }
-            }
-#pragma unroll
-            for (int u = 0; u < 16; ++u) { db.add(d[u]); g0 = fmaf(x0[u], d[u], g0); g1 = fmaf(x1[u], d[u], g1); }
-        }
+        mlpw_walk_samples<3>(s0, s1, [&](int ss, bool ok, float (&v)[3]) {
+            v[0] = ok ? D[(size_t)ss * nhp] : 0.f;
+            v[1] = v[2] = 0.f;
+            if (ok && l == 0) { v[1] = q.z[2 * (size_t)ss]; v[2] = q.z[2 * (size_t)ss + 1]; }
+        }, [&](const float (&v)[3]) { db.add(v[0]); g0 = fmaf(v[1], v[0], g0); g1 = fmaf(v[2], v[0], g1); });
         S[l * nhp + tid] = db.s;
         if (l == 0) { S[nhid * nhp + tid] = g0; S[(nhid + 1) * nhp + tid] = g1; }
         if (l == nhid - 1) {
-            const bool in = tid < nh;
             const float* A = q.pre + l * lstride + tid;
-            const float* St = q.stats + (size_t)l * 2 * nhp;
-            const float m = in ? St[tid] : 0.f, r = in ? St[nhp + tid] : 0.f, ga = in ? q.gamma[l][tid] : 0.f, be = in ? q.beta[l][tid] : 0.f;
+            const GswBnCol bn(q, l, tid);
             float w0 = 0.f, w1 = 0.f;
-#pragma unroll 1
-            for (int s = s0; s < s1; s += 16) {
-                float a[16], p0[16], p1[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) {
-                    const int ss = s + u;
-                    const bool ok = ss < s1;
-                    a[u] = (ok && in) ? fmaxf(fmaf((A[(size_t)ss * nhp] - m) * r, ga, be), 0.f) : 0.f;
-                    p0[u] = ok ? q.gplug[2 * (size_t)ss] : 0.f;
-                    p1[u] = ok ? q.gplug[2 * (size_t)ss + 1] : 0.f;
-                }
-#pragma unroll
-                for (int u = 0; u < 16; ++u) { w0 = fmaf(a[u], p0[u], w0); w1 = fmaf(a[u], p1[u], w1); }
-            }
+            mlpw_walk_samples<3>(s0, s1, [&](int ss, bool ok, float (&v)[3]) {
+                v[0] = (ok && bn.in) ? bn.h(A[(size_t)ss * nhp]) : 0.f;
+                v[1] = ok ? q.gplug[2 * (size_t)ss] : 0.f;
+                v[2] = ok ? q.gplug[2 * (size_t)ss + 1] : 0.f;
+            }, [&](const float (&v)[3]) { w0 = fmaf(v[0], v[1], w0); w1 = fmaf(v[0], v[2], w1); });
             S[(nhid + 2) * nhp + tid] = w0; S[(nhid + 3) * nhp + tid] = w1;
         }
     }
@@ -358,86 +271,16 @@ __global__ __launch_bounds__(MLPW_THREADS) void gsw_wgrad_kernel(GswGrad q, int 
     }
 }
 
-struct GswPtrs {
-    float* w[MLPW_MAX_LAYERS];
-    float* b[MLPW_MAX_LAYERS];
-    float* gw[MLPW_MAX_LAYERS];      // may be null
-    float* gb[MLPW_MAX_LAYERS];
-};
-
-// element e of [hidden -> hidden dW: (nl-2) nh nh | dW_0: 2 nh | dW_last: 2 nh | db_l: (nl-1) nh | db_last: 2]
-__global__ __launch_bounds__(256) void gsw_update_kernel(GswPtrs q, const float* __restrict__ pw, const float* __restrict__ ps, int nchunks, int sstride,
-                                                         int nlayers, int nh, int nhp, float lr) {
-    const int nhid = nlayers - 1, nhh = nh * nh, nbig = (nlayers - 2) * nhh, total = nbig + (nhid + 4) * nh + 2;
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-#pragma clang fp contract(off)      // var -= lr * grad as two roundings (GradientDescentOptimizer's ApplyGradientDescent)
-        const float* P;
-        size_t stride;
-        float *wv, *gv;
-        if (e < nbig) {
-            const int hl = e / nhh, r = e - hl * nhh, i = r / nh, j = r - i * nh;
-            stride = (size_t)nhp * nhp;
-            P = pw + (size_t)hl * nchunks * stride + (size_t)i * nhp + j;
-            wv = q.w[hl + 1] + r; gv = q.gw[hl + 1] ? q.gw[hl + 1] + r : nullptr;
-        } else {
-            int r = e - nbig;
-            stride = sstride;
-            if (r < 2 * nh) {                                   // dW_0 [2][nh]
-                P = ps + (nhid + r / nh) * nhp + r % nh;
-                wv = q.w[0] + r; gv = q.gw[0] ? q.gw[0] + r : nullptr;
-            } else if ((r -= 2 * nh) < 2 * nh) {                // dW_last [nh][2]
-                P = ps + (nhid + 2 + (r & 1)) * nhp + (r >> 1);
-                wv = q.w[nhid] + r; gv = q.gw[nhid] ? q.gw[nhid] + r : nullptr;
-            } else if ((r -= 2 * nh) < nhid * nh) {             // db_l [nh]
-                const int l = r / nh, j = r - l * nh;
-                P = ps + l * nhp + j;
-                wv = q.b[l] + j; gv = q.gb[l] ? q.gb[l] + j : nullptr;
-            } else {                                            // db_last [2]
-                r -= nhid * nh;
-                P = ps + (nhid + 4) * nhp + r;
-                wv = q.b[nhid] + r; gv = q.gb[nhid] ? q.gb[nhid] + r : nullptr;
-            }
-        }
-        float g = 0.f;
-        for (int c = 0; c < nchunks; ++c) g += P[c * stride];
-        if (gv) *gv = g;
-        if (lr != 0.f) *wv = *wv - lr * g;
-    }
-}
-
-static size_t gsw_fwd_floats(int B, int nlayers, int nhp) {          // genw_ws_floats of mlp2d_wide_gen.hip
-    return (size_t)(nlayers - 1) * nhp * ((size_t)B + 2 * (size_t)cgs_ceil_div(B, 32) + 2);
-}
-
-static int gsw_sstride(int nlayers, int nhp) { return (nlayers + 3) * nhp + 4; }
-
 static size_t gsw_ws_floats(int B, int nlayers, int nhp) {
     const size_t H = nlayers - 1, G = cgs_ceil_div(B, 32);
-    return gsw_fwd_floats(B, nlayers, nhp) + H * B * nhp + H * G * 3 * nhp + 2 * (size_t)B +
-           (size_t)MLPW_MAX_CHUNKS * ((size_t)(nlayers - 2) * nhp * nhp + gsw_sstride(nlayers, nhp));
+    return genw_ws_floats(B, nlayers, nhp) + H * B * nhp + H * G * 3 * nhp + 2 * (size_t)B +
+           (size_t)MLPW_MAX_CHUNKS * ((size_t)(nlayers - 2) * nhp * nhp + mlpw_small_stride(nlayers, nhp, 2));
 }
-
-template <int T>
-static int gsw_tile_launch(const GswLayer& a, bool top, hipStream_t st) {
-    const size_t smem = gsw_smem(T, a.nhp);
-    const dim3 grid(cgs_ceil_div(a.B, T)), block(MLPW_THREADS);
-    if (top) {
-        CGS_SMEM_ATTR(160 * 1024, "mlp2d_wide_g_step", gsw_top_kernel<T>);
-        hipLaunchKernelGGL(gsw_top_kernel<T>, grid, block, smem, st, a);
-    } else {
-        CGS_SMEM_ATTR(160 * 1024, "mlp2d_wide_g_step", gsw_layer_kernel<T>);
-        hipLaunchKernelGGL(gsw_layer_kernel<T>, grid, block, smem, st, a);
-    }
-    CGS_CHECK_LAUNCH("mlp2d_wide_g_step");
-    return CGS_OK;
-}
-
-static bool gsw_shape_ok(int nlayers, int nhidden) { return nlayers >= 2 && nlayers <= MLPW_MAX_LAYERS && nhidden >= 65 && nhidden <= 256; }
 
 extern "C" {
 
 size_t cgs_mlp2d_wide_g_step_ws_bytes(int B, int nlayers, int nhidden) {
-    if (B <= 0 || B > (1 << 24) || !gsw_shape_ok(nlayers, nhidden)) return 0;
+    if (B <= 0 || B > (1 << 24) || !mlpw_gen_shape_ok(nlayers, nhidden)) return 0;
     return gsw_ws_floats(B, nlayers, cgs_round_up(nhidden, 32)) * sizeof(float);
 }
 
@@ -445,30 +288,24 @@ int cgs_mlp2d_wide_g_step(float* const* w, float* const* b, const float* const* 
                           float* const* moving_variance, int nlayers, int nhidden, const float* z, const float* grad_plugin, int B, float eps,
                           float lr, float* const* gw, float* const* gb, float* x, void* ws, size_t ws_bytes, void* stream) {
     const char* who = "mlp2d_wide_g_step";
-    // the checks of cgs_mlp2d_g_step, in its order: shape, weights, grad_plugin, batch-norm variables, batch, workspace
-    if (!gsw_shape_ok(nlayers, nhidden)) return cgs_set_error(CGS_EINVAL, "%s: nlayers=%d nhidden=%d (need 2..6, 65..256)", who, nlayers, nhidden);
-    if (!w || !b) return cgs_set_error(CGS_EINVAL, "%s: null weight array", who);
-    for (int l = 0; l < nlayers; ++l)
-        if (!w[l] || !b[l]) return cgs_set_error(CGS_EINVAL, "%s: null weight", who);
+    int rc = mlp2d_check_net(who, (const float* const*)w, (const float* const*)b, nlayers, nhidden, MLPW_MIN_NH, MLPW_MAX_NH);
+    if (rc) return rc;
     if (!grad_plugin) return cgs_set_error(CGS_EINVAL, "%s: null grad_plugin", who);
-    if (!gamma || !beta || !moving_mean || !moving_variance) return cgs_set_error(CGS_EINVAL, "%s: null batch-norm array", who);
-    for (int l = 0; l < nlayers - 1; ++l)
-        if (!gamma[l] || !beta[l] || !moving_mean[l] || !moving_variance[l]) return cgs_set_error(CGS_EINVAL, "%s: null batch-norm variable", who);
-    if (!z || B < 2 || B > (1 << 24) || !(eps > 0.f)) return cgs_set_error(CGS_EINVAL, "%s: bad argument (B=%d, training=1)", who, B);
     const int nl = nlayers, nhp = cgs_round_up(nhidden, 32), H = nl - 1, G = cgs_ceil_div(B, 32);
-    const size_t need = gsw_ws_floats(B, nl, nhp) * sizeof(float);
-    if (!ws || ws_bytes < need) return cgs_set_error(CGS_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    rc = mlp2d_check_gen(who, gamma, beta, moving_mean, moving_variance, nl, z, B, 1 << 24, 1, eps, gsw_ws_floats(B, nl, nhp) * sizeof(float), ws,
+                         ws_bytes);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t lstride = (size_t)B * nhp, pstride = (size_t)G * 2 * nhp, bstride = (size_t)G * 3 * nhp;
     float* pre = (float*)ws;
     float* stats = pre + H * lstride + H * pstride;
-    float* dbuf = pre + gsw_fwd_floats(B, nl, nhp);
+    float* dbuf = pre + genw_ws_floats(B, nl, nhp);
     float* bpart = dbuf + H * lstride;
     float* xs = bpart + H * bstride;
     float* pw = xs + 2 * (size_t)B;
     float* ps = pw + (size_t)MLPW_MAX_CHUNKS * (nl - 2) * nhp * nhp;
-    int rc = cgs_mlp2d_wide_gen_fwd((const float* const*)w, (const float* const*)b, gamma, beta, moving_mean, moving_variance, nl, nhidden, z,
-                                    x ? x : xs, B, 1, eps, nullptr, ws, gsw_fwd_floats(B, nl, nhp) * sizeof(float), stream);
+    rc = cgs_mlp2d_wide_gen_fwd((const float* const*)w, (const float* const*)b, gamma, beta, moving_mean, moving_variance, nl, nhidden, z,
+                                    x ? x : xs, B, 1, eps, nullptr, ws, genw_ws_floats(B, nl, nhp) * sizeof(float), stream);
     if (rc) return rc;
     const int T = mlpw_tile(B);
     // top: output -> layer nl-2; then layer u -> u-1 for u = nl-2 .. 1; then layer 0 alone (its da)
@@ -486,11 +323,12 @@ int cgs_mlp2d_wide_g_step(float* const* w, float* const* b, const float* const* 
         }
         a.nh = nhidden; a.nhp = nhp; a.B = B;
         if (u > 0) {
-            rc = T == 32 ? gsw_tile_launch<32>(a, u == nl - 1, st) : gsw_tile_launch<64>(a, u == nl - 1, st);
+            rc = u == nl - 1 ? mlpw_launch_tile<gsw_top_kernel<32>, gsw_top_kernel<64>>(T, B, gsw_smem(T, nhp), who, who, st, a)
+                             : mlpw_launch_tile<gsw_layer_kernel<32>, gsw_layer_kernel<64>>(T, B, gsw_smem(T, nhp), who, who, st, a);
             if (rc) return rc;
         } else {
             hipLaunchKernelGGL(gsw_first_kernel, dim3(cgs_ceil_div(B, 64)), dim3(MLPW_THREADS), 0, st, a);
-            CGS_CHECK_LAUNCH("mlp2d_wide_g_step");
+            CGS_CHECK_LAUNCH(who);
         }
     }
     GswGrad q = {};
@@ -498,19 +336,11 @@ int cgs_mlp2d_wide_g_step(float* const* w, float* const* b, const float* const* 
     for (int l = 0; l < H; ++l) { q.gamma[l] = gamma[l]; q.beta[l] = beta[l]; }
     q.z = z; q.gplug = grad_plugin; q.pw = pw; q.ps = ps;
     q.nlayers = nl; q.nh = nhidden; q.nhp = nhp; q.B = B;
-    q.chunk = mlpw_chunk(B); q.nchunks = cgs_ceil_div(B, q.chunk); q.sstride = gsw_sstride(nl, nhp);
-    const int NB2 = (nhp / 32 + 1) / 2, nmfma = cgs_ceil_div((nl - 2) * q.nchunks * NB2 * NB2, 4);
+    q.chunk = mlpw_chunk(B); q.nchunks = cgs_ceil_div(B, q.chunk); q.sstride = mlpw_small_stride(nl, nhp, 2);
+    const int nmfma = mlpw_wgrad_blocks(nl, nhp, q.nchunks);
     hipLaunchKernelGGL(gsw_wgrad_kernel, dim3(nmfma + q.nchunks * H), dim3(MLPW_THREADS), 0, st, q, nmfma);
-    CGS_CHECK_LAUNCH("mlp2d_wide_g_step");
-    GswPtrs p;
-    for (int l = 0; l < MLPW_MAX_LAYERS; ++l) {
-        p.w[l] = l < nl ? w[l] : nullptr; p.b[l] = l < nl ? b[l] : nullptr;
-        p.gw[l] = (gw && l < nl) ? gw[l] : nullptr; p.gb[l] = (gb && l < nl) ? gb[l] : nullptr;
-    }
-    const int total = (nl - 2) * nhidden * nhidden + (H + 4) * nhidden + 2;
-    hipLaunchKernelGGL(gsw_update_kernel, dim3(cgs_ceil_div(total, 256)), dim3(256), 0, st, p, pw, ps, q.nchunks, q.sstride, nl, nhidden, nhp, lr);
-    CGS_CHECK_LAUNCH("mlp2d_wide_g_step");
-    return CGS_OK;
+    CGS_CHECK_LAUNCH(who);
+    return mlpw_update<2>(who, mlpw_vars(w, b, gw, gb, nl), pw, ps, q.nchunks, nl, nhidden, nhp, lr, nullptr, st);
 }
 
 }  // extern "C"

@@ -24,7 +24,7 @@
 // So pass B needs no column bound, and reads rows s >= B_total of its last chunk as zero.
 //   floats: acts   [nl-1][Bt][nhp] | deltas [nl-1][Bt][nhp] | dlast [Bt] | bce [Bt]
 //           | partial dW  [nl-2][16][nhp][nhp]
-//           | partial small [16][(nl-1) nhp (db_l) + 2 nhp (dW_0) + nhp (dW_last) + 4 (db_last, loss real, loss fake, 0)]
+//           | partial small [16][mlpw_small_stride at one output: (nl-1) nhp (db_l) + 2 nhp (dW_0) + nhp (dW_last) + 4 (db_last, loss real, loss fake, 0)]
 // At 256 x 6 and 1000 + 1000 rows: 20.5 MB of activations and gradients + 16.8 MB of partial tiles = 37.3 MB.
 #include "mlp2d_wide.h"
 
@@ -40,7 +40,7 @@ struct MlpWTrainWs {
 
 static size_t mlpw_train_ws_floats(int Bt, int nlayers, int nhp) {
     const size_t nhid = nlayers - 1;
-    return 2 * nhid * Bt * nhp + 2 * (size_t)Bt + (size_t)MLPW_MAX_CHUNKS * ((nlayers - 2) * (size_t)nhp * nhp + (nhid + 3) * nhp + 4);
+    return 2 * nhid * Bt * nhp + 2 * (size_t)Bt + (size_t)MLPW_MAX_CHUNKS * ((nlayers - 2) * (size_t)nhp * nhp + mlpw_small_stride(nlayers, nhp, 1));
 }
 
 static MlpWTrainWs mlpw_train_ws(float* ws, int Bt, int nlayers, int nhp) {
@@ -52,18 +52,8 @@ static MlpWTrainWs mlpw_train_ws(float* ws, int Bt, int nlayers, int nhp) {
     s.bce = s.dlast + Bt;
     s.pw = s.bce + Bt;
     s.ps = s.pw + (size_t)MLPW_MAX_CHUNKS * (nlayers - 2) * nhp * nhp;
-    s.Bt = Bt; s.chunk = mlpw_chunk(Bt); s.nchunks = cgs_ceil_div(Bt, s.chunk); s.sstride = (int)(nhid + 3) * nhp + 4;
+    s.Bt = Bt; s.chunk = mlpw_chunk(Bt); s.nchunks = cgs_ceil_div(Bt, s.chunk); s.sstride = mlpw_small_stride(nlayers, nhp, 1);
     return s;
-}
-
-// the tile's H (LDS image, unit j at hpos(j)) -> dst[row0 + row][j], rows of the tile below `rows` only
-template <int T>
-__device__ __forceinline__ void mlpw_store_h(const MlpWLds& L, int nhp, float* __restrict__ dst, int rows) {
-    const int HS = nhp + 4;
-    for (int e = threadIdx.x; e < T * nhp; e += MLPW_THREADS) {
-        const int row = e / nhp, j = e - row * nhp;
-        if (row < rows) dst[(size_t)row * nhp + j] = L.H[row * HS + hpos(j)];
-    }
 }
 
 template <int T>
@@ -72,36 +62,28 @@ __global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void mlpw_train_kern
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const MlpWLds L = mlpw_lds<T>(smem, p.nlayers, p.nhp);
     mlpw_load(p, L);
-    const int tid = threadIdx.x, nh = p.nh, nhp = p.nhp, NB = nhp >> 5, HS = nhp + 4, nl = p.nlayers;
+    const int tid = threadIdx.x, nh = p.nh, nhp = p.nhp, nl = p.nlayers, MW = T * (nhp >> 5);
     const long row0 = (long)blockIdx.x * T;
     const int rows = (int)(B - row0 < T ? B - row0 : T);                   // rows of this tile that exist
     const size_t lstride = (size_t)ws.Bt * nhp, base = (size_t)(part0 + row0) * nhp;
     if (tid < 2 * T) L.xs[tid] = (tid >> 1) < rows ? x[2 * row0 + tid] : 0.f;
     __syncthreads();
-    for (int e = tid; e < T * nhp; e += MLPW_THREADS) {                     // as mlpw_eval
-        const int row = e / nhp, j = e - row * nhp;
-        float a = 0.f;
-        if (j < nh) a = fmaf(L.xs[2 * row + 1], p.w[0][nh + j], fmaf(L.xs[2 * row], p.w[0][j], p.b[0][j]));
-        const unsigned long long m = __ballot(a > 0.f);
-        if ((tid & 31) == 0) L.masks[row * NB + (j >> 5)] = (unsigned)((tid & 32) ? m >> 32 : m);
-        L.H[row * HS + hpos(j)] = fmaxf(a, 0.f);
-    }
+    // mlpw_eval's composition, H stored after every layer and the top gradient seeded
+    mlpw_first<T, true>(L, L.xs, p.w[0], p.b[0], nh, nhp, L.masks);
     __syncthreads();
     mlpw_store_h<T>(L, nhp, ws.acts + base, rows);
     for (int l = 1; l < nl - 1; ++l) {
-        mlpw_pass<T, false>(p, L, p.w[l], p.b[l], l);
+        mlpw_pass<T, false>(L, nh, nhp, p.w[l], p.b[l], L.masks, l);
         mlpw_store_h<T>(L, nhp, ws.acts + l * lstride + base, rows);
     }
-    const int row = tid >> 2, q4 = tid & 3;
     if (tid < 4 * T) {
-        float part = 0.f;
-        for (int q = q4; q < nhp; q += 4) part = fmaf(L.H[row * HS + q], L.wlp[q], part);
-        part += __shfl_xor(part, 1, 64);
-        part += __shfl_xor(part, 2, 64);
-        const float logit = part + p.b[nl - 1][0];
+        const int row = tid >> 2;
+        float v[1];
+        mlpw_rowdot<1>(L, L.wlp, nhp, v);
+        const float logit = v[0] + p.b[nl - 1][0];
         const float seed = scale * (mlpw_sigmoid(logit) - target);        // d (scale * BCE(logit, target)) / d logit
-        if (q4 == 0) {
-            L.xs[row] = seed;                                              // the points are spent: xs carries the seeds to the next loop
+        if ((tid & 3) == 0) {
+            L.xs[row] = seed;                                              // the points are spent: xs carries the seeds to the top gradient
             if (row < rows) {
                 ws.dlast[part0 + row0 + row] = seed;
                 ws.bce[part0 + row0 + row] = scale * (fmaxf(logit, 0.f) - logit * target + log1pf(expf(-fabsf(logit))));
@@ -109,20 +91,16 @@ __global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void mlpw_train_kern
         }
     }
     __syncthreads();
-    for (int e = tid; e < T * nhp; e += MLPW_THREADS) {
-        const int row_ = e / nhp, j = e - row_ * nhp;
-        const unsigned mw = L.masks[((nl - 2) * T + row_) * NB + (j >> 5)];
-        L.H[row_ * HS + hpos(j)] = (j < nh && ((mw >> (j & 31)) & 1u)) ? L.xs[row_] * p.w[nl - 1][j] : 0.f;
-    }
+    mlpw_top_grad<T, true>(L, L.masks + (nl - 2) * MW, p.w[nl - 1], L.xs, nh, nhp);
     __syncthreads();
     mlpw_store_h<T>(L, nhp, ws.deltas + (nl - 2) * lstride + base, rows);
     for (int l = nl - 2; l >= 1; --l) {
-        mlpw_pass<T, true>(p, L, p.w[l], nullptr, l - 1);
+        mlpw_pass<T, true>(L, nh, nhp, p.w[l], nullptr, L.masks, l - 1);
         mlpw_store_h<T>(L, nhp, ws.deltas + (l - 1) * lstride + base, rows);
     }
 }
 
-// blocks [0, nmfma): 4 waves, wave task t = 4 block + wave -> (hidden -> hidden layer, chunk, 64 x 64 block of dW).
+// blocks [0, nmfma): mlpw_wgrad_mfma, the A fragment loaded from acts.
 // blocks [nmfma, nmfma + nchunks (nl-1)): (chunk, hidden layer l): thread j < nhp sums column j of Delta_l over the chunk (db_l); l = 0 adds
 // x^T Delta_0; l = nl-2 adds A_{nl-2}^T dlast and, in threads 0..2, sum dlast and the two loss sums.
 __global__ __launch_bounds__(MLPW_THREADS) void mlpw_wgrad_kernel(MlpWTrainWs ws, int nlayers, int nhp, int nmfma, const float* __restrict__ xr, int Br,
@@ -130,83 +108,32 @@ __global__ __launch_bounds__(MLPW_THREADS) void mlpw_wgrad_kernel(MlpWTrainWs ws
     const int tid = threadIdx.x, Bt = ws.Bt, nhid = nlayers - 1;
     const size_t lstride = (size_t)Bt * nhp;
     if ((int)blockIdx.x < nmfma) {
-        const int NB = nhp >> 5, NB2 = (NB + 1) >> 1, per = NB2 * NB2;
-        const int lane = tid & 63, h = lane >> 5, c31 = lane & 31;
-        const int t = blockIdx.x * 4 + (tid >> 6);
-        if (t >= (nlayers - 2) * ws.nchunks * per) return;
-        const int lc = t / per, blk = t - lc * per, hl = lc / ws.nchunks, c = lc - hl * ws.nchunks;     // hl = 0: dW of layer 1
-        const int ti = 2 * (blk / NB2), tj = 2 * (blk % NB2);
-        const bool i1 = ti + 1 < NB, j1 = tj + 1 < NB;
-        const int s0 = c * ws.chunk, s1 = min(Bt, s0 + ws.chunk);
-        const float* A = ws.acts + hl * lstride + ti * 32 + c31;
-        const float* D = ws.deltas + (hl + 1) * lstride + tj * 32 + c31;
-        mlpw_f16 acc[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-#pragma unroll 1
-        for (int s = s0; s < s1; s += 8) {                                  // 4 MFMA steps of 2 samples; the chunk size is a multiple of 8
-            float a0[4], a1[4], b0[4], b1[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {                                   // rows past the chunk's end (the last chunk's past B_total) read as zero
-                const int ss = s + 2 * u + h;
-                const bool ok = ss < s1;
-                const size_t o = (size_t)ss * nhp;
-                a0[u] = ok ? A[o] : 0.f; a1[u] = (ok && i1) ? A[o + 32] : 0.f;
-                b0[u] = ok ? D[o] : 0.f; b1[u] = (ok && j1) ? D[o + 32] : 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], b0[u], acc[0][0], 0, 0, 0);
-                if (j1) acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], b1[u], acc[0][1], 0, 0, 0);
-                if (i1) acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], b0[u], acc[1][0], 0, 0, 0);
-                if (i1 && j1) acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], b1[u], acc[1][1], 0, 0, 0);
-            }
-        }
-        float* P = ws.pw + (size_t)lc * nhp * nhp;                          // [layer][chunk][nhp][nhp]
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                if ((a && !i1) || (b && !j1)) continue;
-#pragma unroll
-                for (int r = 0; r < 16; ++r)     // accumulator element r of lane (h, c31): row (r & 3) + 8 (r >> 2) + 4 h, column c31
-                    P[(size_t)((ti + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * nhp + (tj + b) * 32 + c31] = acc[a][b][r];
-            }
+        mlpw_wgrad_mfma(nlayers, nhp, Bt, ws.chunk, ws.nchunks, ws.deltas, ws.pw, [&](int hl, int col, bool i1) {
+            return [A = ws.acts + hl * lstride + col, i1](size_t o, bool ok, float& a0, float& a1) {
+                a0 = ok ? A[o] : 0.f; a1 = (ok && i1) ? A[o + 32] : 0.f;
+            };
+        });
         return;
     }
     const int sb = blockIdx.x - nmfma, c = sb / nhid, l = sb - c * nhid;
     const int s0 = c * ws.chunk, s1 = min(Bt, s0 + ws.chunk);
     float* S = ws.ps + (size_t)c * ws.sstride;
     if (tid < nhp) {
-        // 16 samples' loads in flight, then their terms added in ascending sample order: the sums are those of a plain serial loop without
-        // a load's latency per term (the chunk size is a multiple of 16; rows past the chunk's end add an exact zero)
         const float* D = ws.deltas + l * lstride + tid;
         float db = 0.f, g0 = 0.f, g1 = 0.f;
-#pragma unroll 1
-        for (int s = s0; s < s1; s += 16) {
-            float d[16], x0[16], x1[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const int ss = s + u;
-                const bool ok = ss < s1;
-                d[u] = ok ? D[(size_t)ss * nhp] : 0.f;
-                x0[u] = x1[u] = 0.f;
-                if (ok && l == 0) {
-                    const float* xp = ss < Br ? xr + 2 * (size_t)ss : xf + 2 * (size_t)(ss - Br);
-                    x0[u] = xp[0]; x1[u] = xp[1];
-                }
+        mlpw_walk_samples<3>(s0, s1, [&](int ss, bool ok, float (&v)[3]) {
+            v[0] = ok ? D[(size_t)ss * nhp] : 0.f;
+            v[1] = v[2] = 0.f;
+            if (ok && l == 0) {
+                const float* xp = ss < Br ? xr + 2 * (size_t)ss : xf + 2 * (size_t)(ss - Br);
+                v[1] = xp[0]; v[2] = xp[1];
             }
-#pragma unroll
-            for (int u = 0; u < 16; ++u) { db += d[u]; g0 = fmaf(x0[u], d[u], g0); g1 = fmaf(x1[u], d[u], g1); }
-        }
+        }, [&](const float (&v)[3]) { db += v[0]; g0 = fmaf(v[1], v[0], g0); g1 = fmaf(v[2], v[0], g1); });
         S[l * nhp + tid] = db;
         if (l == 0) { S[nhid * nhp + tid] = g0; S[(nhid + 1) * nhp + tid] = g1; }
         if (l == nhid - 1) {
             const float* A = ws.acts + l * lstride + tid;
+            // not through mlpw_walk_samples: with it the compiler turns every load of both walks into a branch of its own
             float g = 0.f;
 #pragma unroll 1
             for (int s = s0; s < s1; s += 16) {
@@ -233,63 +160,6 @@ __global__ __launch_bounds__(MLPW_THREADS) void mlpw_wgrad_kernel(MlpWTrainWs ws
     }
 }
 
-struct MlpWTrainPtrs {
-    float* w[MLPW_MAX_LAYERS];
-    float* b[MLPW_MAX_LAYERS];
-    float* gw[MLPW_MAX_LAYERS];      // may be null
-    float* gb[MLPW_MAX_LAYERS];
-};
-
-// element e of [hidden -> hidden dW: (nl-2) nh nh | dW_0: 2 nh | dW_last: nh | db_l: (nl-1) nh | db_last: 1 | loss: 2]
-__global__ __launch_bounds__(256) void mlpw_update_kernel(MlpWTrainPtrs q, MlpWTrainWs ws, int nlayers, int nh, int nhp, float lr, float* __restrict__ loss) {
-    const int nhid = nlayers - 1, nhh = nh * nh, nbig = (nlayers - 2) * nhh, total = nbig + (nhid + 3) * nh + 3;
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-#pragma clang fp contract(off)      // var -= lr * grad as two roundings (GradientDescentOptimizer's ApplyGradientDescent)
-        const float* P;
-        size_t stride;
-        float *wv, *gv;
-        if (e < nbig) {
-            const int hl = e / nhh, r = e - hl * nhh, i = r / nh, j = r - i * nh;
-            stride = (size_t)nhp * nhp;
-            P = ws.pw + (size_t)hl * ws.nchunks * stride + (size_t)i * nhp + j;
-            wv = q.w[hl + 1] + r; gv = q.gw[hl + 1] ? q.gw[hl + 1] + r : nullptr;
-        } else {
-            int r = e - nbig;
-            stride = ws.sstride;
-            if (r < 2 * nh) {                                   // dW_0 [2][nh]
-                P = ws.ps + (nhid + r / nh) * nhp + r % nh;
-                wv = q.w[0] + r; gv = q.gw[0] ? q.gw[0] + r : nullptr;
-            } else if ((r -= 2 * nh) < nh) {                    // dW_last [nh][1]
-                P = ws.ps + (nhid + 2) * nhp + r;
-                wv = q.w[nhid] + r; gv = q.gw[nhid] ? q.gw[nhid] + r : nullptr;
-            } else if ((r -= nh) < nhid * nh) {                 // db_l [nh]
-                const int l = r / nh, j = r - l * nh;
-                P = ws.ps + l * nhp + j;
-                wv = q.b[l] + j; gv = q.gb[l] ? q.gb[l] + j : nullptr;
-            } else if ((r -= nhid * nh) == 0) {                 // db_last
-                P = ws.ps + (nhid + 3) * nhp;
-                wv = q.b[nhid]; gv = q.gb[nhid];
-            } else {                                            // d_loss_real, d_loss_fake
-                P = ws.ps + (nhid + 3) * nhp + r;
-                wv = nullptr; gv = loss ? loss + (r - 1) : nullptr;
-            }
-        }
-        float g = 0.f;
-        for (int c = 0; c < ws.nchunks; ++c) g += P[c * stride];
-        if (gv) *gv = g;
-        if (wv && lr != 0.f) *wv = *wv - lr * g;
-    }
-}
-
-template <int T>
-static int mlpw_train_launch(const MlpWParams& p, const float* x, int B, int part0, float target, const MlpWTrainWs& ws, hipStream_t st) {
-    const size_t smem = mlpw_smem(T, p.nlayers, p.nhp);
-    CGS_SMEM_ATTR(160 * 1024, "mlp2d_wide_d_step", mlpw_train_kernel<T>);
-    hipLaunchKernelGGL(mlpw_train_kernel<T>, dim3(cgs_ceil_div(B, T)), dim3(MLPW_THREADS), smem, st, p, x, B, part0, target, 1.f / (float)B, ws);
-    CGS_CHECK_LAUNCH("mlpw_train");
-    return CGS_OK;
-}
-
 size_t cgs_mlp2d_wide_train_ws(int Bt, int nlayers, int nh) { return mlpw_train_ws_floats(Bt, nlayers, cgs_round_up(nh, 32)) * sizeof(float); }
 
 // the caller (mlp2d.hip) has checked every argument and the workspace size; 64 < nh <= 256
@@ -300,22 +170,14 @@ int cgs_mlp2d_wide_train(float* const* w, float* const* b, int nlayers, int nh, 
     const int Bt = B_real + B_fake, nhp = p.nhp, nhid = nlayers - 1;
     const MlpWTrainWs ws = mlpw_train_ws((float*)ws_, Bt, nlayers, nhp);
     for (int part = 0; part < 2; ++part) {      // real rows (target 1) then fake rows (target 0); each loss term is a MEAN
-        const int B = part ? B_fake : B_real, part0 = part ? B_real : 0;
-        const float* x = part ? fake : real;
-        const int rc = mlpw_tile(B) == 32 ? mlpw_train_launch<32>(p, x, B, part0, part ? 0.f : 1.f, ws, st)
-                                          : mlpw_train_launch<64>(p, x, B, part0, part ? 0.f : 1.f, ws, st);
+        const int B = part ? B_fake : B_real, part0 = part ? B_real : 0, T = mlpw_tile(B);
+        const int rc = mlpw_launch_tile<mlpw_train_kernel<32>, mlpw_train_kernel<64>>(T, B, mlpw_smem(T, nlayers, nhp), "mlp2d_wide_d_step", "mlpw_train",
+                                                                                      st, p, part ? fake : real, B, part0, part ? 0.f : 1.f,
+                                                                                      1.f / (float)B, ws);
         if (rc) return rc;
     }
-    const int NB2 = (nhp / 32 + 1) / 2, nmfma = cgs_ceil_div((nlayers - 2) * ws.nchunks * NB2 * NB2, 4);
+    const int nmfma = mlpw_wgrad_blocks(nlayers, nhp, ws.nchunks);
     hipLaunchKernelGGL(mlpw_wgrad_kernel, dim3(nmfma + ws.nchunks * nhid), dim3(MLPW_THREADS), 0, st, ws, nlayers, nhp, nmfma, real, B_real, fake);
     CGS_CHECK_LAUNCH("mlpw_wgrad");
-    MlpWTrainPtrs q;
-    for (int l = 0; l < MLPW_MAX_LAYERS; ++l) {
-        q.w[l] = l < nlayers ? w[l] : nullptr; q.b[l] = l < nlayers ? b[l] : nullptr;
-        q.gw[l] = (gw && l < nlayers) ? gw[l] : nullptr; q.gb[l] = (gb && l < nlayers) ? gb[l] : nullptr;
-    }
-    const int total = (nlayers - 2) * nh * nh + (nhid + 3) * nh + 3;
-    hipLaunchKernelGGL(mlpw_update_kernel, dim3(cgs_ceil_div(total, 256)), dim3(256), 0, st, q, ws, nlayers, nh, nhp, lr, loss);
-    CGS_CHECK_LAUNCH("mlpw_update");
-    return CGS_OK;
+    return mlpw_update<1>("mlpw_update", mlpw_vars(w, b, gw, gb, nlayers), ws.pw, ws.ps, ws.nchunks, nlayers, nh, nhp, lr, loss, st);
 }

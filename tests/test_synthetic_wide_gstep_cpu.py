@@ -194,6 +194,96 @@ def test_narrow_g_step_still_stops_at_64_units():
     assert msg.startswith(b"mlp2d_g_step") and b"nlayers" in msg
 
 
+def _ladder(fn, narrow, step):
+    """-> [(what, call arguments, return code, message)] of every refusal of a generator entry point, in the order the entry point checks.
+    The pointer arrays are host arrays of non-null dummy addresses: every rung returns before anything is dereferenced on the device."""
+    import ctypes as C
+    from cgs_amd import lib
+    who = fn[4:].encode()
+    nl, nh, B = (6, 64, 1000) if narrow else (6, 256, 1000)
+    buf = (C.c_float * 4)()
+    addr = C.addressof(buf)
+    full = lambda n: (C.c_void_p * 6)(*([addr] * n + [None] * (6 - n)))
+    W, BN = full(nl), full(nl - 1)
+    l = lib.load()
+    if narrow:
+        need = lambda b: int(l.cgs_mlp2d_gen_ws_bytes(b, nl, 1 if step else 0))
+    else:
+        need = lambda b: int(getattr(l, "cgs_mlp2d_wide_g_step_ws_bytes" if step else "cgs_mlp2d_wide_gen_ws_bytes")(b, nl, nh))
+
+    def args(w=W, b=W, gamma=BN, beta=BN, mm=BN, mv=BN, nl_=nl, nh_=nh, z=addr, out=addr, B_=B, train=1, eps=1e-5, ws=addr, ws_bytes=None):
+        ws_bytes = need(B_) if ws_bytes is None else ws_bytes
+        if step:        # w b gamma beta mm mv nl nh z grad_plugin B eps lr gw gb x ws ws_bytes stream
+            return (w, b, gamma, beta, mm, mv, nl_, nh_, z, out, B_, eps, 5e-3, None, None, None, ws, ws_bytes, None)
+        return (w, b, gamma, beta, mm, mv, nl_, nh_, z, out, B_, train, eps, None, ws, ws_bytes, None)
+
+    lo, hi = (1, 64) if narrow else (65, 256)
+    shape = lambda a, h: b"%s: nlayers=%d nhidden=%d (need 2..6, %d..%d)" % (who, a, h, lo, hi)
+    badarg = lambda b_, t: b"%s: bad argument (B=%d, training=%d)" % (who, b_, t)
+    E, EW = lib.EINVAL, lib.EWORKSPACE
+    rungs = [
+        ("one layer", args(nl_=1), E, shape(1, nh)),
+        ("seven layers", args(nl_=7), E, shape(7, nh)),
+        ("too wide", args(nh_=hi + 1), E, shape(nl, hi + 1)),
+        ("too narrow", args(nh_=lo - 1), E, shape(nl, lo - 1)),
+        ("shape before anything else", args(nl_=7, w=None, out=None, gamma=None, B_=0, eps=0.0, ws=None), E, shape(7, nh)),
+        ("null w array", args(w=None), E, who + b": null weight array"),
+        ("null b array", args(b=None), E, who + b": null weight array"),
+        ("a null weight", args(w=full(nl - 1)), E, who + b": null weight"),
+        ("a null bias", args(b=full(nl - 1)), E, who + b": null weight"),
+        ("weights before the output", args(w=full(nl - 1), out=None, gamma=None), E, who + b": null weight"),
+        ("null output / grad_plugin", args(out=None), E, who + (b": null grad_plugin" if step else b": null output")),
+        ("output before batch norm", args(out=None, gamma=None, B_=0), E, who + (b": null grad_plugin" if step else b": null output")),
+    ]
+    for k in ("gamma", "beta", "mm", "mv"):
+        rungs.append(("null %s array" % k, args(**{k: None}), E, who + b": null batch-norm array"))
+    rungs.append(("arrays before variables", args(gamma=full(nl - 2), beta=None), E, who + b": null batch-norm array"))
+    for k in ("gamma", "beta", "mm", "mv"):
+        rungs.append(("a null %s" % k, args(**{k: full(nl - 2)}), E, who + b": null batch-norm variable"))
+    rungs.append(("batch norm before the batch", args(mv=full(nl - 2), B_=0, ws=None), E, who + b": null batch-norm variable"))
+    rungs += [
+        ("null z", args(z=None), E, badarg(B, 1)),
+        ("B = 1 in training", args(B_=1), E, badarg(1, 1)),
+        ("B = 0", args(B_=0), E, badarg(0, 1)),
+        ("B < 0", args(B_=-5), E, badarg(-5, 1)),
+        ("eps = 0", args(eps=0.0), E, badarg(B, 1)),
+        ("eps < 0", args(eps=-1e-5), E, badarg(B, 1)),
+        ("eps nan", args(eps=float("nan")), E, badarg(B, 1)),
+        ("the batch before the workspace", args(B_=1, ws=None, ws_bytes=0), E, badarg(1, 1)),
+    ]
+    if not step:
+        rungs += [("B = 0 at inference", args(B_=0, train=0), E, badarg(0, 0)),
+                  ("eps = 0 at inference", args(train=0, eps=0.0), E, badarg(B, 0)),
+                  ("any non-zero is_training is training", args(B_=1, train=7), E, badarg(1, 1))]
+    if not narrow:
+        rungs.append(("B = 2^24 + 1", args(B_=(1 << 24) + 1, ws_bytes=1 << 40), E, badarg((1 << 24) + 1, 1)))
+        if not step:
+            rungs.append(("B = 2^24 + 1 at inference", args(B_=(1 << 24) + 1, train=0, ws_bytes=1 << 40), E, badarg((1 << 24) + 1, 0)))
+    n = need(B)
+    assert n > 4
+    wsmsg = lambda have: b"%s: workspace %d < %d bytes" % (who, have, n)
+    rungs += [
+        ("short workspace", args(ws_bytes=n - 4), EW, wsmsg(n - 4)),
+        ("no workspace bytes", args(ws_bytes=0), EW, wsmsg(0)),
+        ("null workspace", args(ws=None), EW, wsmsg(n)),
+    ]
+    if not step:
+        rungs.append(("short workspace at inference", args(train=0, ws_bytes=n - 4), EW, wsmsg(n - 4)))
+    return l, rungs
+
+
+@pytest.mark.parametrize("fn,narrow,step", [("cgs_mlp2d_gen_fwd", True, False), ("cgs_mlp2d_g_step", True, True),
+                                            ("cgs_mlp2d_wide_gen_fwd", False, False), ("cgs_mlp2d_wide_g_step", False, True)])
+def test_generator_entry_points_refuse_in_one_order_with_one_text(fn, narrow, step):
+    """The whole refusal ladder of the four generator entry points -- shape, weight arrays, weights, output or grad_plugin, batch-norm
+    arrays, batch-norm variables, batch and eps, workspace -- rung by rung: the return code and the full text of cgs_last_error().
+    Every rung returns before the first device call."""
+    l, rungs = _ladder(fn, narrow, step)
+    for what, a, rc, msg in rungs:
+        assert getattr(l, fn)(*a) == rc, (fn, what)
+        assert l.cgs_last_error() == msg, (fn, what)
+
+
 def test_wide_g_step_workspace_size():
     from cgs_amd import lib
     l = lib.load()
