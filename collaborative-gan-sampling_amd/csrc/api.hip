@@ -11,6 +11,10 @@ static thread_local const char* g_last_kernel = "";
 static thread_local double g_last_flops = 0.0;
 static thread_local int g_last_tail[2] = {0, 0};
 void cgs_note_tail(int tiles, int split) { g_last_tail[0] = tiles; g_last_tail[1] = split; }
+static thread_local int g_last_plan[5] = {0, 0, 0, 0, 0};
+void cgs_note_igemm_plan(int xcd_map, int cls_flip, int uni, int gx, int splitk) {
+    g_last_plan[0] = xcd_map; g_last_plan[1] = cls_flip; g_last_plan[2] = uni; g_last_plan[3] = gx; g_last_plan[4] = splitk;
+}
 static thread_local int g_contraction = CGS_CONTRACTION_F32;
 int cgs_contraction_mode() { return g_contraction; }
 
@@ -34,6 +38,9 @@ const char* cgs_last_kernel(void) { return g_last_kernel; }
 double cgs_last_executed_flops(void) { return g_last_flops; }
 int cgs_last_tail_tiles(void) { return g_last_tail[0]; }
 int cgs_last_tail_split(void) { return g_last_tail[1]; }
+void cgs_last_igemm_plan(int out[5]) {
+    if (out) for (int i = 0; i < 5; ++i) out[i] = g_last_plan[i];
+}
 int cgs_set_contraction(int mode) {
     if (mode < CGS_CONTRACTION_F32 || mode > CGS_CONTRACTION_BX6_ALL) return cgs_set_error(CGS_EINVAL, "set_contraction: mode %d", mode);
     g_contraction = mode;
@@ -150,6 +157,7 @@ static int run_dir(const ConvCall& c, int B, const float* in, const float* w, co
     const bool dirT = c.dirT, nstats = x.form == FORM_NSTATS;
     cgs_note_flops(0.0);
     cgs_note_tail(0, 0);
+    cgs_note_igemm_plan(0, 0, 0, 0, 0);
     if (B <= 0) return cgs_set_error(CGS_EINVAL, "%s: B=%d", who, B);
     if (!in || !w || !out) return cgs_set_error(CGS_EINVAL, "%s: null tensor", who);
     if (epilogue < CGS_EPI_NONE || epilogue > CGS_EPI_TANH_BWD) return cgs_set_error(CGS_EINVAL, "%s: epilogue %d", who, epilogue);

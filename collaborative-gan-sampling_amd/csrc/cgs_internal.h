@@ -11,6 +11,7 @@ void cgs_note_kernel(const char* name);   // remembered per thread, read back by
 void cgs_note_flops(double executed);     // ... by cgs_last_executed_flops()
 void cgs_add_flops(double executed);      // (accumulating form: one entry point may launch several batch chunks)
 void cgs_note_tail(int tiles, int split); // ... by cgs_last_tail_tiles() / cgs_last_tail_split()
+void cgs_note_igemm_plan(int xcd_map, int cls_flip, int uni, int gx, int splitk);   // ... by cgs_last_igemm_plan()
 
 #define CGS_CHECK_LAUNCH(name)                                                        \
     do {                                                                              \

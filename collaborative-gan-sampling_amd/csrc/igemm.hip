@@ -1358,6 +1358,7 @@ static int launch_cfg(const IgemmParams& p, hipStream_t s) {
     static char name[64];
     snprintf(name, sizeof(name), "%s<%d, %d, %d, %s, %d, %s>", TW == 2 ? "igemm_up_kernel" : TW == 1 ? "igemm_ns_kernel" : "igemm_kernel", BM, BN, NW, VEC ? "true" : "false", TBK, PAR ? "true" : "false");
     cgs_note_kernel(name);
+    cgs_note_igemm_plan(q.xcd_map, q.cls_flip, p.uni, (int)gx, p.splitk > 1 ? p.splitk : 1);
     return CGS_OK;
 }
 

@@ -37,6 +37,7 @@ SIGNATURES = {
     "cgs_last_executed_flops": (C.c_double, []),
     "cgs_last_tail_tiles": (_i, []),
     "cgs_last_tail_split": (_i, []),
+    "cgs_last_igemm_plan": (None, [C.POINTER(C.c_int)]),
     "cgs_set_contraction": (_i, [_i]),
     "cgs_get_contraction": (_i, []),
     "cgs_conv_ws_bytes": (_z, [_i] * 7),
@@ -237,6 +238,13 @@ def get_contraction():
 def last_kernel():
     """Name of the kernel the last conv / deconv / linear dispatch launched (as rocprofv3 prints it)."""
     return load().cgs_last_kernel().decode()
+
+
+def last_igemm_plan():
+    """(xcd_map, cls_flip, uni, gx, splitk) of the last implicit-GEMM launch; all 0 when the last conv-family call ran another family."""
+    out = (C.c_int * 5)()
+    load().cgs_last_igemm_plan(out)
+    return tuple(out)
 
 
 def conv_ws_bytes(op, kh, kw, sh, sw, cin, cout):

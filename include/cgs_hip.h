@@ -99,6 +99,11 @@ double cgs_last_executed_flops(void);
  * tests.  The partial tiles are added in a fixed order: results stay bit-identical from run to run. */
 int cgs_last_tail_tiles(void);
 int cgs_last_tail_split(void);
+/* Launch plan of the calling thread's most recent implicit-GEMM launch (all 0: the call ran another family), for tests:
+ * out[0] = per-XCD block decode on (1) / off (0), out[1] = classes per group reversed in odd rounds (0 = no flip),
+ * out[2] = uniform-tile K loop allowed, out[3] = grid x (block ids per class and K slice), out[4] = split-K factor (1 = none).
+ * Scheduling details of csrc/igemm.hip: results do not depend on them. */
+void cgs_last_igemm_plan(int out[5]);
 
 /* Contraction arithmetic of the implicit-GEMM layers, per calling THREAD (default CGS_CONTRACTION_F32; no process-wide state).
  * F32: v_mfma_f32_32x32x2_f32 -- exact fp32 products, an fp32 fma chain over K: what tf.nn.conv2d / conv2d_transpose / matmul

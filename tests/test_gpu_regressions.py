@@ -237,7 +237,8 @@ def test_tail_split_launches(case):
     """Round 5: a launch whose tiles fill ONE partial round of workgroup slots (T = a * 256 + r tiles) contracts its last r tiles in
     several K slices (csrc/igemm.hip, igemm_choose_tail; partial tiles added in a fixed order by tail_reduce_kernel) -- the product plan,
     case "linear_bwd_mnist".  The other cases are launches of several rounds, whose short last round is not cut (measured, not
-    adopted: the comment above igemm_choose_tail); they skip here.  The big launch must agree with the same op on 64-sample
+    adopted: the comment above igemm_choose_tail).  Split or not, the tiles and the split are what the restated planner of
+    tests/igemm_cases.py predicts for the call.  The big launch must agree with the same op on 64-sample
     pieces (small grids: the oracle-pinned paths), carry its epilogue through the reduce kernel, and be bit-identical from run to run."""
     from cgs_amd import kernels as K, lib as L
     d = torch.device("cuda:0")
@@ -264,10 +265,15 @@ def test_tail_split_launches(case):
         args = (x,)
     big = run(*args)
     tiles, split = int(lib.cgs_last_tail_tiles()), int(lib.cgs_last_tail_split())
-    if tiles == 0:
-        assert case != "linear_bwd_mnist", "the one-round tail split is the product plan for this launch"
-        pytest.skip("launches of several rounds are not split (measured, not adopted)")
-    assert split >= 2, (case, tiles, split, L.last_kernel())
+    import igemm_cases as IC              # the restated planner says, for the device's compute-unit count, whether and how this launch is split
+    call = {"linear_bwd_mnist": (IC.BD, B, 1, 1, 6272, 1024, 1, 1), "deconv_bwd_mnist": (IC.TB, B, 7, 7, 128, 64, 4, 2),
+            "conv_bwd_aux": (IC.BD, B, 14, 14, 64, 128, 4, 2), "deconv_fwd_affine": (IC.TF, B, 7, 7, 128, 64, 4, 2)}[case]
+    pred = IC.case_plan(lib, IC.Case(*call, "plain", IC.EPI_NONE, "full", ""), torch.cuda.get_device_properties(d).multi_processor_count)
+    assert (tiles, split) == (pred.tail_n, pred.tail_s if pred.tail_s > 1 else 0), (case, tiles, split, pred.tail_n, pred.tail_s, L.last_kernel())
+    assert L.last_kernel() == pred.kernel
+    if torch.cuda.get_device_properties(d).multi_processor_count == 256:
+        assert case != "linear_bwd_mnist" or tiles > 0, "the one-round tail split is the product plan for this launch"
+    assert tiles == 0 or split >= 2, (case, tiles, split, L.last_kernel())
     pieces = torch.cat([run(*[t[i:i + 64].contiguous() for t in args]) for i in range(0, B, 64)])
     assert int(lib.cgs_last_tail_tiles()) == 0                             # (the small grids do not split a tail)
     assert torch.allclose(big, pieces, rtol=0, atol=2e-5 * pieces.abs().max().item()), (big - pieces).abs().max().item()
