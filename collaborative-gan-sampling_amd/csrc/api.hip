@@ -141,7 +141,7 @@ struct NsArgs { const float *mean, *invstd, *gamma, *beta; float leak; int group
 // as partial rows in stat_part; FORM_NSTATS (*_bwd_data_nstats): the norm backward's two column sums, from ns and x_norm (in ep_aux);
 // FORM_SIGNS (*_signs): a forward leaves the sign mask of its output in sign_out, a backward-data takes aux_signs for the fp32 ep_aux;
 // FORM_UPDATE (*_bwd_data_update): the result is not stored -- the momentum step of the refinement loop is applied to ``out`` (the feature) and up_mom.
-enum ConvForm { FORM_PLAIN, FORM_STATS, FORM_NSTATS, FORM_SIGNS, FORM_UPDATE };
+enum ConvForm { FORM_PLAIN = CGS_FORM_PLAIN, FORM_STATS = CGS_FORM_STATS, FORM_NSTATS = CGS_FORM_NSTATS, FORM_SIGNS = CGS_FORM_SIGNS, FORM_UPDATE = CGS_FORM_UPDATE };
 struct ConvExtras {
     ConvForm form = FORM_PLAIN;
     float* stat_part = nullptr; size_t stat_part_bytes = 0;
@@ -392,6 +392,21 @@ int cgs_conv_update_form(int op, int B, int H, int W, int Cin, int Ho, int Wo, i
     if (ws_bytes < packed) return 0;
     if (row_order) *row_order = cgs_igemm_row_order(q.g);
     return cgs_igemm_update_form(q.g, ws_bytes - packed);
+}
+
+// ---- the launch plan of a call before it is launched (cgs_hip.h; host only) ----
+int cgs_conv_igemm_plan(int op, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw, int epilogue, int form,
+                        size_t ws_bytes, cgs_igemm_plan_info* info, unsigned char* perm) {
+    if (!info || form < CGS_FORM_PLAIN || form > CGS_FORM_UPDATE || epilogue < CGS_EPI_NONE || epilogue > CGS_EPI_TANH_BWD) return 0;
+    const ConvPlan q = conv_plan_of(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, ws_bytes);
+    if (q.fam != CGS_FAMILY_IGEMM || check_layer(q.c.L, "conv_igemm_plan")) return 0;
+    if (q.c.dirT && (sh > 2 || sw > 2)) return 0;
+    // (the forms are the entry points': statistics and sign masks of a forward, norm-backward statistics and the update of a backward-data)
+    if (q.c.bwd != (form == CGS_FORM_NSTATS || form == CGS_FORM_UPDATE) && form != CGS_FORM_PLAIN) return 0;
+    if (!whole_batch_in_one_launch(q.g)) return 0;                  // the entry point would split the batch
+    const size_t packed = cgs_packed_floats(q.g) * sizeof(float);
+    if (ws_bytes < packed) return 0;
+    return cgs_igemm_plan_info_of(q.g, form, ws_bytes - packed, info, perm);
 }
 
 // ---- sign masks (cgs_hip.h): the activation gradient of relu / lrelu needs one bit per element of the saved activation ----

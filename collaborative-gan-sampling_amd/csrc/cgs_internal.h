@@ -120,6 +120,27 @@ __host__ __device__ inline int cgs_tap_order(int i, int n, int parity_first) {
     return i < ne ? 2 * i : 2 * (i - ne) + 1;
 }
 
+// GEMM rows of parity class i of a launch
+static inline long cgs_igemm_rows(const IgemmParams& p, int i) { return (long)p.B * p.cls[i].R * p.cls[i].C; }
+// one launch addresses its tensors with 32-bit byte offsets (the caller splits the batch)
+static inline bool cgs_igemm_over_2gib(const IgemmParams& p) {
+    return (long)p.B * p.Hout * p.Wout * p.N * 4 > 0x7fffffffL || (long)p.B * p.Hin * p.Win * p.Cred * 4 > 0x7fffffffL;
+}
+// Fused statistics: one partial row per (128-row tile, wave row), the parity classes back to back (equal M: cgs_conv_stat_layout).
+// -> partial rows per class (IgemmParams::stat_cls_rows), -1 = parity classes of unequal size
+static inline int cgs_igemm_stat_cls_rows(const IgemmParams& p) {
+    const long M0 = cgs_igemm_rows(p, 0);
+    for (int i = 1; i < p.nclasses; ++i)
+        if (cgs_igemm_rows(p, i) != M0) return -1;
+    return (int)(2 * ((M0 + 127) / 128));
+}
+// Block ids per class (grid x) of a launch of mtiles x nblk_n tiles, and the decode that reads them (IgemmParams::xcd_map; igemm_kernel,
+// igemm_bx6_kernel): the per-XCD decode runs over the m-tile count padded to 8
+static inline long cgs_igemm_grid_x(long mtiles, int nblk_n, int* xcd_map) {
+    *xcd_map = (mtiles % 8 == 0 || mtiles >= 64) ? 1 : 0;        // per-XCD decode only where it keeps the 8 XCDs evenly loaded
+    return (*xcd_map ? (mtiles + 7) / 8 * 8 : mtiles) * nblk_n;
+}
+
 // geometry builders (igemm.hip)
 void cgs_geom_F(const CgsLayer& L, IgemmParams& p);
 void cgs_geom_T(const CgsLayer& L, IgemmParams& p);
@@ -142,6 +163,8 @@ int cgs_contraction_mode();                             // thread-local: CGS_CON
 // cgs_hip.h, 0 = it cannot (the launcher then refuses up_mom)
 int cgs_igemm_update_form(const IgemmParams& p, size_t slab_bytes);
 int cgs_igemm_row_order(const IgemmParams& p);       // GEMM row order the launcher will pick: 0 (image, pixel); 1 (pixel, image); 2 (pixel, image) in whole 128-image tiles
+// the launch's whole plan for cgs_conv_igemm_plan (form: CGS_FORM_*; 0 = the launcher would refuse the form)
+int cgs_igemm_plan_info_of(const IgemmParams& p, int form, size_t slab_bytes, cgs_igemm_plan_info* info, unsigned char* perm);
 size_t cgs_convt_quad_ws_floats_bound(int kh, int kw, int Cs);
 int cgs_convt_taps_ok(const CgsLayer& L);          // 4x4 stride-2 transposed conv to one channel: all 16 taps as MFMA columns (convt_taps.hip)
 int cgs_convt_taps_launch(const CgsLayer& L, int B, const float* in, const float* w, const float* bias, float* out, int epilogue,

@@ -24,6 +24,7 @@
 // conflict-free).
 #include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "cgs_internal.h"
 #include "igemm_epilogue.h"
@@ -1055,8 +1056,15 @@ __global__ __launch_bounds__(256) void tail_reduce_kernel(IgemmParams p, int BM,
 
 static long igemm_blocks(const IgemmParams& p, int BN, int BM = 128) {
     long blocks = 0;
-    for (int i = 0; i < p.nclasses; ++i) blocks += (((long)p.B * p.cls[i].R * p.cls[i].C + BM - 1) / BM) * (p.Np / BN);
+    for (int i = 0; i < p.nclasses; ++i) blocks += ((cgs_igemm_rows(p, i) + BM - 1) / BM) * (p.Np / BN);
     return blocks;
+}
+
+// base pixels per image of the largest parity class
+static int igemm_max_rc(const IgemmParams& p) {
+    int maxRC = 0;
+    for (int i = 0; i < p.nclasses; ++i) maxRC = p.cls[i].R * p.cls[i].C > maxRC ? p.cls[i].R * p.cls[i].C : maxRC;
+    return maxRC;
 }
 
 // split factor for grids that leave most of the 256 CUs (x2 block slots) idle
@@ -1084,7 +1092,7 @@ static int choose_splitk(const IgemmParams& p) {
     double slice_mb = 0.0;
     long maxM = 0;
     for (int i = 0; i < p.nclasses; ++i) {
-        const long m = (long)p.B * p.cls[i].R * p.cls[i].C;
+        const long m = cgs_igemm_rows(p, i);
         if (m <= 0) continue;
         const int nk = cgs_ceil_div(p.cls[i].K, BK);
         if (nk > nk_max) nk_max = nk;
@@ -1105,11 +1113,36 @@ static int choose_splitk(const IgemmParams& p) {
 }
 
 // Block tile of a launch (the row policy and the split-K decision are made): 128 x 128 or 128 x 64 (``wide``), 32- or 16-deep K tiles
-// (``deep``); ``mid`` = a mid-size grid that took the narrow tile to fill the block slots.  One function: the launcher and the
-// workspace sizing (tail split) must agree on it.
+// (``deep``); ``mid`` = a mid-size grid that took the narrow tile to fill the block slots.
 struct IgemmTiles { bool wide, mid, deep, tall, wide_for_tail; };
-struct IgemmTail { int from, n, s; };
-static IgemmTail igemm_choose_tail(const IgemmParams& p, const IgemmTiles& t);
+struct IgemmTail { int n, s; };          // the last n tiles of the launch, s K-slices each (s <= 1: no tail split)
+
+// What a launch carries beside the plain contraction, as the planner sees it (the launcher derives it from the stat_part / ns_mean /
+// sign_out / up_mom pointers, a query states it): statistics, the norm-backward twin of them, a sign mask, the fused momentum update.
+struct IgemmForm { bool stats, ns, signs, update; };
+
+// The plan of one launch: igemm_plan() fills it from the geometry, the form and the slab bytes on offer; cgs_igemm_launch applies it and
+// every host query reads it.  Nothing else decides anything about a launch.
+struct IgemmPlan {
+    const char* refusal;         // != null: the launcher's error text, the form is not offered for this geometry (nothing below is planned)
+    IgemmForm form;
+    int BM, BN, TBK, twin;       // the instantiation igemm_{,ns_,up_}kernel<BM, BN, 4, vec, TBK, par> (twin: 0 plain, 1 ns, 2 up)
+    bool vec, par;
+    int splitk;                  // split-K factor (1: none) and the classes' slab offsets in floats
+    int slab_off[CGS_MAX_CLASSES];
+    IgemmTail tail;              // tail split; its first id is gx_tiles - tail.n
+    int pix_major, lpt;          // row order, and the final permutation of the base pixels (lpt only)
+    unsigned char perm[CGS_MAX_CLASSES][256];
+    int stat_cls_rows;
+    int xcd_map, cls_flip, uni, prio_t[3];
+    long gx_tiles, gx;           // block ids per class: one per tile (padded ids included), and with tail.s ids for each tail tile; 0 = nothing to launch
+    int update;                  // CGS_UPDATE_*: where the fused update is applied (0: not an update launch)
+    size_t slab_bytes;           // slab bytes the plan uses (split-K slabs or the tail's partial tiles)
+    double flops;                // executed FLOPs
+    int reduce;                  // the kernel that follows (CGS_REDUCE_* of cgs_hip.h), and its grid
+    unsigned reduce_grid[3];
+};
+static IgemmTail igemm_choose_tail(const IgemmParams& p, const IgemmPlan& pl, const IgemmTiles& t);
 
 // The launch-shape rules below that reason about "rounds" of workgroups (the tail split, the class flip, the one-round balancing) are
 // written for the 256 compute units of an MI355X: the kernel's flip decode shifts by 8 and the planners deal blocks modulo 256.  The
@@ -1126,22 +1159,22 @@ static bool igemm_round_rules_apply() {
 }
 
 // ``tail_wide``: may the rule "wide tiles + tail split" be taken (the launcher asks again without it when the caller's slab is too small)
-static IgemmTiles igemm_choose_tiles(const IgemmParams& p, bool tail_wide = true) {
+// (p: the geometry; pl: the plan so far -- the form, the row order, the split-K factor)
+static IgemmTiles igemm_choose_tiles(const IgemmParams& p, const IgemmPlan& pl, bool tail_wide) {
     const bool vec = p.vec != 0;
-    int maxRC = 0;
-    for (int i = 0; i < p.nclasses; ++i) maxRC = p.cls[i].R * p.cls[i].C > maxRC ? p.cls[i].R * p.cls[i].C : maxRC;
+    const int maxRC = igemm_max_rc(p);
     bool wide = (p.Np % 128) == 0, wide_for_tail = false;
-    if (wide && p.lpt && maxRC <= 64) {   // uneven tiles (9..25 valid taps on grids <= 8x8) need >= 2 rounds of blocks over the 512 block slots to balance: halve BN if short
+    if (wide && pl.lpt && maxRC <= 64) {   // uneven tiles (9..25 valid taps on grids <= 8x8) need >= 2 rounds of blocks over the 512 block slots to balance: halve BN if short
         long blocks = 0;
-        for (int i = 0; i < p.nclasses; ++i) blocks += ((long)p.B * p.cls[i].R * p.cls[i].C / 128) * (p.Np / 128);
+        for (int i = 0; i < p.nclasses; ++i) blocks += (cgs_igemm_rows(p, i) / 128) * (p.Np / 128);
         if (blocks < 1024) wide = false;
         // ... unless the wide tiles make ONE partial round that the tail split evens out (igemm_choose_tail: 512 < T <= 1024 tiles at four
         // per CU, a remainder of at most 176 over whole CUs, no statistics / sign mask to leave): mnist's 7x7 128<-64 backward-data, 784
         // tiles, 200.2 us as 1568 narrow tiles -> 183.4 us (0.72 -> 0.79 of peak; profiles/r05_e_wide_tail_ab.txt)
         // -- and only if the tail planner, asked about exactly that tiling, does split it (it can still say no: an m-tile count that the per-XCD
         // decode pads, fewer than eight K tiles): otherwise the launch would run the partial round of wide tiles the rule above avoids
-        if (!wide && tail_wide && vec && p.splitk == 1 && !p.stat_part && !p.sign_out && (p.N & 3) == 0 && p.nclasses == 1 && blocks >= 512 && blocks <= 1024 &&
-            (blocks % 256) != 0 && (blocks % 256) <= 176 && igemm_choose_tail(p, IgemmTiles{true, false, false, false, true}).s > 1) {
+        if (!wide && tail_wide && vec && pl.splitk == 1 && !pl.form.stats && !pl.form.signs && (p.N & 3) == 0 && p.nclasses == 1 && blocks >= 512 && blocks <= 1024 &&
+            (blocks % 256) != 0 && (blocks % 256) <= 176 && igemm_choose_tail(p, pl, IgemmTiles{true, false, false, false, true}).s > 1) {
             wide = true;
             wide_for_tail = true;
         }
@@ -1158,26 +1191,26 @@ static IgemmTiles igemm_choose_tiles(const IgemmParams& p, bool tail_wide = true
     // 32x32 256->512 302 -> 265 us (not for grids < 256 blocks, which are split over K instead: 32x32 256<-512 272 -> 295 us)
     // (with the 32-deep K tiles: the same grids as 16-deep 128x64 blocks measured 93 / 329 us for the last two)
     bool mid = false;
-    if (wide && vec && p.splitk == 1) {
+    if (wide && vec && pl.splitk == 1) {
         const long wb = igemm_blocks(p, 128);
         if (wb >= 256 && wb < 512) { wide = false; mid = true; }
         // a launch that leaves a sign mask (one-pass epilogue only), or statistics when the workspace has no room for the split-K slabs
         // (with room it is split: splitk_reduce_stats_kernel): under 256 blocks of 128x128 it would leave most CUs idle (config 5's
         // PatchGAN 4x4 128->256 layer: 128 blocks, 54 TFLOP/s) -- as 128x64 blocks at least every CU gets one
-        else if (wb < 256 && (p.stat_part || p.sign_out)) { wide = false; mid = true; }
+        else if (wb < 256 && (pl.form.stats || pl.form.signs)) { wide = false; mid = true; }
     }
     bool deep = true;
-    if (vec && p.splitk == 1 && !mid) {
+    if (vec && pl.splitk == 1 && !mid) {
         long min_blocks = 1L << 40, tot_blocks = 0;
         for (int i = 0; i < p.nclasses; ++i) {
-            const long m = (long)p.B * p.cls[i].R * p.cls[i].C;
+            const long m = cgs_igemm_rows(p, i);
             if (m > 0) { const long bl = (m + 127) / 128 * (p.Np / (wide ? 128 : 64)); if (bl < min_blocks) min_blocks = bl; tot_blocks += bl; }
         }
         deep = min_blocks < 512;        // (thresholds 256 / 512 / 1024 measured: 512 is best on dcgan64 and neutral elsewhere)
         // ... except image-major launches whose classes TOGETHER fill the 1024 slots of the 16-deep form with even tiles (the four
         // parity classes of config 5's transposed layers, 256 blocks each: 128x128 64<-128 102 -> 86 us, 64x64 256->128 164 -> 152 us);
         // the pixel-major 8x8 256<-512 layer of dcgan64 (1024 very uneven blocks) stays 32-deep: 0.61 vs 0.74 ms
-        if (deep && !p.pix_major && p.nclasses > 1 && tot_blocks >= 1024) deep = false;
+        if (deep && !pl.pix_major && p.nclasses > 1 && tot_blocks >= 1024) deep = false;
     }
     // Tall tiles, 256 x 64 (four 64 x 64 wave tiles stacked: the per-wave shape of the 128 x 128 block), for launches to 64 output channels
     // whose K loops are SHORT (<= 512 per class: 32 tiles of 16) and whose grid is many rounds of blocks: half the blocks, so half the
@@ -1190,7 +1223,7 @@ static IgemmTiles igemm_choose_tiles(const IgemmParams& p, bool tail_wide = true
         int kmax = 0;
         for (int i = 0; i < p.nclasses; ++i) kmax = p.cls[i].K > kmax ? p.cls[i].K : kmax;
         // (pixel-major launches only: config 5's image-major 128x128 128->64 transposed layer, K = 512, measured 166.8 -> 168.8 us)
-        tall = vec && !wide && !mid && !deep && p.splitk == 1 && p.Np == 64 && p.pix_major && (p.B % 256) == 0 && kmax <= 512 &&
+        tall = vec && !wide && !mid && !deep && pl.splitk == 1 && p.Np == 64 && pl.pix_major && (p.B % 256) == 0 && kmax <= 512 &&
                igemm_blocks(p, 64, 256) >= 1536;
     }
     return IgemmTiles{wide, mid, deep, tall, wide_for_tail && wide};
@@ -1209,13 +1242,13 @@ static int igemm_blocks_per_cu(bool wide, bool deep) { return deep ? (wide ? 2 :
 // Launches of SEVERAL rounds (T = q * L + r on L = 256 * blocks-per-CU slots, the short last round cut the same way) were measured too and
 // are NOT split: +2 % / +-0 / +4.5 % on three of them, -3.4 % and -1.3 % on two (dcgan32 16x16 64<-128, dcgan64 32x32 64<-128: their
 // last round already overlaps the tail of the one before, and the slices pay a prologue, a raw 32 KB store and the reduce pass each).
-static IgemmTail igemm_choose_tail(const IgemmParams& p, const IgemmTiles& t) {
-    IgemmTail none{0, 0, 0};
+static IgemmTail igemm_choose_tail(const IgemmParams& p, const IgemmPlan& pl, const IgemmTiles& t) {
+    IgemmTail none{0, 0};
     if (!igemm_round_rules_apply()) return none;
-    if (!p.vec || p.splitk > 1 || p.stat_part || p.sign_out || (p.N & 3) || t.tall) return none;
+    if (!p.vec || pl.splitk > 1 || pl.form.stats || pl.form.signs || (p.N & 3) || t.tall) return none;
     const int bn = t.wide ? 128 : 64, tbk = t.deep ? 32 : 16;
     const IgemmClass& cl = p.cls[p.nclasses - 1];
-    const long Ml = (long)p.B * cl.R * cl.C;
+    const long Ml = cgs_igemm_rows(p, p.nclasses - 1);
     if (Ml <= 0) return none;
     const long mtl = (Ml + 127) / 128, Tl = mtl * (p.Np / bn);          // tiles of the last class
     const long T = igemm_blocks(p, bn);
@@ -1231,136 +1264,15 @@ static IgemmTail igemm_choose_tail(const IgemmParams& p, const IgemmTiles& t) {
     if (S < 2) return none;
     if (r > Tl) r = Tl;
     for (int i = 0; i < p.nclasses; ++i)                                 // (one id space for all classes: equal sizes only)
-        if ((long)p.B * p.cls[i].R * p.cls[i].C != Ml) return none;
+        if (cgs_igemm_rows(p, i) != Ml) return none;
     // the tail tiles are the LAST ids of the last class in the launch's own decode (per-XCD decode: ids run over the padded m-tile count)
-    const bool xcd_map = (mtl % 8 == 0 || mtl >= 64);
-    const long ids = (xcd_map ? (mtl + 7) / 8 * 8 : mtl) * (p.Np / bn);
+    int xcd_map;
+    cgs_igemm_grid_x(mtl, p.Np / bn, &xcd_map);
     if (xcd_map && (mtl % 8) != 0) return none;                          // (padded ids decode to no tile: keep the tail dense)
-    return IgemmTail{(int)(ids - r), (int)r, S};
+    return IgemmTail{(int)r, S};
 }
 
 static size_t igemm_tail_bytes(const IgemmTail& tl, bool wide) { return (size_t)tl.n * tl.s * 128 * (wide ? 128 : 64) * sizeof(float); }
-
-// slab bytes behind the packed weights a launch of this geometry can use: split-K slabs (under-filled grids) or tail-split partial tiles
-size_t cgs_igemm_slab_bytes(const IgemmParams& p_in) {
-    const size_t sk = cgs_igemm_splitk_bytes(p_in);
-    if (sk) return sk;
-    IgemmParams p = p_in;
-    p.splitk = 1; p.stat_part = nullptr; p.sign_out = nullptr;
-    cgs_igemm_row_policy(p, 128);
-    const IgemmTiles t = igemm_choose_tiles(p);
-    const IgemmTail tl = igemm_choose_tail(p, t);
-    return tl.s > 1 ? igemm_tail_bytes(tl, t.wide) : 0;
-}
-
-int cgs_igemm_signs_ok(const IgemmParams& p) {
-    return (p.N % 32) == 0 && (p.epilogue == CGS_EPI_AFFINE_RELU || p.epilogue == CGS_EPI_LRELU) && choose_splitk(p) <= 1;
-}
-
-size_t cgs_igemm_splitk_bytes(const IgemmParams& p) {
-    const int s = choose_splitk(p);
-    if (s <= 1) return 0;
-    size_t n = 0;
-    for (int i = 0; i < p.nclasses; ++i) n += (size_t)s * p.B * p.cls[i].R * p.cls[i].C * p.Np;
-    return n * sizeof(float);
-}
-
-// The fused momentum update (IgemmParams::up_*): where would a launch of this geometry, with slab_bytes of workspace behind its packed
-// weights, apply it -- the planning steps of cgs_igemm_launch in its order (split-K first, then the tile and the tail split), so the answer
-// given before a capture is the launch's own.  0 = not offered: the generic-K gather (Cred % 32 != 0), N % 4 != 0, an epilogue, statistics
-// or a sign mask on the same launch, the tall 256 x 64 tile (no twin is instantiated for it).
-int cgs_igemm_update_form(const IgemmParams& p_in, size_t slab_bytes) {
-    IgemmParams p = p_in;
-    if (!p.vec || (p.N & 3) || p.epilogue != CGS_EPI_NONE || p.bias || p.stat_part || p.sign_out) return 0;
-    p.splitk = 1; p.slab = nullptr;
-    p.tail_from = p.tail_n = p.tail_s = 0;
-    cgs_igemm_row_policy(p, 128);
-    const size_t need = cgs_igemm_splitk_bytes(p);
-    if (need && slab_bytes >= need) return CGS_UPDATE_SPLITK;
-    IgemmTiles tiles = igemm_choose_tiles(p);
-    IgemmTail tl = igemm_choose_tail(p, tiles);
-    bool tail_fits = tl.s > 1 && slab_bytes >= igemm_tail_bytes(tl, tiles.wide);
-    if (tiles.wide_for_tail && !tail_fits) {
-        tiles = igemm_choose_tiles(p, false);
-        tl = igemm_choose_tail(p, tiles);
-        tail_fits = tl.s > 1 && slab_bytes >= igemm_tail_bytes(tl, tiles.wide);
-    }
-    if (tiles.tall) return 0;
-    return tail_fits ? CGS_UPDATE_TAIL : CGS_UPDATE_EPILOGUE;
-}
-
-// TW: the kernel twin -- 0 igemm_kernel, 1 igemm_ns_kernel (norm-backward sums), 2 igemm_up_kernel (fused momentum update)
-template <int BM, int BN, int NW, bool VEC, int TBK, bool PAR, int TW>
-static int launch_cfg(const IgemmParams& p, hipStream_t s) {
-    void (*kern)(IgemmParams);
-    if constexpr (TW == 2) kern = igemm_up_kernel<BM, BN, NW, VEC, TBK, PAR>;
-    else if constexpr (TW == 1) kern = igemm_ns_kernel<BM, BN, NW, VEC, TBK, PAR>;
-    else kern = igemm_kernel<BM, BN, NW, VEC, TBK, PAR>;
-    constexpr int EH = (VEC && TBK == 16) ? 2 : 1;
-    constexpr int WM = BM / 64;
-    constexpr size_t kloop_f = (size_t)2 * BM * (TBK + 4) + 2 * TBK * BN, stage_f = (size_t)NW * (BM / WM / EH) * (BN / (NW / WM) + 4);
-    constexpr size_t smem = (kloop_f > stage_f ? kloop_f : stage_f) * sizeof(float) + BM * sizeof(int);
-    static bool attr_done[64] = {};       // per device: the attribute belongs to the device's code object
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    dev_ &= 63;
-    if (!attr_done[dev_]) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return cgs_set_error(CGS_ELAUNCH, "igemm smem attr: %s", hipGetErrorString(e));
-        attr_done[dev_] = true;
-    }
-    long maxM = 0;
-    for (int i = 0; i < p.nclasses; ++i) {
-        long m = (long)p.B * p.cls[i].R * p.cls[i].C;
-        if (m > maxM) maxM = m;
-    }
-    if (maxM == 0) return CGS_OK;
-    const long mtiles = (maxM + BM - 1) / BM;
-    IgemmParams q = p;
-    q.xcd_map = (mtiles % 8 == 0 || mtiles >= 64) ? 1 : 0;        // per-XCD decode only where it keeps the 8 XCDs evenly loaded
-    long gx = (q.xcd_map ? (mtiles + 7) / 8 * 8 : mtiles) * (p.Np / BN);
-    if (p.tail_s > 1) {          // the tail tiles' ids are replaced by tail_s ids each (the planner and this decode agree: igemm_choose_tail)
-        if ((long)p.tail_from + p.tail_n != gx) return cgs_set_error(CGS_EINVAL, "igemm: tail split planned for another grid (%d + %d != %ld)", p.tail_from, p.tail_n, gx);
-        gx = (long)p.tail_from + (long)p.tail_n * p.tail_s;
-    }
-    unsigned gy = (unsigned)p.nclasses;
-    // (image-major launches of two rounds only: measured per stage at 64 / 128 / 256 images, profiles/r05_ai_class_flip_ab.txt -- dcgan64 at batch 64: 102.5 -> 89.0,
-    // 95.2 -> 82.4, 89.9 -> 77.5 us; the pixel-major launches of 128- and 256-image batches, whose tiles differ by pixel as well, lose up to 14 % with it)
-    {
-        // (the flip decides per CLASS range of gx blocks which round it lies in: those ranges must not straddle a round -- gx divides 256 --
-        // and a group of classes that is reversed must lie inside one round)
-        const long total = gx * (long)p.nclasses * (p.splitk > 1 ? p.splitk : 1);
-        q.cls_flip = 0;
-        if (igemm_round_rules_apply() && p.nclasses > 1 && !p.pix_major && total > 256 && total <= 512 && gx > 0 && (256 % gx) == 0 && p.tail_s <= 1) {
-            const long per_round = 256 / gx;                          // class ranges per round of 256 blocks
-            if (p.splitk > 1 && (per_round % p.nclasses) == 0) q.cls_flip = p.nclasses;                 // whole K slices per round: reverse all classes
-            else if (p.splitk == 1 && per_round < p.nclasses && (p.nclasses % per_round) == 0) q.cls_flip = (int)per_round;      // several rounds per slice
-        }
-    }
-    if (gx > 0x7fffffffL) return cgs_set_error(CGS_EINVAL, "igemm: grid too large");
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, gy, p.splitk > 1 ? p.splitk : 1), dim3(64 * NW), smem, s, q);
-    CGS_CHECK_LAUNCH("igemm");
-    if (p.tail_s > 1) {
-        if (p.up_mom) hipLaunchKernelGGL(tail_reduce_kernel<true>, dim3((unsigned)p.tail_n, TAIL_RSPLIT), dim3(256), 0, s, q, BM, BN);
-        else hipLaunchKernelGGL(tail_reduce_kernel<false>, dim3((unsigned)p.tail_n, TAIL_RSPLIT), dim3(256), 0, s, q, BM, BN);
-        CGS_CHECK_LAUNCH("tail_reduce");
-    }
-    if (p.splitk > 1) {
-        long tot = 0;
-        for (int i = 0; i < p.nclasses; ++i) { long t = (long)p.B * p.cls[i].R * p.cls[i].C * (p.Np / 4); if (t > tot) tot = t; }
-        unsigned rb = (unsigned)((tot + 63) / 64 > 4096 ? 4096 : (tot + 63) / 64);       // 64 output quads per 256-thread block
-        if (p.stat_part) hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3((unsigned)p.stat_cls_rows, (unsigned)((p.N + 31) / 32), p.nclasses), dim3(256), 0, s, p);
-        else if (p.up_mom) hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3(rb, p.nclasses), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(rb, p.nclasses), dim3(256), 0, s, p);
-        CGS_CHECK_LAUNCH("splitk_reduce");
-    }
-    // the name rocprofv3 prints for this instantiation
-    static char name[64];
-    snprintf(name, sizeof(name), "%s<%d, %d, %d, %s, %d, %s>", TW == 2 ? "igemm_up_kernel" : TW == 1 ? "igemm_ns_kernel" : "igemm_kernel", BM, BN, NW, VEC ? "true" : "false", TBK, PAR ? "true" : "false");
-    cgs_note_kernel(name);
-    cgs_note_igemm_plan(q.xcd_map, q.cls_flip, p.uni, (int)gx, p.splitk > 1 ? p.splitk : 1);
-    return CGS_OK;
-}
 
 // pixel-major row order (a tile = ONE base pixel of 128 images, so a tap that falls into the zero padding does so for the
 // whole tile and is skipped) pays when the batch fills whole tiles and the pixel grid is small enough that the padding is a
@@ -1368,116 +1280,98 @@ static int launch_cfg(const IgemmParams& p, hipStream_t s) {
 // -3..-5.6 % per layer, also for the 268 MB input of the 32x32x64 forward layer, which no longer fits the Infinity Cache:
 // the ~128 blocks an XCD runs at once are 128 pixels of the SAME image group, so the re-reads meet in its L2)
 static bool igemm_pix_major(const IgemmParams& p) {
-    int maxRC = 0;
-    for (int i = 0; i < p.nclasses; ++i) maxRC = p.cls[i].R * p.cls[i].C > maxRC ? p.cls[i].R * p.cls[i].C : maxRC;
+    const int maxRC = igemm_max_rc(p);
     const size_t in_bytes = (size_t)p.B * p.Hin * p.Win * p.Cred * 4;
     return p.vec && p.B >= 128 && maxRC <= 256 && maxRC > 1 && in_bytes <= ((size_t)384 << 20);
 }
 
+// taps of base pixel ``pix`` of class c that fall inside the input image
+static int igemm_valid_taps(const IgemmParams& p, const IgemmClass& c, int pix) {
+    const int r = pix / c.C, cc = pix - r * c.C;
+    int ny = 0, nx = 0;
+    for (int ta = 0; ta < c.nty; ++ta) { const int iy = r * p.S + c.dy0 + ta * p.dstep; ny += (iy >= 0 && iy < p.Hin); }
+    for (int tb = 0; tb < c.ntx; ++tb) { const int ix = cc * p.S + c.dx0 + tb * p.dstep; nx += (ix >= 0 && ix < p.Win); }
+    return ny * nx;
+}
+
 // GEMM row order of a launch and, for whole-tile pixel-major launches, the heaviest-first pixel order (BM = rows of a block tile)
-void cgs_igemm_row_policy(IgemmParams& p, int BM) {
-    p.pix_major = igemm_pix_major(p);
-    p.lpt = p.pix_major && (p.B % BM) == 0;
-    if (p.lpt)
+static void igemm_row_policy(const IgemmParams& p, int BM, int& pix_major, int& lpt, unsigned char (*perm)[256]) {
+    pix_major = igemm_pix_major(p);
+    lpt = pix_major && (p.B % BM) == 0;
+    if (lpt)
         for (int ci = 0; ci < p.nclasses; ++ci) {
             const IgemmClass& c = p.cls[ci];
-            int cnt[256];
-            for (int pix = 0; pix < c.R * c.C; ++pix) {
-                const int r = pix / c.C, cc = pix - r * c.C;
-                int ny = 0, nx = 0;
-                for (int ta = 0; ta < c.nty; ++ta) { const int iy = r * p.S + c.dy0 + ta * p.dstep; ny += (iy >= 0 && iy < p.Hin); }
-                for (int tb = 0; tb < c.ntx; ++tb) { const int ix = cc * p.S + c.dx0 + tb * p.dstep; nx += (ix >= 0 && ix < p.Win); }
-                cnt[pix] = ny * nx;
-                p.perm[ci][pix] = (unsigned char)pix;
-            }
-            for (int i = 1; i < c.R * c.C; ++i)       // insertion sort, descending tap count, stable
-                for (int j = i; j > 0 && cnt[p.perm[ci][j]] > cnt[p.perm[ci][j - 1]]; --j) {
-                    unsigned char t = p.perm[ci][j]; p.perm[ci][j] = p.perm[ci][j - 1]; p.perm[ci][j - 1] = t;
-                }
+            int cnt[256], at[258] = {};               // counting sort, descending tap count (<= 16 x 16 taps), stable
+            for (int pix = 0; pix < c.R * c.C; ++pix) ++at[256 - (cnt[pix] = igemm_valid_taps(p, c, pix)) + 1];
+            for (int v = 1; v < 258; ++v) at[v] += at[v - 1];
+            for (int pix = 0; pix < c.R * c.C; ++pix) perm[ci][at[256 - cnt[pix]]++] = (unsigned char)pix;
         }
 }
+void cgs_igemm_row_policy(IgemmParams& p, int BM) { igemm_row_policy(p, BM, p.pix_major, p.lpt, p.perm); }
 
 // multiply-accumulates a launch really issues -> cgs_last_executed_flops: the algorithmic count minus the zero-padding taps whose
 // K tiles the kernel skips (pixel-major tiles whose BM rows are one base pixel; exact, see igemm_kernel) -- for honest rooflines
-void cgs_igemm_count_flops(const IgemmParams& p, int BM) {
+static double igemm_executed_flops(const IgemmParams& p, bool pix_major, int BM) {
     double macs = 0.0;
     for (int ci = 0; ci < p.nclasses; ++ci) {
         const IgemmClass& c = p.cls[ci];
-        const long M = (long)p.B * c.R * c.C;
+        const long M = cgs_igemm_rows(p, ci);
         const int ntaps = c.nty * c.ntx;
-        if (!(p.vec && p.pix_major)) { macs += (double)M * p.N * p.Cred * ntaps; continue; }
+        if (!(p.vec && pix_major)) { macs += (double)M * p.N * p.Cred * ntaps; continue; }
+        if ((p.B % BM) == 0) {      // whole tiles: every tile lies inside one base pixel (the same sum, pixel by pixel instead of tile by tile)
+            for (int pix = 0; pix < c.R * c.C; ++pix) macs += (double)p.B * p.N * p.Cred * igemm_valid_taps(p, c, pix);
+            continue;
+        }
         for (long m0 = 0; m0 < M; m0 += BM) {
             const long ml = m0 + BM - 1 < M ? m0 + BM - 1 : M - 1;
             const int pf = (int)(m0 / p.B), pl = (int)(ml / p.B);
-            int taps = ntaps;
-            if (pf == pl) {
-                const int r = pf / c.C, cc = pf - r * c.C;
-                int ny = 0, nx = 0;
-                for (int ta = 0; ta < c.nty; ++ta) { const int iy = r * p.S + c.dy0 + ta * p.dstep; ny += (iy >= 0 && iy < p.Hin); }
-                for (int tb = 0; tb < c.ntx; ++tb) { const int ix = cc * p.S + c.dx0 + tb * p.dstep; nx += (ix >= 0 && ix < p.Win); }
-                taps = ny * nx;
-            }
-            macs += (double)(ml - m0 + 1) * p.N * p.Cred * taps;
+            macs += (double)(ml - m0 + 1) * p.N * p.Cred * (pf == pl ? igemm_valid_taps(p, c, pf) : ntaps);
         }
     }
-    cgs_add_flops(2.0 * macs);
+    return 2.0 * macs;
 }
+void cgs_igemm_count_flops(const IgemmParams& p, int BM) { cgs_add_flops(igemm_executed_flops(p, p.pix_major != 0, BM)); }
 
-int cgs_igemm_row_order(const IgemmParams& p) {
-    if (!igemm_pix_major(p)) return 0;
-    return (p.B % 128) == 0 ? 2 : 1;
-}
-
-int cgs_igemm_launch(const IgemmParams& p_in, void* slab, size_t slab_bytes, hipStream_t s) {
-    IgemmParams p = p_in;
-    p.splitk = 1; p.slab = nullptr;
-    p.tail_from = p.tail_n = p.tail_s = 0;
-    p.prio_t[0] = p.prio_t[1] = p.prio_t[2] = 0;
-    int maxRC = 0;
-    for (int i = 0; i < p.nclasses; ++i) maxRC = p.cls[i].R * p.cls[i].C > maxRC ? p.cls[i].R * p.cls[i].C : maxRC;
-    cgs_igemm_row_policy(p, 128);
-    if ((long)p.B * p.Hout * p.Wout * p.N * 4 > 0x7fffffffL || (long)p.B * p.Hin * p.Win * p.Cred * 4 > 0x7fffffffL)
-        return cgs_set_error(CGS_EINVAL, "igemm: a tensor of one launch exceeds 2 GiB (the caller splits the batch)");
-    if (p.stat_part && ((p.N & 3) || p.epilogue != CGS_EPI_NONE))
-        return cgs_set_error(CGS_EINVAL, "igemm: fused statistics need N %% 4 == 0 and no epilogue");
-    if (p.stat_part && p.ns_mean && (!p.ns_inv || !p.ns_gamma || !p.ns_beta || !p.ep_aux || p.ns_gimg < 0))
-        return cgs_set_error(CGS_EINVAL, "igemm: norm-backward statistics need x (ep_aux), mean, invstd, gamma and beta");
-    p.stat_cls_rows = 0;
-    if (p.stat_part) {        // one partial row per (128-row tile, wave row), the parity classes back to back (equal M: cgs_conv_stat_layout)
-        const long M0 = (long)p.B * p.cls[0].R * p.cls[0].C;
-        for (int i = 1; i < p.nclasses; ++i)
-            if ((long)p.B * p.cls[i].R * p.cls[i].C != M0) return cgs_set_error(CGS_EINVAL, "igemm: fused statistics need parity classes of equal size");
-        p.stat_cls_rows = (int)(2 * ((M0 + 127) / 128));
-    }
-    if (p.sign_out && !cgs_igemm_signs_ok(p))
-        return cgs_set_error(CGS_EINVAL, "igemm: a sign mask needs N %% 32 == 0, the relu / lrelu forward epilogues and a grid that is not split over K");
-    {   // split-K for under-filled grids, if the caller's workspace has room for the partial slabs
-        const size_t need = p.sign_out ? 0 : cgs_igemm_splitk_bytes(p);      // (a sign mask comes out of the one-pass epilogue; statistics: splitk_reduce_stats_kernel)
-        if (need && slab && slab_bytes >= need) {
-            p.splitk = choose_splitk(p); p.slab = (float*)slab;
-            size_t off = 0;
-            for (int i = 0; i < p.nclasses; ++i) {
-                p.cls[i].slab_off = (int)off;
-                off += (size_t)p.splitk * p.B * p.cls[i].R * p.cls[i].C * p.Np;
-            }
-        }
-    }
+// The planner: geometry, form and slab bytes on offer (0 = no slab) -> the plan.  It reads no pointer of p and makes no HIP call beside the
+// cached compute-unit count of igemm_round_rules_apply.  Steps: what the form needs of the geometry; row policy; split-K if its slabs fit;
+// tiles and tail split (asked again without the wide-for-tail rule when the slab has no room for that tail); the 256-row row policy of tall
+// tiles; executed FLOPs; prio_t; bin packing; uni; half; the kernel twin; the grid with its decode, the class flip, the reduce kernel.
+static IgemmPlan igemm_plan(const IgemmParams& p, IgemmForm form, size_t slab_bytes) {
+    IgemmPlan pl{};
+    pl.form = form;
+    pl.splitk = 1;
     const bool vec = p.vec != 0;
-    IgemmTiles tiles = igemm_choose_tiles(p);
-    IgemmTail tl = igemm_choose_tail(p, tiles);
-    bool tail_fits = tl.s > 1 && slab && slab_bytes >= igemm_tail_bytes(tl, tiles.wide);
-    if (tiles.wide_for_tail && !tail_fits) {         // wide tiles were chosen FOR the tail split and the caller's slab has no room for it: the narrow plan
-        tiles = igemm_choose_tiles(p, false);
-        tl = igemm_choose_tail(p, tiles);
-        tail_fits = tl.s > 1 && slab && slab_bytes >= igemm_tail_bytes(tl, tiles.wide);
+    const int maxRC = igemm_max_rc(p);
+    const int sk = choose_splitk(p);
+    if (form.stats && ((p.N & 3) || p.epilogue != CGS_EPI_NONE)) pl.refusal = "igemm: fused statistics need N % 4 == 0 and no epilogue";
+    else if (form.stats && cgs_igemm_stat_cls_rows(p) < 0) pl.refusal = "igemm: fused statistics need parity classes of equal size";
+    else if (form.signs && !((p.N % 32) == 0 && (p.epilogue == CGS_EPI_AFFINE_RELU || p.epilogue == CGS_EPI_LRELU) && sk <= 1))
+        pl.refusal = "igemm: a sign mask needs N % 32 == 0, the relu / lrelu forward epilogues and a grid that is not split over K";
+    if (pl.refusal) return pl;
+    igemm_row_policy(p, 128, pl.pix_major, pl.lpt, pl.perm);
+    if (form.stats) pl.stat_cls_rows = cgs_igemm_stat_cls_rows(p);
+    if (sk > 1 && !form.signs) {   // split-K for under-filled grids, if the caller's workspace has room for the partial slabs
+        size_t off = 0;            // (a sign mask comes out of the one-pass epilogue; statistics: splitk_reduce_stats_kernel)
+        for (int i = 0; i < p.nclasses; ++i) {
+            pl.slab_off[i] = (int)off;
+            off += (size_t)sk * cgs_igemm_rows(p, i) * p.Np;
+        }
+        if (off && slab_bytes >= off * sizeof(float)) { pl.splitk = sk; pl.slab_bytes = off * sizeof(float); }
     }
-    bool wide = tiles.wide, deep = tiles.deep;
-    const bool tall = tiles.tall;
-    if (tall) cgs_igemm_row_policy(p, 256);          // (whole 256-image tiles of one pixel: lpt needs B % 256 == 0)
-    cgs_igemm_count_flops(p, tall ? 256 : 128);
+    IgemmTiles tiles = igemm_choose_tiles(p, pl, true);
+    IgemmTail tl = igemm_choose_tail(p, pl, tiles);
+    bool tail_fits = tl.s > 1 && slab_bytes >= igemm_tail_bytes(tl, tiles.wide);
+    if (tiles.wide_for_tail && !tail_fits) {         // wide tiles were chosen FOR the tail split and the caller's slab has no room for it: the narrow plan
+        tiles = igemm_choose_tiles(p, pl, false);
+        tl = igemm_choose_tail(p, pl, tiles);
+        tail_fits = tl.s > 1 && slab_bytes >= igemm_tail_bytes(tl, tiles.wide);
+    }
+    const bool wide = tiles.wide, deep = tiles.deep, tall = tiles.tall;
+    if (tall) igemm_row_policy(p, 256, pl.pix_major, pl.lpt, pl.perm);          // (whole 256-image tiles of one pixel: lpt needs B % 256 == 0)
+    pl.flops = igemm_executed_flops(p, pl.pix_major != 0, tall ? 256 : 128);
     if (tail_fits) {   // tail split (see igemm_choose_tail), if the caller's workspace has room for the partial tiles
-        p.tail_from = tl.from; p.tail_n = tl.n; p.tail_s = tl.s; p.slab = (float*)slab;
-        cgs_note_tail(tl.n, tl.s);
+        pl.tail = tl;
+        pl.slab_bytes = igemm_tail_bytes(tl, wide);
     }
     {
         // Launches whose blocks are all resident at once (one "round": <= 4 blocks per CU with the 16-deep tiles, 2 with the
@@ -1490,62 +1384,217 @@ int cgs_igemm_launch(const IgemmParams& p_in, void* slab, size_t slab_bytes, hip
         // (block slots per CU: the one model the tail planner uses too, igemm_blocks_per_cu)
         const int bn_sel = wide ? 128 : 64, per_cu = vec ? igemm_blocks_per_cu(wide, deep) : 2;
         const long total_blocks = igemm_blocks(p, bn_sel);
-        const bool one_round = igemm_round_rules_apply() && vec && p.splitk == 1 && !tall && total_blocks <= (long)IGEMM_CUS * per_cu && total_blocks >= IGEMM_CUS;
+        const bool one_round = igemm_round_rules_apply() && vec && pl.splitk == 1 && !tall && total_blocks <= (long)IGEMM_CUS * per_cu && total_blocks >= IGEMM_CUS;
         // (a) measured per layer at batch 1024: +2..4 % on every pixel-major layer (one or two rounds of 128x128 / 128x64 blocks),
         // -3 % on the transposed 128x64 layers with their 8192 short blocks (a fresh block at priority 3 starves the ones about
         // to finish), neutral elsewhere -> pixel-major launches only
-        if (vec && !deep && p.splitk == 1 && p.pix_major && total_blocks >= 256) { p.prio_t[0] = 85; p.prio_t[1] = 170; p.prio_t[2] = 0; }
+        if (vec && !deep && pl.splitk == 1 && pl.pix_major && total_blocks >= 256) { pl.prio_t[0] = 85; pl.prio_t[1] = 170; pl.prio_t[2] = 0; }
         const int nblk_n = p.Np / bn_sel;
-        if (one_round && p.lpt && p.nclasses == 1 && p.B / 128 == 8 && (32 % nblk_n) == 0) {
+        if (one_round && pl.lpt && p.nclasses == 1 && p.B / 128 == 8 && (32 % nblk_n) == 0) {
             const IgemmClass& c = p.cls[0];
             const int RC = c.R * c.C, nbins = 32 / nblk_n, cap = (RC + nbins - 1) / nbins;
-            int cnt[256], load[32] = {}, used[32] = {};
+            int load[32] = {}, used[32] = {};
             unsigned char bin_items[32][256];
-            for (int pix = 0; pix < RC; ++pix) {
-                const int r = pix / c.C, cc = pix - r * c.C;
-                int ny = 0, nx = 0;
-                for (int ta = 0; ta < c.nty; ++ta) { const int iy = r * p.S + c.dy0 + ta * p.dstep; ny += (iy >= 0 && iy < p.Hin); }
-                for (int tb = 0; tb < c.ntx; ++tb) { const int ix = cc * p.S + c.dx0 + tb * p.dstep; nx += (ix >= 0 && ix < p.Win); }
-                cnt[pix] = ny * nx;
-            }
-            for (int i = 0; i < RC; ++i) {                       // p.perm[0] is sorted by descending tap count
-                const int pix = p.perm[0][i];
+            for (int i = 0; i < RC; ++i) {                       // pl.perm[0] is sorted by descending tap count
+                const int pix = pl.perm[0][i];
                 int best = -1;
                 for (int b = 0; b < nbins; ++b) {
                     const int slots = (RC - b + nbins - 1) / nbins;       // positions b, b + nbins, ... < RC
                     if (used[b] < slots && used[b] < cap && (best < 0 || load[b] < load[best])) best = b;
                 }
                 bin_items[best][used[best]++] = (unsigned char)pix;
-                load[best] += cnt[pix];
+                load[best] += igemm_valid_taps(p, c, pix);
             }
             for (int b = 0; b < nbins; ++b)
-                for (int k = 0; k < used[b]; ++k) p.perm[0][b + k * nbins] = bin_items[b][k];
+                for (int k = 0; k < used[b]; ++k) pl.perm[0][b + k * nbins] = bin_items[b][k];
         }
     }
-    p.uni = !(p.nclasses > 1 && wide && maxRC <= 64);
+    pl.uni = !(p.nclasses > 1 && wide && maxRC <= 64);
     // Launches of at most 64 GEMM rows that are split over K (the fully connected layers at the reference's batch size, nsgan/main.py:32: 64 x 6272 x 1024):
     // 64-row tiles -- a 128-row tile is half padding there and the blocks are matrix-bound (4-8 K tiles each on their own SIMDs).  Same-process
     // A/B (round 5, profiles/r05_t_bm64_ab.txt): mnist's 6272->1024 forward 34.6 -> 25.9 us, backward 32.5 -> 24.0 us, the batch-64 call 12.14 -> 11.38 ms.
-    bool half = vec && wide && deep && p.splitk > 1 && !p.tap_parity && (long)p.B * maxRC <= 64;
-    // (a launch that leaves the norm-backward sums runs the igemm_ns_kernel twin of its tile; every other launch the kernel of the rounds before)
-    const bool ns = p.stat_part && p.ns_mean;
+    const bool half = vec && wide && deep && pl.splitk > 1 && !p.tap_parity && (long)p.B * maxRC <= 64;
     // (the fused momentum update: the igemm_up_kernel twin of the four VEC tiles -- a split-K launch leaves raw slabs from the plain kernel and
-    // updates in splitk_reduce_kernel<true>; what cgs_igemm_update_form said for this geometry must be what was planned here)
-    if (p.up_mom) {
-        const int form = p.splitk > 1 ? CGS_UPDATE_SPLITK : (p.tail_s > 1 ? CGS_UPDATE_TAIL : CGS_UPDATE_EPILOGUE);
-        if (!vec || tall || cgs_igemm_update_form(p_in, slab ? slab_bytes : 0) != form)
-            return cgs_set_error(CGS_EINVAL, "igemm: the fused update is not offered for this launch (cgs_conv_update_form)");
+    // updates in splitk_reduce_kernel<true>; no twin is instantiated for the generic-K gather or the tall 256 x 64 tile)
+    if (form.update) {
+        if (!vec || tall || (p.N & 3) || p.epilogue != CGS_EPI_NONE || form.stats || form.signs) {
+            pl.refusal = "igemm: the fused update is not offered for this launch (cgs_conv_update_form)";
+            return pl;
+        }
+        pl.update = pl.splitk > 1 ? CGS_UPDATE_SPLITK : (pl.tail.s > 1 ? CGS_UPDATE_TAIL : CGS_UPDATE_EPILOGUE);
     }
-    const bool upk = p.up_mom && p.splitk == 1;
-#define LC(...) (ns ? launch_cfg<__VA_ARGS__, 1>(p, s) : launch_cfg<__VA_ARGS__, 0>(p, s))
-#define LCU(...) (upk ? launch_cfg<__VA_ARGS__, 2>(p, s) : LC(__VA_ARGS__))
-    if (half) return LC(64, 128, 4, true, 32, false);
-    if (tall) return p.tap_parity ? LC(256, 64, 4, true, 16, true) : LC(256, 64, 4, true, 16, false);
-    if (vec && !deep && !p.tap_parity) return wide ? LCU(128, 128, 4, true, 16, false) : LCU(128, 64, 4, true, 16, false);
-    if (vec && !deep && p.tap_parity) return wide ? LCU(128, 128, 4, true, 16, true) : LCU(128, 64, 4, true, 16, true);
-    if (vec && p.tap_parity) return wide ? LCU(128, 128, 4, true, 32, true) : LCU(128, 64, 4, true, 32, true);
-    if (vec) return wide ? LCU(128, 128, 4, true, 32, false) : LCU(128, 64, 4, true, 32, false);
-    return wide ? LC(128, 128, 4, false, 16, false) : LC(128, 64, 4, false, 16, false);
-#undef LCU
-#undef LC
+    // (a launch that leaves the norm-backward sums runs the igemm_ns_kernel twin of its tile; every other launch the kernel of the rounds before)
+    pl.twin = pl.update && pl.splitk == 1 ? 2 : (form.ns ? 1 : 0);
+    pl.vec = vec;
+    pl.par = vec && p.tap_parity;
+    pl.BM = half ? 64 : (tall ? 256 : 128);
+    pl.BN = wide ? 128 : 64;
+    pl.TBK = (vec && deep) ? 32 : 16;
+    // the grid: the tail tiles are the LAST ids of the last class and are replaced by tail.s ids each
+    long maxM = 0;
+    for (int i = 0; i < p.nclasses; ++i) maxM = cgs_igemm_rows(p, i) > maxM ? cgs_igemm_rows(p, i) : maxM;
+    if (maxM == 0) return pl;
+    pl.gx_tiles = cgs_igemm_grid_x((maxM + pl.BM - 1) / pl.BM, p.Np / pl.BN, &pl.xcd_map);
+    pl.gx = pl.gx_tiles + (pl.tail.s > 1 ? (long)pl.tail.n * (pl.tail.s - 1) : 0);
+    // (image-major launches of two rounds only: measured per stage at 64 / 128 / 256 images, profiles/r05_ai_class_flip_ab.txt -- dcgan64 at batch 64: 102.5 -> 89.0,
+    // 95.2 -> 82.4, 89.9 -> 77.5 us; the pixel-major launches of 128- and 256-image batches, whose tiles differ by pixel as well, lose up to 14 % with it)
+    {
+        // (the flip decides per CLASS range of gx blocks which round it lies in: those ranges must not straddle a round -- gx divides 256 --
+        // and a group of classes that is reversed must lie inside one round)
+        const long total = pl.gx * (long)p.nclasses * pl.splitk;
+        if (igemm_round_rules_apply() && p.nclasses > 1 && !pl.pix_major && total > 256 && total <= 512 && (256 % pl.gx) == 0 && pl.tail.s <= 1) {
+            const long per_round = 256 / pl.gx;                       // class ranges per round of 256 blocks
+            if (pl.splitk > 1 && (per_round % p.nclasses) == 0) pl.cls_flip = p.nclasses;                 // whole K slices per round: reverse all classes
+            else if (pl.splitk == 1 && per_round < p.nclasses && (p.nclasses % per_round) == 0) pl.cls_flip = (int)per_round;      // several rounds per slice
+        }
+    }
+    if (pl.tail.s > 1) {
+        pl.reduce = form.update ? CGS_REDUCE_TAIL_UPDATE : CGS_REDUCE_TAIL;
+        pl.reduce_grid[0] = (unsigned)pl.tail.n; pl.reduce_grid[1] = TAIL_RSPLIT; pl.reduce_grid[2] = 1;
+    }
+    if (pl.splitk > 1) {
+        long tot = 0;
+        for (int i = 0; i < p.nclasses; ++i) { long t = cgs_igemm_rows(p, i) * (p.Np / 4); if (t > tot) tot = t; }
+        const unsigned rb = (unsigned)((tot + 63) / 64 > 4096 ? 4096 : (tot + 63) / 64);       // 64 output quads per 256-thread block
+        pl.reduce = form.stats ? CGS_REDUCE_SPLITK_STATS : (form.update ? CGS_REDUCE_SPLITK_UPDATE : CGS_REDUCE_SPLITK);
+        pl.reduce_grid[0] = form.stats ? (unsigned)pl.stat_cls_rows : rb;
+        pl.reduce_grid[1] = form.stats ? (unsigned)((p.N + 31) / 32) : (unsigned)p.nclasses;
+        pl.reduce_grid[2] = form.stats ? (unsigned)p.nclasses : 1;
+    }
+    return pl;
+}
+
+// ---- the host queries: each reads the plan ----
+static const IgemmForm FORM_OF[] = {/* CGS_FORM_PLAIN */ {false, false, false, false}, /* _STATS */ {true, false, false, false},
+                                    /* _NSTATS */ {true, true, false, false}, /* _SIGNS */ {false, false, true, false},
+                                    /* _UPDATE */ {false, false, false, true}};
+static const size_t ANY_SLAB = ~(size_t)0;
+
+size_t cgs_igemm_splitk_bytes(const IgemmParams& p) {
+    const IgemmPlan pl = igemm_plan(p, FORM_OF[CGS_FORM_PLAIN], ANY_SLAB);
+    return pl.splitk > 1 ? pl.slab_bytes : 0;
+}
+
+// slab bytes behind the packed weights a launch of this geometry can use: split-K slabs (under-filled grids) or tail-split partial tiles
+size_t cgs_igemm_slab_bytes(const IgemmParams& p) { return igemm_plan(p, FORM_OF[CGS_FORM_PLAIN], ANY_SLAB).slab_bytes; }
+
+int cgs_igemm_signs_ok(const IgemmParams& p) { return !igemm_plan(p, FORM_OF[CGS_FORM_SIGNS], 0).refusal; }
+
+// The fused momentum update (IgemmParams::up_*): where would a launch of this geometry, with slab_bytes of workspace behind its packed
+// weights, apply it -- the launch's own plan, so the answer given before a capture is the launch's.  0 = not offered: the generic-K gather
+// (Cred % 32 != 0), N % 4 != 0, an epilogue, the tall 256 x 64 tile (no twin is instantiated for it).
+int cgs_igemm_update_form(const IgemmParams& p, size_t slab_bytes) { return igemm_plan(p, FORM_OF[CGS_FORM_UPDATE], slab_bytes).update; }
+
+static int igemm_row_order(const IgemmPlan& pl) { return !pl.pix_major ? 0 : (pl.lpt ? 2 : 1); }
+int cgs_igemm_row_order(const IgemmParams& p) { return igemm_row_order(igemm_plan(p, FORM_OF[CGS_FORM_PLAIN], 0)); }
+
+// the kernel that follows a launch whose tail tiles or whose whole grid left raw partial sums
+static int igemm_launch_reduce(const IgemmPlan& pl, const IgemmParams& q, hipStream_t s) {
+    const dim3 rg(pl.reduce_grid[0], pl.reduce_grid[1], pl.reduce_grid[2]);
+    switch (pl.reduce) {
+        case CGS_REDUCE_TAIL_UPDATE: hipLaunchKernelGGL(tail_reduce_kernel<true>, rg, dim3(256), 0, s, q, pl.BM, pl.BN); break;
+        case CGS_REDUCE_TAIL: hipLaunchKernelGGL(tail_reduce_kernel<false>, rg, dim3(256), 0, s, q, pl.BM, pl.BN); break;
+        case CGS_REDUCE_SPLITK_UPDATE: hipLaunchKernelGGL(splitk_reduce_kernel<true>, rg, dim3(256), 0, s, q); break;
+        case CGS_REDUCE_SPLITK: hipLaunchKernelGGL(splitk_reduce_kernel<false>, rg, dim3(256), 0, s, q); break;
+        case CGS_REDUCE_SPLITK_STATS: hipLaunchKernelGGL(splitk_reduce_stats_kernel, rg, dim3(256), 0, s, q); break;
+        default: return CGS_OK;
+    }
+    CGS_CHECK_LAUNCH(pl.tail.s > 1 ? "tail_reduce" : "splitk_reduce");
+    return CGS_OK;
+}
+
+// What of a launch needs template parameters: the kernel, its LDS bytes, the name rocprofv3 prints for it and its shared-memory attribute.
+// One row per instantiation: the 13 tiles of igemm_kernel and igemm_ns_kernel, the 8 of igemm_up_kernel (none for the 64- and 256-row tiles).
+struct IgemmInst {
+    int BM, BN, TBK, twin;
+    bool vec, par;
+    void (*kern)(IgemmParams);
+    size_t smem;
+    const char* name;
+    int (*smem_attr)();
+};
+static constexpr size_t igemm_smem_bytes(int BM, int BN, int NW, bool VEC, int TBK) {
+    const int EH = (VEC && TBK == 16) ? 2 : 1, WM = BM / 64;
+    const size_t kloop_f = (size_t)2 * BM * (TBK + 4) + 2 * TBK * BN, stage_f = (size_t)NW * (BM / WM / EH) * (BN / (NW / WM) + 4);
+    return (kloop_f > stage_f ? kloop_f : stage_f) * sizeof(float) + BM * sizeof(int);
+}
+template <void (*KERN)(IgemmParams), size_t SMEM>
+static int igemm_smem_attr() {
+    CGS_SMEM_ATTR(SMEM, "igemm", KERN);
+    return CGS_OK;
+}
+#define IGEMM_INST(K, TW, BM, BN, VEC, TBK, PAR)                                                                                      \
+    {BM, BN, TBK, TW, VEC, PAR, K<BM, BN, 4, VEC, TBK, PAR>, igemm_smem_bytes(BM, BN, 4, VEC, TBK),                                    \
+     #K "<" #BM ", " #BN ", 4, " #VEC ", " #TBK ", " #PAR ">", igemm_smem_attr<K<BM, BN, 4, VEC, TBK, PAR>, igemm_smem_bytes(BM, BN, 4, VEC, TBK)>}
+#define IGEMM_TILE(...) IGEMM_INST(igemm_ns_kernel, 1, __VA_ARGS__), IGEMM_INST(igemm_kernel, 0, __VA_ARGS__)
+#define IGEMM_TILE_UP(...) IGEMM_INST(igemm_up_kernel, 2, __VA_ARGS__), IGEMM_TILE(__VA_ARGS__)
+static const IgemmInst IGEMM_INSTS[] = {
+    IGEMM_TILE(64, 128, true, 32, false),      IGEMM_TILE(256, 64, true, 16, true),       IGEMM_TILE(256, 64, true, 16, false),
+    IGEMM_TILE_UP(128, 128, true, 16, false),  IGEMM_TILE_UP(128, 64, true, 16, false),   IGEMM_TILE_UP(128, 128, true, 16, true),
+    IGEMM_TILE_UP(128, 64, true, 16, true),    IGEMM_TILE_UP(128, 128, true, 32, true),   IGEMM_TILE_UP(128, 64, true, 32, true),
+    IGEMM_TILE_UP(128, 128, true, 32, false),  IGEMM_TILE_UP(128, 64, true, 32, false),   IGEMM_TILE(128, 128, false, 16, false),
+    IGEMM_TILE(128, 64, false, 16, false)};
+#undef IGEMM_TILE_UP
+#undef IGEMM_TILE
+#undef IGEMM_INST
+static_assert(sizeof(IGEMM_INSTS) / sizeof(IGEMM_INSTS[0]) == 34, "13 igemm_kernel, 13 igemm_ns_kernel, 8 igemm_up_kernel");
+
+static const IgemmInst* igemm_inst_of(const IgemmPlan& pl) {
+    for (const IgemmInst& k : IGEMM_INSTS)
+        if (k.BM == pl.BM && k.BN == pl.BN && k.TBK == pl.TBK && k.twin == pl.twin && k.vec == pl.vec && k.par == pl.par) return &k;
+    return nullptr;
+}
+
+// cgs_conv_igemm_plan (cgs_hip.h) behind the family and batch checks of api.hip: 0 = the launcher would refuse the form
+int cgs_igemm_plan_info_of(const IgemmParams& p, int form, size_t slab_bytes, cgs_igemm_plan_info* info, unsigned char* perm) {
+    const IgemmPlan pl = igemm_plan(p, FORM_OF[form], slab_bytes);
+    const IgemmInst* k = pl.refusal ? nullptr : igemm_inst_of(pl);
+    if (!k) return 0;
+    info->kernel = k->name;
+    info->reduce = pl.reduce;
+    info->tail_tiles = pl.tail.s > 1 ? pl.tail.n : 0; info->tail_split = pl.tail.s > 1 ? pl.tail.s : 0;
+    info->plan[0] = pl.xcd_map; info->plan[1] = pl.cls_flip; info->plan[2] = pl.uni; info->plan[3] = (int)pl.gx; info->plan[4] = pl.splitk;
+    for (int i = 0; i < 3; ++i) info->prio_t[i] = pl.prio_t[i];
+    info->row_order = igemm_row_order(pl);
+    info->executed_flops = pl.flops;
+    for (int i = 0; i < CGS_MAX_CLASSES; ++i) {
+        info->perm_len[i] = (pl.lpt && i < p.nclasses) ? p.cls[i].R * p.cls[i].C : 0;
+        if (perm) memcpy(perm + 256 * i, pl.perm[i], (size_t)info->perm_len[i]);
+    }
+    return 1;
+}
+
+// validate, plan, apply, launch
+int cgs_igemm_launch(const IgemmParams& p_in, void* slab, size_t slab_bytes, hipStream_t s) {
+    if (cgs_igemm_over_2gib(p_in)) return cgs_set_error(CGS_EINVAL, "igemm: a tensor of one launch exceeds 2 GiB (the caller splits the batch)");
+    if (p_in.stat_part && p_in.ns_mean && (!p_in.ns_inv || !p_in.ns_gamma || !p_in.ns_beta || !p_in.ep_aux || p_in.ns_gimg < 0))
+        return cgs_set_error(CGS_EINVAL, "igemm: norm-backward statistics need x (ep_aux), mean, invstd, gamma and beta");
+    const IgemmForm form{p_in.stat_part != nullptr, p_in.stat_part && p_in.ns_mean, p_in.sign_out != nullptr, p_in.up_mom != nullptr};
+    const IgemmPlan pl = igemm_plan(p_in, form, slab ? slab_bytes : 0);
+    cgs_add_flops(pl.flops);
+    if (pl.tail.s > 1) cgs_note_tail(pl.tail.n, pl.tail.s);
+    if (pl.refusal) return cgs_set_error(CGS_EINVAL, "%s", pl.refusal);
+    if (form.update && p_in.bias) return cgs_set_error(CGS_EINVAL, "igemm: the fused update is not offered for this launch (cgs_conv_update_form)");
+    const IgemmInst* k = igemm_inst_of(pl);
+    if (!k) return cgs_set_error(CGS_EINVAL, "igemm: no kernel for the planned tile %d x %d x %d", pl.BM, pl.BN, pl.TBK);
+    int rc = k->smem_attr();
+    if (rc) return rc;
+    if (pl.gx == 0) return CGS_OK;
+    if (pl.gx > 0x7fffffffL) return cgs_set_error(CGS_EINVAL, "igemm: grid too large");
+    IgemmParams q = p_in;
+    q.splitk = pl.splitk;
+    q.slab = pl.slab_bytes ? (float*)slab : nullptr;
+    for (int i = 0; i < q.nclasses && pl.splitk > 1; ++i) q.cls[i].slab_off = pl.slab_off[i];
+    q.tail_from = pl.tail.s > 1 ? (int)(pl.gx_tiles - pl.tail.n) : 0; q.tail_n = pl.tail.n; q.tail_s = pl.tail.s;
+    q.pix_major = pl.pix_major; q.lpt = pl.lpt;
+    if (pl.lpt) memcpy(q.perm, pl.perm, sizeof(q.perm[0]) * q.nclasses);
+    q.stat_cls_rows = pl.stat_cls_rows;
+    q.xcd_map = pl.xcd_map; q.cls_flip = pl.cls_flip; q.uni = pl.uni;
+    for (int i = 0; i < 3; ++i) q.prio_t[i] = pl.prio_t[i];
+    hipLaunchKernelGGL(k->kern, dim3((unsigned)pl.gx, (unsigned)q.nclasses, pl.splitk), dim3(256), k->smem, s, q);
+    CGS_CHECK_LAUNCH("igemm");
+    if ((rc = igemm_launch_reduce(pl, q, s))) return rc;
+    cgs_note_kernel(k->name);
+    cgs_note_igemm_plan(pl.xcd_map, pl.cls_flip, pl.uni, (int)pl.gx, pl.splitk);
+    return CGS_OK;
 }

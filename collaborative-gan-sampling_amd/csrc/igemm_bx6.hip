@@ -514,28 +514,21 @@ int cgs_igemm_bx6_ok(const CgsLayer& L, bool dirT, int B, bool any_size) {
     return blocks >= 256 && K >= 512;
 }
 
+// (name: what rocprofv3 prints for the instantiation)
 template <int BM, int BN, bool PAR>
-static int launch_bx6(const IgemmParams& p, hipStream_t s) {
+static int launch_bx6(const IgemmParams& p, hipStream_t s, const char* name) {
     constexpr int NT = BM * BN / 128;
     constexpr size_t buf = (NT == 64 ? 1 : 2) * 3 * (size_t)(BM + BN) * 32, stage = (size_t)(NT / 64) * 32 * 68 * 4;
     constexpr size_t smem = (buf > stage ? buf : stage) + BM * sizeof(int);
     CGS_SMEM_ATTR(smem, "igemm_bx6", igemm_bx6_kernel<BM, BN, PAR>);
     long maxM = 0;
-    for (int i = 0; i < p.nclasses; ++i) {
-        const long m = (long)p.B * p.cls[i].R * p.cls[i].C;
-        if (m > maxM) maxM = m;
-    }
+    for (int i = 0; i < p.nclasses; ++i) maxM = cgs_igemm_rows(p, i) > maxM ? cgs_igemm_rows(p, i) : maxM;
     if (maxM == 0) return CGS_OK;
-    const long mtiles = (maxM + BM - 1) / BM;
     IgemmParams q = p;
-    q.xcd_map = (mtiles % 8 == 0 || mtiles >= 64) ? 1 : 0;
-    long gx = (q.xcd_map ? (mtiles + 7) / 8 * 8 : mtiles) * (p.Np / BN);
-    unsigned gy = (unsigned)p.nclasses;
+    const long gx = cgs_igemm_grid_x((maxM + BM - 1) / BM, p.Np / BN, &q.xcd_map);
     if (gx > 0x7fffffffL) return cgs_set_error(CGS_EINVAL, "igemm_bx6: grid too large");
-    hipLaunchKernelGGL((igemm_bx6_kernel<BM, BN, PAR>), dim3((unsigned)gx, gy, 1), dim3(NT), smem, s, q);
+    hipLaunchKernelGGL((igemm_bx6_kernel<BM, BN, PAR>), dim3((unsigned)gx, (unsigned)p.nclasses, 1), dim3(NT), smem, s, q);
     CGS_CHECK_LAUNCH("igemm_bx6");
-    static thread_local char name[64];
-    snprintf(name, sizeof(name), "igemm_bx6_kernel<%d, %d, %s>", BM, BN, PAR ? "true" : "false");
     cgs_note_kernel(name);
     return CGS_OK;
 }
@@ -551,18 +544,15 @@ int cgs_igemm_bx6_launch(const IgemmParams& p_in, hipStream_t s) {
     const bool n256 = (p.N % 256) == 0;
     const int BM = (n256 || (p.N % 128) != 0) ? 128 : 256;
     cgs_igemm_row_policy(p, BM);
-    if ((long)p.B * p.Hout * p.Wout * p.N * 4 > 0x7fffffffL || (long)p.B * p.Hin * p.Win * p.Cred * 4 > 0x7fffffffL)
-        return cgs_set_error(CGS_EINVAL, "igemm_bx6: a tensor of one launch exceeds 2 GiB (the caller splits the batch)");
+    if (cgs_igemm_over_2gib(p)) return cgs_set_error(CGS_EINVAL, "igemm_bx6: a tensor of one launch exceeds 2 GiB (the caller splits the batch)");
     if (p.stat_part && p.epilogue != CGS_EPI_NONE) return cgs_set_error(CGS_EINVAL, "igemm_bx6: fused statistics need no epilogue");
-    p.stat_cls_rows = 0;
-    if (p.stat_part) {
-        const long M0 = (long)p.B * p.cls[0].R * p.cls[0].C;
-        for (int i = 1; i < p.nclasses; ++i)
-            if ((long)p.B * p.cls[i].R * p.cls[i].C != M0) return cgs_set_error(CGS_EINVAL, "igemm_bx6: fused statistics need parity classes of equal size");
-        p.stat_cls_rows = (int)(2 * ((M0 + 127) / 128));
-    }
+    p.stat_cls_rows = p.stat_part ? cgs_igemm_stat_cls_rows(p) : 0;
+    if (p.stat_cls_rows < 0) return cgs_set_error(CGS_EINVAL, "igemm_bx6: fused statistics need parity classes of equal size");
     cgs_igemm_count_flops(p, BM);
-    if (n256) return p.tap_parity ? launch_bx6<128, 256, true>(p, s) : launch_bx6<128, 256, false>(p, s);
-    if ((p.N % 128) == 0) return p.tap_parity ? launch_bx6<256, 128, true>(p, s) : launch_bx6<256, 128, false>(p, s);
-    return p.tap_parity ? launch_bx6<128, 64, true>(p, s) : launch_bx6<128, 64, false>(p, s);
+#define BX6(BM, BN) (p.tap_parity ? launch_bx6<BM, BN, true>(p, s, "igemm_bx6_kernel<" #BM ", " #BN ", true>") \
+                                  : launch_bx6<BM, BN, false>(p, s, "igemm_bx6_kernel<" #BM ", " #BN ", false>"))
+    if (n256) return BX6(128, 256);
+    if ((p.N % 128) == 0) return BX6(256, 128);
+    return BX6(128, 64);
+#undef BX6
 }

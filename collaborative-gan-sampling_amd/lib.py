@@ -25,6 +25,16 @@ class LadamSeed(C.Structure):
     _fields_ = [("s_real", C.c_void_p), ("loss_avg", C.c_void_p), ("gain", C.c_void_p), ("first", C.c_int)]
 
 
+class IgemmPlanInfo(C.Structure):
+    """cgs_igemm_plan_info of include/cgs_hip.h: what cgs_conv_igemm_plan says about an implicit-GEMM launch before it is made."""
+    _fields_ = [("kernel", C.c_char_p), ("reduce", C.c_int), ("tail_tiles", C.c_int), ("tail_split", C.c_int), ("plan", C.c_int * 5),
+                ("prio_t", C.c_int * 3), ("row_order", C.c_int), ("perm_len", C.c_int * 4), ("executed_flops", C.c_double)]
+
+
+FORM_PLAIN, FORM_STATS, FORM_NSTATS, FORM_SIGNS, FORM_UPDATE = 0, 1, 2, 3, 4
+REDUCE_KERNELS = ("none", "tail_reduce_kernel<false>", "tail_reduce_kernel<true>", "splitk_reduce_kernel<false>", "splitk_reduce_kernel<true>",
+                  "splitk_reduce_stats_kernel")          # by CGS_REDUCE_*
+
 _p, _i, _f, _z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _ll = C.c_longlong
 
@@ -38,6 +48,7 @@ SIGNATURES = {
     "cgs_last_tail_tiles": (_i, []),
     "cgs_last_tail_split": (_i, []),
     "cgs_last_igemm_plan": (None, [C.POINTER(C.c_int)]),
+    "cgs_conv_igemm_plan": (_i, [_i] * 14 + [_z, C.POINTER(IgemmPlanInfo), _p]),
     "cgs_set_contraction": (_i, [_i]),
     "cgs_get_contraction": (_i, []),
     "cgs_conv_ws_bytes": (_z, [_i] * 7),
@@ -245,6 +256,19 @@ def last_igemm_plan():
     out = (C.c_int * 5)()
     load().cgs_last_igemm_plan(out)
     return tuple(out)
+
+
+def conv_igemm_plan(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, form, ws_bytes):
+    """The plan of an implicit-GEMM launch before it is made (cgs_conv_igemm_plan; host only): None where the call would not run the
+    exact-fp32 implicit GEMM in one launch or would refuse the form, else a dict: kernel, reduce (a name of REDUCE_KERNELS), tail
+    (tiles, split), plan (the tuple of last_igemm_plan), prio_t, row_order, flops and perm (four lists, per parity class the base pixels in
+    visiting order; None in natural order)."""
+    info, perm = IgemmPlanInfo(), (C.c_ubyte * 1024)()
+    if not load().cgs_conv_igemm_plan(op, B, H, W, Cin, Ho, Wo, Cout, kh, kw, sh, sw, epilogue, form, ws_bytes, C.byref(info), perm):
+        return None
+    perms = [list(perm[256 * c:256 * c + n]) for c, n in enumerate(info.perm_len)] if any(info.perm_len) else None
+    return {"kernel": info.kernel.decode(), "reduce": REDUCE_KERNELS[info.reduce], "tail": (info.tail_tiles, info.tail_split),
+            "plan": tuple(info.plan), "prio_t": tuple(info.prio_t), "row_order": info.row_order, "flops": info.executed_flops, "perm": perms}
 
 
 def conv_ws_bytes(op, kh, kw, sh, sw, cin, cout):

@@ -104,6 +104,37 @@ int cgs_last_tail_split(void);
  * out[2] = uniform-tile K loop allowed, out[3] = grid x (block ids per class and K slice), out[4] = split-K factor (1 = none).
  * Scheduling details of csrc/igemm.hip: results do not depend on them. */
 void cgs_last_igemm_plan(int out[5]);
+/* The same plan BEFORE the launch, and the rest of it (host only: needs no device, launches nothing; for tests and profiling).
+ * Arguments as cgs_conv_family's; form = what the entry point adds to the plain call (CGS_FORM_*: the *_fwd_stats, *_bwd_data_nstats,
+ * *_fwd_signs and *_bwd_data_update entry points); ws_bytes = the call's whole workspace.  Returns 0 where the call would not run the
+ * exact-fp32 implicit GEMM (CGS_FAMILY_IGEMM) in ONE launch or where that launch would refuse the form, otherwise 1 and *info: the
+ * instantiation as cgs_last_kernel will name it (a constant string), the reduce kernel that follows it, what cgs_last_tail_tiles / _split,
+ * cgs_last_igemm_plan and cgs_last_executed_flops will say, the priority thresholds, the GEMM row order (as cgs_conv_update_form's) and,
+ * per parity class c, perm_len[c] base pixels in the order the m-tiles visit them, written to perm[256 * c ...] (perm: 1024 bytes or NULL;
+ * perm_len 0 = natural order).  Without a device the round rules apply as on the MI355X's 256 compute units (cgs_conv_ws_bytes_for too). */
+#define CGS_FORM_PLAIN 0
+#define CGS_FORM_STATS 1
+#define CGS_FORM_NSTATS 2
+#define CGS_FORM_SIGNS 3
+#define CGS_FORM_UPDATE 4
+#define CGS_REDUCE_NONE 0
+#define CGS_REDUCE_TAIL 1            /* tail_reduce_kernel<false>   */
+#define CGS_REDUCE_TAIL_UPDATE 2     /* tail_reduce_kernel<true>    */
+#define CGS_REDUCE_SPLITK 3          /* splitk_reduce_kernel<false> */
+#define CGS_REDUCE_SPLITK_UPDATE 4   /* splitk_reduce_kernel<true>  */
+#define CGS_REDUCE_SPLITK_STATS 5    /* splitk_reduce_stats_kernel  */
+typedef struct cgs_igemm_plan_info {
+    const char* kernel;
+    int reduce;
+    int tail_tiles, tail_split;
+    int plan[5];
+    int prio_t[3];
+    int row_order;
+    int perm_len[4];
+    double executed_flops;
+} cgs_igemm_plan_info;
+int cgs_conv_igemm_plan(int op, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int sh, int sw,
+                        int epilogue, int form, size_t ws_bytes, cgs_igemm_plan_info* info, unsigned char* perm);
 
 /* Contraction arithmetic of the implicit-GEMM layers, per calling THREAD (default CGS_CONTRACTION_F32; no process-wide state).
  * F32: v_mfma_f32_32x32x2_f32 -- exact fp32 products, an fp32 fma chain over K: what tf.nn.conv2d / conv2d_transpose / matmul

@@ -4,7 +4,8 @@ host-only queries, the table's coverage, the executed-FLOP count and the referen
 the launches to them).  Not a test module and not a conftest: the tests import it by name.  Exact-fp32 contraction only.
 
     geometry   conv_call_of (csrc/api.hip), cgs_geom_F / cgs_geom_T: the parity classes in their sorted order, vec, tap_parity, Np
-    plan       cgs_igemm_launch and launch_cfg in their own order: row policy, split-K (time model and slab test), tiles (with the second
+    plan       igemm_plan (what cgs_igemm_launch applies and the host queries read; plan()'s "launch_cfg" is its grid step) in its own
+               order: row policy, split-K (time model and slab test), tiles (with the second
                ask without tail_wide), tail split, half / tall (and its second row policy), bin packing, prio_t, uni, xcd_map, gx,
                cls_flip -> Plan: the exact kernel name, the reduce kernel that follows, the executed FLOP count, every plan feature
     brute_flops   the executed count again, by looping over every tile, row and tap
@@ -316,7 +317,7 @@ Plan = collections.namedtuple(
 
 
 def plan(g, slab, form="plain", epilogue=EPI_NONE, cus=256):
-    """cgs_igemm_launch + launch_cfg for a launch of geometry ``g`` with ``slab`` bytes of workspace behind its packed weights.
+    """igemm_plan for a launch of geometry ``g`` with ``slab`` bytes of workspace behind its packed weights.
     ``form`` sets stat_part (stats, nstats), the norm-backward twin (nstats), sign_out (signs), up_mom (update) as the entry points do.
     ``refused``: the launcher returns an error instead (a form the call does not offer)."""
     assert form in FORMS

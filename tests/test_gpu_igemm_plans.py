@@ -1,7 +1,9 @@
-"""The implicit-GEMM launch plans one by one (csrc/igemm.hip: cgs_igemm_launch, launch_cfg, the three reduce kernels and the _ns / _up
+"""The implicit-GEMM launch plans one by one (csrc/igemm.hip: igemm_plan, cgs_igemm_launch, the three reduce kernels and the _ns / _up
 twins): one test per row of tests/igemm_cases.py's table.  Each row runs its call through cgs_amd.kernels at the workspace the row names
 ("full": what the workspace cache hands the call; "none": the fp32 packed weights alone, no slab) and asserts, in this order,
 
+    the query    what cgs_conv_igemm_plan said about the call and workspace before the launch (kernel, tail, plan note, executed FLOPs)
+                 is what the launch noted
     the plan     cgs_last_kernel() is the predicted instantiation, exactly; cgs_last_tail_tiles() / cgs_last_tail_split(),
                  cgs_last_igemm_plan() (xcd_map, cls_flip, uni, gx, split-K factor) and cgs_last_executed_flops() equal the restated
                  planner's answer -- so a plan change that sends the row elsewhere fails here by name instead of testing another plan
@@ -108,9 +110,16 @@ def test_launch_plan(case, monkeypatch):
                         float(lib.cgs_last_executed_flops()))
         return left
 
+    # what the library says about this call and workspace BEFORE the launch (cgs_conv_igemm_plan, host only) ...
+    said = L.conv_igemm_plan(c.op, c.B, c.H, c.W, c.Cin, Ho if c.op in (TF, TB) else 0, Wo if c.op in (TF, TB) else 0, c.Cout, c.k, c.k, c.s, c.s,
+                             c.epilogue, {"plain": L.FORM_PLAIN, "stats": L.FORM_STATS, "nstats": L.FORM_NSTATS, "signs": L.FORM_SIGNS,
+                                          "update": L.FORM_UPDATE}[c.form], IC.ws_bytes(lib, c))
+    assert said is not None
     got = run()
     name, tiles, split, (xcd, flip, uni, gx, sk), flops = got["plan"]
     what = IC.case_id(c)
+    # ... is what the launch noted
+    assert (said["kernel"], *said["tail"], said["plan"], said["flops"]) == got["plan"], (said, got["plan"])
     print(f"\n{what}: {name} tail {tiles} x {split}, xcd_map {xcd} cls_flip {flip} uni {uni} gx {gx} split-K {sk}, {flops:.0f} flops, then {pred.reduce}")
     assert name == pred.kernel, (name, pred.kernel)
     assert (tiles, split) == (pred.tail_n, pred.tail_s if pred.tail_s > 1 else 0), (tiles, split, pred.tail_n, pred.tail_s)

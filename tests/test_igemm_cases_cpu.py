@@ -1,7 +1,12 @@
 """tests/igemm_cases.py without a device: the restated planner against the library's host-only queries (on the table and on a sweep of a few
 thousand geometries around it), the table's coverage of the plan features, the executed-FLOP count by brute force, the size budget of
 the float64 references, and the float32 oracle's own distance from the float64 reference (the reference side of the bar).  Without a
-device the library's round rules are on, so the restatement is compared at cus = 256.  Run with -s for the figures and the coverage list."""
+device the library's round rules are on, so the restatement is compared at cus = 256.  Run with -s for the figures and the coverage list.
+
+cgs_conv_igemm_plan returns the library's whole plan of a call without launching it; on every table row and on every sweep call, in every
+form its entry points offer and at the sweep's three workspaces, it is compared with plan() field by field: the kernel name, the reduce
+kernel, the tail, xcd_map, cls_flip, uni, gx, the split-K factor, prio_t, the row order, the executed FLOPs, every class's permutation
+(bin packing included) and whether the launcher would refuse the form."""
 import ctypes
 import random
 
@@ -73,6 +78,49 @@ def check_call(lib, op, B, H, W, Cin, Ho, Wo, Cout, k, s):
     return n + 1
 
 
+FORM_CODES = {"plain": 0, "stats": 1, "nstats": 2, "signs": 3, "update": 4}          # CGS_FORM_* of include/cgs_hip.h
+# the forms the entry points of an op offer, each with the epilogue they pass (the signs entry point: the forward's own relu / lrelu)
+OP_FORMS = {F: (("plain", IC.EPI_NONE), ("stats", IC.EPI_NONE)), TF: (("plain", IC.EPI_NONE), ("stats", IC.EPI_NONE), ("signs", IC.EPI_LRELU)),
+            BD: (("plain", IC.EPI_NONE), ("nstats", IC.EPI_NONE), ("update", IC.EPI_NONE)),
+            TB: (("plain", IC.EPI_NONE), ("nstats", IC.EPI_NONE), ("update", IC.EPI_NONE))}
+
+
+def sweep_workspaces(lib, op, B, H, W, Cin, Ho, Wo, Cout, k, s):
+    """The workspaces the sweep asks about: full, the packed weights alone, four bytes short of the slab the plain call would use."""
+    g = IC.geometry(op, B, H, W, Cin, Ho, Wo, Cout, k, s)
+    full = max(int(lib.cgs_conv_ws_bytes_for(op, B, H, W, Cin, Cout, k, k, s, s)), 16)
+    packed4 = 4 * IC.packed_floats(g)
+    need = IC.splitk_bytes(g)
+    if not need:
+        tiles, tl, _, _ = IC._tiles_and_tail(IC._state(g), 1 << 60)
+        need = IC.tail_bytes(tl, tiles.wide) if tl.s > 1 else 0
+    return sorted({full, packed4, packed4 + need - 4 if need else packed4})
+
+
+def check_plan(call, form, epilogue, nbytes):
+    """cgs_conv_igemm_plan, the whole plan before the launch, field by field against the restated planner.  -> comparisons made."""
+    from cgs_amd import lib as L
+    op, B, H, W, Cin, Ho, Wo, Cout, k, s = call
+    got = L.conv_igemm_plan(op, B, H, W, Cin, Ho, Wo, Cout, k, k, s, s, epilogue, FORM_CODES[form], nbytes)
+    g = IC.geometry(op, B, H, W, Cin, Ho, Wo, Cout, k, s)
+    packed4 = 4 * IC.packed_floats(g)
+    what = (call, form, epilogue, nbytes)
+    if nbytes < packed4 or nbytes <= 0 or not whole_batch(g) or lib_family(L.load(), op, B, H, W, Cin, Ho, Wo, Cout, k, s, epilogue, nbytes) != IC.FAMILY_IGEMM:
+        assert got is None, what
+        return 1
+    p = IC.plan(g, nbytes - packed4, form, epilogue)
+    assert (got is None) == p.refused, ("refused", what, got, p.refused)
+    if got is None:
+        return 1
+    want = {"kernel": p.kernel, "reduce": p.reduce, "tail": (p.tail_n, p.tail_s if p.tail_s > 1 else 0),
+            "plan": (p.xcd_map, p.cls_flip, p.uni, p.gx, p.splitk), "prio_t": tuple(p.prio_t), "row_order": p.row_order, "flops": float(p.flops),
+            "perm": None if p.perm is None else [list(q) for q in p.perm] + [[]] * (4 - len(p.perm))}
+    assert p.flops < 2 ** 53
+    for field in want:
+        assert got[field] == want[field], (field, what, got[field], want[field])
+    return len(want) + 1
+
+
 def call_of(case):
     Ho, Wo = IC.out_hw(case)
     if case.op in (F, BD):
@@ -88,6 +136,11 @@ def test_restatement_equals_the_library_on_the_table(lib):
         n += check_call(lib, *call_of(case))
         p = IC.case_plan(lib, case)
         assert not p.refused, (IC.case_id(case), "the entry point would refuse this form")
+        # the whole plan, before any launch: at the row's own workspace (where the query must answer) and at the sweep's three
+        from cgs_amd import lib as L
+        assert L.conv_igemm_plan(op, B, H, W, Cin, Ho, Wo, Cout, k, k, s, s, case.epilogue, FORM_CODES[case.form], IC.ws_bytes(lib, case)) is not None
+        for nbytes in sorted({IC.ws_bytes(lib, case), *sweep_workspaces(lib, *call_of(case))}):
+            n += check_plan(call_of(case), case.form, case.epilogue, nbytes)
     print(f"\nrestatement == library on {len(IC.CASES)} table rows, {n} comparisons")
 
 
@@ -117,7 +170,15 @@ def test_restatement_equals_the_library_on_a_sweep(lib):
             Ho, Wo = s * H - odd, s * W - odd
         calls.add((op, B, H, W, Cin, Ho, Wo, Cout, k, s))
     n = sum(check_call(lib, *c) for c in sorted(calls))
-    print(f"\nrestatement == library on a sweep of {len(calls)} calls, {n} comparisons")
+    # the whole plan of every call, in every form its op's entry points offer, at the three workspaces (a call that does not take the
+    # implicit-GEMM family there must be answered with "no plan")
+    planned = 0
+    for c in sorted(calls):
+        made = [check_plan(c, form, epilogue, nbytes) for nbytes in sweep_workspaces(lib, *c) for form, epilogue in OP_FORMS[c[0]]]
+        n += sum(made)
+        planned += max(made) > 1             # (a "no plan" answer is one comparison, a plan nine)
+    assert planned > len(calls) // 2
+    print(f"\nrestatement == library on a sweep of {len(calls)} calls ({planned} with a plan to compare), {n} comparisons")
 
 
 def features(case, p):
