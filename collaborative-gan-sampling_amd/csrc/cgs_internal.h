@@ -277,10 +277,6 @@ int cgs_mlp2d_wide_saliency(const float* const* w, const float* const* b, int nl
 int cgs_refine2d_wide(const float* const* w, const float* const* b, int nlayers, int nh, const float* x, float mean_host,
                       const float* mean_dev, float inv_batch, int steps, float rate, int method, float* best_x, float* best_step,
                       float* traj, int B, hipStream_t st);
-// its D step (mlp2d_wide_train.hip): workspace bytes, and the step on a workspace of at least that size
-size_t cgs_mlp2d_wide_train_ws(int Bt, int nlayers, int nh);
-int cgs_mlp2d_wide_train(float* const* w, float* const* b, int nlayers, int nh, const float* real, int B_real, const float* fake, int B_fake,
-                         float lr, float* const* gw, float* const* gb, float* loss, void* ws, hipStream_t st);
 
 bool cgs_convt_quad_fits(const CgsLayer& L);
 int cgs_conv_smalln_f_ok(const CgsLayer& L, int B, int epilogue);

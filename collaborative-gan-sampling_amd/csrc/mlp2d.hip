@@ -7,18 +7,8 @@
 //   forward  h_out[j] = relu(b[j] + sum_k h_in[k] * W[k][j])   : h_in[k] broadcast by readlane, W row k from LDS
 //   backward g_in[k]  = sum_j g_out[j] * W[k][j]               : lane k walks row k of the TRANSPOSED copy W^T[j][k]
 // Both LDS walks are stride-1 across lanes (conflict free).  All layers' weights (and transposes) live in LDS.
-#include "cgs_internal.h"
-#include "mlp2d_check.h"
+#include "mlp2d_shared.h"
 #include <climits>
-
-#define MLP_MAX_LAYERS 6      // all layers (and their transposes) LDS-resident: 6 layers = 133 KB of 160 KB
-#define MLP_WIDE_MAX 256      // D only (sigmoid / saliency / refiner, and the D step under its own name): 65 .. 256 units go to the sample-tile kernels of mlp2d_wide*.hip
-
-struct MlpParams {
-    const float* w[MLP_MAX_LAYERS];   // layer l: [din_l][dout_l] row-major (tf.layers.dense kernel)
-    const float* b[MLP_MAX_LAYERS];
-    int nlayers, nh;                   // dims: 2 -> nh -> ... -> nh -> 1
-};
 
 __device__ __forceinline__ float bcast(float v, int k) { return __shfl(v, k, 64); }
 
@@ -37,7 +27,7 @@ __device__ __forceinline__ MlpLds mlp_lds(float* smem, int nlayers) {
     return L;
 }
 
-__device__ void mlp_load(const MlpParams& p, const MlpLds& L) {
+__device__ void mlp_load(const Mlp2dParams& p, const MlpLds& L) {
     const int tid = threadIdx.x, nt = blockDim.x;
     for (int i = tid; i < 128; i += nt) { const int k = i >> 6, j = i & 63; L.w1[i] = j < p.nh ? p.w[0][k * p.nh + j] : 0.f; }
     for (int i = tid; i < 64; i += nt) L.wl[i] = i < p.nh ? p.w[p.nlayers - 1][i] : 0.f;
@@ -56,13 +46,15 @@ __device__ void mlp_load(const MlpParams& p, const MlpLds& L) {
     __syncthreads();
 }
 
-// one evaluation for the wave's sample at (x0, x1): logit and d logit / d x.  Lane j = hidden unit j.
-__device__ __forceinline__ void mlp_eval(const MlpParams& p, const MlpLds& L, float x0, float x1, int lane, float& logit,
-                                         float& dldx0, float& dldx1) {
-    unsigned long long masks[MLP_MAX_LAYERS];
+// Forward for the wave's sample at (x0, x1), lane j = hidden unit j: -> the logit.  masks[l] = the ReLU decisions of hidden layer l;
+// keep(l, h) sees every hidden activation.
+template <class Keep>
+__device__ __forceinline__ float mlp_forward(const Mlp2dParams& p, const MlpLds& L, float x0, float x1, int lane,
+                                             unsigned long long (&masks)[MLP2D_MAX_LAYERS], Keep&& keep) {
     float h = fmaf(x1, L.w1[64 + lane], fmaf(x0, L.w1[lane], L.bias[lane]));
     masks[0] = __ballot(h > 0.f);
     h = fmaxf(h, 0.f);
+    keep(0, h);
     for (int l = 1; l < p.nlayers - 1; ++l) {
         const float* W = L.wh + (size_t)(l - 1) * 8192;
         float a = L.bias[l * 64 + lane];
@@ -70,15 +62,22 @@ __device__ __forceinline__ void mlp_eval(const MlpParams& p, const MlpLds& L, fl
         for (int k = 0; k < 64; ++k) a = fmaf(bcast(h, k), W[k * 64 + lane], a);
         masks[l] = __ballot(a > 0.f);
         h = fmaxf(a, 0.f);
+        keep(l, h);
     }
     float part = h * L.wl[lane];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
-    logit = part + L.bias[(p.nlayers - 1) * 64];
-    // backward: g = d logit / d h (lane = unit)
-    float g = L.wl[lane];
+    return part + L.bias[(p.nlayers - 1) * 64];
+}
+
+// Backward from g = the gradient w.r.t. the top hidden activation (lane = unit): -> the gradient w.r.t. the first layer's pre-activation;
+// keep(l, g) sees the gradient w.r.t. the pre-activation of every hidden layer l.
+template <class Keep>
+__device__ __forceinline__ float mlp_backward(const Mlp2dParams& p, const MlpLds& L, int lane, const unsigned long long (&masks)[MLP2D_MAX_LAYERS],
+                                              float g, Keep&& keep) {
     for (int l = p.nlayers - 2; l >= 1; --l) {
         g = ((masks[l] >> lane) & 1ull) ? g : 0.f;
+        keep(l, g);
         const float* WT = L.wh + (size_t)(l - 1) * 8192 + 4096;
         float a = 0.f;
 #pragma unroll 8
@@ -86,16 +85,25 @@ __device__ __forceinline__ void mlp_eval(const MlpParams& p, const MlpLds& L, fl
         g = a;
     }
     g = ((masks[0] >> lane) & 1ull) ? g : 0.f;
+    keep(0, g);
+    return g;
+}
+
+// one evaluation for the wave's sample at (x0, x1): logit and d logit / d x
+__device__ __forceinline__ void mlp_eval(const Mlp2dParams& p, const MlpLds& L, float x0, float x1, int lane, float& logit,
+                                         float& dldx0, float& dldx1) {
+    unsigned long long masks[MLP2D_MAX_LAYERS];
+    const auto none = [](int, float) {};
+    logit = mlp_forward(p, L, x0, x1, lane, masks, none);
+    const float g = mlp_backward(p, L, lane, masks, L.wl[lane], none);
     float d0 = g * L.w1[lane], d1 = g * L.w1[64 + lane];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { d0 += __shfl_xor(d0, off, 64); d1 += __shfl_xor(d1, off, 64); }
     dldx0 = d0; dldx1 = d1;
 }
 
-__device__ __forceinline__ float sigmoidf_(float v) { return v >= 0.f ? 1.f / (1.f + expf(-v)) : expf(v) / (1.f + expf(v)); }
-
 // sigmoid [B] and saliency [B,2] = inv_batch * (sigmoid - 1) * d logit / dx   (synthetic/GAN.py:108-111)
-__global__ __launch_bounds__(1024) void mlp_saliency_kernel(MlpParams p, const float* __restrict__ x, float* __restrict__ sig,
+__global__ __launch_bounds__(1024) void mlp_saliency_kernel(Mlp2dParams p, const float* __restrict__ x, float* __restrict__ sig,
                                                             float* __restrict__ sal, int B, float inv_batch) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const MlpLds L = mlp_lds(smem, p.nlayers);
@@ -105,15 +113,15 @@ __global__ __launch_bounds__(1024) void mlp_saliency_kernel(MlpParams p, const f
         float logit, d0, d1;
         mlp_eval(p, L, x[2 * s], x[2 * s + 1], lane, logit, d0, d1);
         if (lane == 0) {
-            const float sg = sigmoidf_(logit);
+            const float sg = sigmoid_stable(logit);
             sig[s] = sg;
             if (sal) { sal[2 * s] = inv_batch * (sg - 1.f) * d0; sal[2 * s + 1] = inv_batch * (sg - 1.f) * d1; }
         }
     }
 }
 
-// the whole refiner_cpu loop for one sample per wave.  method: 0 sgd, 1 momentum, 2 ladam (policy.py:26-61, numpy branch)
-__global__ __launch_bounds__(1024) void refine2d_kernel(MlpParams p, const float* __restrict__ x_in, float real_mean_host,
+// the whole refiner_cpu loop for one sample per wave (Refine2dState of mlp2d_shared.h): pass i evaluates the point of step i
+__global__ __launch_bounds__(1024) void refine2d_kernel(Mlp2dParams p, const float* __restrict__ x_in, float real_mean_host,
                                                         const float* __restrict__ real_mean_dev,
                                                         float inv_batch, int steps, float rate, int method,
                                                         float* __restrict__ best_x, float* __restrict__ best_step,
@@ -124,42 +132,16 @@ __global__ __launch_bounds__(1024) void refine2d_kernel(MlpParams p, const float
     const float real_mean = real_mean_dev ? real_mean_dev[0] : real_mean_host;      // device scalar: no host round trip per batch
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     for (int s = blockIdx.x * nw + wave; s < B; s += gridDim.x * nw) {
-        float x0 = x_in[2 * s], x1 = x_in[2 * s + 1];
-        float logit, d0, d1;
-        mlp_eval(p, L, x0, x1, lane, logit, d0, d1);
-        float sg = sigmoidf_(logit);
-        float g0 = inv_batch * (sg - 1.f) * d0, g1 = inv_batch * (sg - 1.f) * d1;
-        float loss = real_mean - sg;                                   // refiner_cpu.py:28
-        float bx0 = x0, bx1 = x1, bl = loss, bs = 0.f;
-        float m0 = 0.f, m1 = 0.f, v0 = 0.f, v1 = 0.f, ll = 0.f;
-        if (traj && lane == 0) { traj[((size_t)s * (steps + 1)) * 2] = x0; traj[((size_t)s * (steps + 1)) * 2 + 1] = x1; }
-        for (int i = 0; i < steps; ++i) {
-#pragma clang fp contract(off)
-            if (method == 0) {
-                x0 -= rate * g0; x1 -= rate * g1;
-            } else if (method == 1) {
-                const float a0 = rate * g0, a1 = rate * g1;
-                m0 = i == 0 ? a0 : 0.9f * m0 + a0; m1 = i == 0 ? a1 : 0.9f * m1 + a1;
-                x0 -= m0; x1 -= m1;
-            } else {                                                   // ladam, policy.py:39-61
-                if (i == 0) { m0 = g0; m1 = g1; v0 = g0 * g0; v1 = g1 * g1; ll = loss; }
-                else {
-                    m0 = 0.9f * m0 + 0.1f * g0; m1 = 0.9f * m1 + 0.1f * g1;        // (1. - 0.9) rounds to 0.1f in float32
-                    v0 = 0.5f * v0 + 0.5f * (g0 * g0); v1 = 0.5f * v1 + 0.5f * (g1 * g1);
-                    ll = 0.5f * ll + 0.5f * loss;
-                }
-                const float c = fmaxf(ll + 0.5f, 0.f);
-                const float rs = c * c;
-                x0 -= rate * m0 / (sqrtf(v0) + 1e-8f) * rs; x1 -= rate * m1 / (sqrtf(v1) + 1e-8f) * rs;
-            }
-            mlp_eval(p, L, x0, x1, lane, logit, d0, d1);
-            sg = sigmoidf_(logit);
-            g0 = inv_batch * (sg - 1.f) * d0; g1 = inv_batch * (sg - 1.f) * d1;
-            loss = real_mean - sg;
-            if (bl - loss > 0.f) { bl = loss; bx0 = x0; bx1 = x1; bs = (float)(i + 1); }          // refiner_cpu.py:58-61
-            if (traj && lane == 0) { traj[((size_t)s * (steps + 1) + i + 1) * 2] = x0; traj[((size_t)s * (steps + 1) + i + 1) * 2 + 1] = x1; }
+        Refine2dState r(x_in[2 * s], x_in[2 * s + 1]);
+        for (int i = 0; ; ++i) {
+            float logit, d0, d1;
+            mlp_eval(p, L, r.x0, r.x1, lane, logit, d0, d1);
+            r.seen(i, logit, d0, d1, inv_batch, real_mean);
+            if (traj && lane == 0) r.record(traj, (size_t)s, steps, i);
+            if (i == steps) break;
+            r.step(i, method, rate);
         }
-        if (lane == 0) { best_x[2 * s] = bx0; best_x[2 * s + 1] = bx1; best_step[s] = bs; }
+        if (lane == 0) { best_x[2 * s] = r.bx0; best_x[2 * s + 1] = r.bx1; best_step[s] = r.bs; }
     }
 }
 
@@ -171,7 +153,7 @@ __global__ __launch_bounds__(1024) void refine2d_kernel(MlpParams p, const float
 // db_l = column sums of Delta_l, summed over the samples in a FIXED order (deterministic), then w -= lr * g in place.
 // ------------------------------------------------------------------------------------------------------------------
 // acts / deltas: [B_total][nlayers-1][64]; dlast / bce: [B_total]
-__global__ __launch_bounds__(1024) void mlp_train_fwdbwd_kernel(MlpParams p, const float* __restrict__ x, int B, int row0, float target,
+__global__ __launch_bounds__(1024) void mlp_train_fwdbwd_kernel(Mlp2dParams p, const float* __restrict__ x, int B, int row0, float target,
                                                                 float scale, float* __restrict__ acts, float* __restrict__ deltas,
                                                                 float* __restrict__ dlast, float* __restrict__ bce) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -182,64 +164,34 @@ __global__ __launch_bounds__(1024) void mlp_train_fwdbwd_kernel(MlpParams p, con
     for (int s = blockIdx.x * nw + wave; s < B; s += gridDim.x * nw) {
         float* A = acts + (size_t)(row0 + s) * nhid * 64;
         float* D = deltas + (size_t)(row0 + s) * nhid * 64;
-        unsigned long long masks[MLP_MAX_LAYERS];
-        const float x0 = x[2 * s], x1 = x[2 * s + 1];
-        float h = fmaf(x1, L.w1[64 + lane], fmaf(x0, L.w1[lane], L.bias[lane]));
-        masks[0] = __ballot(h > 0.f);
-        h = fmaxf(h, 0.f);
-        A[lane] = h;
-        for (int l = 1; l < nhid; ++l) {
-            const float* W = L.wh + (size_t)(l - 1) * 8192;
-            float a = L.bias[l * 64 + lane];
-#pragma unroll 8
-            for (int k = 0; k < 64; ++k) a = fmaf(bcast(h, k), W[k * 64 + lane], a);
-            masks[l] = __ballot(a > 0.f);
-            h = fmaxf(a, 0.f);
-            A[l * 64 + lane] = h;
-        }
-        float part = h * L.wl[lane];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
-        const float logit = part + L.bias[(p.nlayers - 1) * 64];
-        const float seed = scale * (sigmoidf_(logit) - target);            // d (scale * BCE(logit, target)) / d logit
+        unsigned long long masks[MLP2D_MAX_LAYERS];
+        const float logit = mlp_forward(p, L, x[2 * s], x[2 * s + 1], lane, masks, [&](int l, float h) { A[l * 64 + lane] = h; });
+        const float seed = scale * (sigmoid_stable(logit) - target);            // d (scale * BCE(logit, target)) / d logit
         if (lane == 0) {
             dlast[row0 + s] = seed;
             bce[row0 + s] = scale * (fmaxf(logit, 0.f) - logit * target + log1pf(expf(-fabsf(logit))));
         }
-        float g = seed * L.wl[lane];
-        for (int l = nhid - 1; l >= 1; --l) {
-            g = ((masks[l] >> lane) & 1ull) ? g : 0.f;
-            D[l * 64 + lane] = g;
-            const float* WT = L.wh + (size_t)(l - 1) * 8192 + 4096;
-            float a = 0.f;
-#pragma unroll 8
-            for (int jj = 0; jj < 64; ++jj) a = fmaf(bcast(g, jj), WT[jj * 64 + lane], a);
-            g = a;
-        }
-        g = ((masks[0] >> lane) & 1ull) ? g : 0.f;
-        D[lane] = g;
+        mlp_backward(p, L, lane, masks, seed * L.wl[lane], [&](int l, float g) { D[l * 64 + lane] = g; });
     }
 }
 
-struct MlpTrainPtrs {
-    float* w[MLP_MAX_LAYERS];
-    float* b[MLP_MAX_LAYERS];
-    float* gw[MLP_MAX_LAYERS];      // may be null
-    float* gb[MLP_MAX_LAYERS];
+// The sample tile of the two weight-gradient kernels: 64 samples' inputs of a layer and its output gradients
+struct MlpGradTile {
+    float As[64][65];
+    __attribute__((aligned(16))) float Ds[64][64];
 };
 
 // block l < nlayers: gradient (+ SGD step) of layer l; block nlayers: the two loss sums.  1024 threads: thread -> row i = t / 16
 // of the [din][dout] kernel and 4 columns j4 .. j4+3; the sample dimension is walked in tiles of 64 staged through LDS.
-__global__ __launch_bounds__(1024) void mlp_train_grad_kernel(MlpTrainPtrs q, int nlayers, int nh, const float* __restrict__ xr, int Br,
+__global__ __launch_bounds__(1024) void mlp_train_grad_kernel(Mlp2dVars q, int nlayers, int nh, const float* __restrict__ xr, int Br,
                                                               const float* __restrict__ xf, int Bf, const float* __restrict__ acts,
                                                               const float* __restrict__ deltas, const float* __restrict__ dlast,
                                                               const float* __restrict__ bce, float lr, float* __restrict__ loss) {
-    __shared__ float As[64][65];
-    __shared__ __attribute__((aligned(16))) float Ds[64][64];
+    __shared__ MlpGradTile T;
     const int t = threadIdx.x, Bt = Br + Bf, nhid = nlayers - 1;
     const int l = blockIdx.x;
     if (l == nlayers) {            // d_loss_real, d_loss_fake: fixed-order strided sums + a fixed tree
-        float* red = &As[0][0];
+        float* red = &T.As[0][0];
         for (int part = 0; part < 2; ++part) {
             const int lo = part ? Br : 0, hi = part ? Bt : Br;
             float s = 0.f;
@@ -265,13 +217,13 @@ __global__ __launch_bounds__(1024) void mlp_train_grad_kernel(MlpTrainPtrs q, in
                 if (l == nlayers - 1) { if (c == 0) d = dlast[b]; }
                 else d = deltas[((size_t)b * nhid + l) * 64 + c];
             }
-            As[bb][c] = a; Ds[bb][c] = d;
+            T.As[bb][c] = a; T.Ds[bb][c] = d;
         }
         __syncthreads();
 #pragma unroll 8
         for (int bb = 0; bb < 64; ++bb) {
-            const float a = As[bb][i];
-            const float4 d = *(const float4*)&Ds[bb][j4];
+            const float a = T.As[bb][i];
+            const float4 d = *(const float4*)&T.Ds[bb][j4];
             acc[0] = fmaf(a, d.x, acc[0]); acc[1] = fmaf(a, d.y, acc[1]); acc[2] = fmaf(a, d.z, acc[2]); acc[3] = fmaf(a, d.w, acc[3]);
             accb[0] += d.x; accb[1] += d.y; accb[2] += d.z; accb[3] += d.w;
         }
@@ -292,52 +244,42 @@ __global__ __launch_bounds__(1024) void mlp_train_grad_kernel(MlpTrainPtrs q, in
     }
 }
 
-// max_nh: 64 for the kernels of this file; MLP_WIDE_MAX for the entry points that mlp2d_wide.hip serves past 64.  min_nh: 65 for the
-// entry point that only mlp2d_wide_train.hip serves
-static int mlp_fill(MlpParams& p, const float* const* w, const float* const* b, int nlayers, int nh, int max_nh, const char* who, int min_nh = 1) {
-    const int rc = mlp2d_check_net(who, w, b, nlayers, nh, min_nh, max_nh);
-    if (rc) return rc;
-    for (int l = 0; l < nlayers; ++l) { p.w[l] = w[l]; p.b[l] = b[l]; }
-    p.nlayers = nlayers; p.nh = nh;
+static size_t mlp_smem(int nlayers) { return (size_t)(192 + nlayers * 64 + (nlayers - 2) * 8192) * sizeof(float); }
+
+// One launch of the wave-per-sample kernel K over B samples: 16 waves a block, at most 256 blocks; the LDS attribute once per kernel and
+// device (the flag inside CGS_SMEM_ATTR is this function's, one per K), the launch, its check.  `who` names the entry point, `what` the launch.
+template <auto K, class... Args>
+static int mlp_launch(int B, int nlayers, const char* who, const char* what, void* stream, const Args&... args) {
+    CGS_SMEM_ATTR(160 * 1024, who, K);
+    int blocks = (B + 15) / 16; if (blocks > 256) blocks = 256;
+    hipLaunchKernelGGL(K, dim3(blocks), dim3(1024), mlp_smem(nlayers), (hipStream_t)stream, args...);
+    CGS_CHECK_LAUNCH(what);
     return CGS_OK;
 }
-
-static size_t mlp_smem(int nlayers) { return (size_t)(192 + nlayers * 64 + (nlayers - 2) * 8192) * sizeof(float); }
 
 extern "C" {
 
 int cgs_mlp2d_sigmoid_saliency(const float* const* w, const float* const* b, int nlayers, int nhidden, const float* x,
                                float* sigmoid, float* saliency, int B, float inv_batch, void* stream) {
-    MlpParams p;
-    int rc = mlp_fill(p, w, b, nlayers, nhidden, MLP_WIDE_MAX, "mlp2d_sigmoid_saliency");
+    const int rc = mlp2d_check_net("mlp2d_sigmoid_saliency", w, b, nlayers, nhidden, 1, MLP2D_MAX_NH);
     if (rc) return rc;
     if (B <= 0 || !x || !sigmoid) return cgs_set_error(CGS_EINVAL, "mlp2d_sigmoid_saliency: bad argument");
-    if (nhidden > 64) return cgs_mlp2d_wide_saliency(w, b, nlayers, nhidden, x, sigmoid, saliency, B, inv_batch, (hipStream_t)stream);
-    const size_t smem = mlp_smem(nlayers);
-    CGS_SMEM_ATTR(160 * 1024, "mlp2d_sigmoid_saliency", mlp_saliency_kernel);
-    int blocks = (B + 15) / 16; if (blocks > 256) blocks = 256;
-    hipLaunchKernelGGL(mlp_saliency_kernel, dim3(blocks), dim3(1024), smem, (hipStream_t)stream, p, x, sigmoid, saliency, B, inv_batch);
-    CGS_CHECK_LAUNCH("mlp2d_sigmoid_saliency");
-    return CGS_OK;
+    if (nhidden > MLP2D_NARROW_MAX_NH) return cgs_mlp2d_wide_saliency(w, b, nlayers, nhidden, x, sigmoid, saliency, B, inv_batch, (hipStream_t)stream);
+    return mlp_launch<mlp_saliency_kernel>(B, nlayers, "mlp2d_sigmoid_saliency", "mlp2d_sigmoid_saliency", stream, mlp2d_params(w, b, nlayers, nhidden), x,
+                                           sigmoid, saliency, B, inv_batch);
 }
 
 static int refine2d_launch(const float* const* w, const float* const* b, int nlayers, int nhidden, const float* x, float mean_host,
                            const float* mean_dev, float inv_batch, int steps, float rate, int method, float* best_x, float* best_step,
                            float* traj, int B, void* stream) {
-    MlpParams p;
-    int rc = mlp_fill(p, w, b, nlayers, nhidden, MLP_WIDE_MAX, "refine2d");
+    const int rc = mlp2d_check_net("refine2d", w, b, nlayers, nhidden, 1, MLP2D_MAX_NH);
     if (rc) return rc;
     if (B <= 0 || steps < 0 || method < 0 || method > 2 || !x || !best_x || !best_step) return cgs_set_error(CGS_EINVAL, "refine2d: bad argument");
-    if (nhidden > 64)
+    if (nhidden > MLP2D_NARROW_MAX_NH)
         return cgs_refine2d_wide(w, b, nlayers, nhidden, x, mean_host, mean_dev, inv_batch, steps, rate, method, best_x, best_step, traj, B,
                                  (hipStream_t)stream);
-    const size_t smem = mlp_smem(nlayers);
-    CGS_SMEM_ATTR(160 * 1024, "refine2d", refine2d_kernel);
-    int blocks = (B + 15) / 16; if (blocks > 256) blocks = 256;
-    hipLaunchKernelGGL(refine2d_kernel, dim3(blocks), dim3(1024), smem, (hipStream_t)stream, p, x, mean_host, mean_dev, inv_batch, steps, rate,
-                       method, best_x, best_step, traj, B);
-    CGS_CHECK_LAUNCH("refine2d");
-    return CGS_OK;
+    return mlp_launch<refine2d_kernel>(B, nlayers, "refine2d", "refine2d", stream, mlp2d_params(w, b, nlayers, nhidden), x, mean_host, mean_dev, inv_batch,
+                                       steps, rate, method, best_x, best_step, traj, B);
 }
 
 int cgs_refine2d(const float* const* w, const float* const* b, int nlayers, int nhidden, const float* x, float real_sigmoid_mean,
@@ -354,14 +296,13 @@ int cgs_refine2d_devbase(const float* const* w, const float* const* b, int nlaye
 }
 
 size_t cgs_mlp2d_train_ws_bytes(int B_total, int nlayers) {
-    if (B_total <= 0 || nlayers < 2 || nlayers > MLP_MAX_LAYERS) return 0;
+    if (B_total <= 0 || nlayers < 2 || nlayers > MLP2D_MAX_LAYERS) return 0;
     return ((size_t)B_total * (nlayers - 1) * 64 * 2 + (size_t)B_total * 2) * sizeof(float);
 }
 
 int cgs_mlp2d_d_step(float* const* w, float* const* b, int nlayers, int nhidden, const float* real, int B_real, const float* fake,
                      int B_fake, float lr, float* const* gw, float* const* gb, float* loss, void* ws, size_t ws_bytes, void* stream) {
-    MlpParams p;
-    int rc = mlp_fill(p, (const float* const*)w, (const float* const*)b, nlayers, nhidden, 64, "mlp2d_d_step");
+    int rc = mlp2d_check_net("mlp2d_d_step", (const float* const*)w, (const float* const*)b, nlayers, nhidden, 1, MLP2D_NARROW_MAX_NH);
     if (rc) return rc;
     if (B_real <= 0 || B_fake <= 0 || !real || !fake) return cgs_set_error(CGS_EINVAL, "mlp2d_d_step: bad argument");
     const int Bt = B_real + B_fake;
@@ -371,40 +312,17 @@ int cgs_mlp2d_d_step(float* const* w, float* const* b, int nlayers, int nhidden,
     float* deltas = acts + (size_t)Bt * (nlayers - 1) * 64;
     float* dlast = deltas + (size_t)Bt * (nlayers - 1) * 64;
     float* bce = dlast + Bt;
-    const size_t smem = mlp_smem(nlayers);
-    CGS_SMEM_ATTR(160 * 1024, "mlp2d_d_step", mlp_train_fwdbwd_kernel);
+    const Mlp2dParams p = mlp2d_params((const float* const*)w, (const float* const*)b, nlayers, nhidden);
     for (int part = 0; part < 2; ++part) {      // real rows (target 1) then refined rows (target 0); each loss term is a MEAN
         const int B = part ? B_fake : B_real;
-        int blocks = (B + 15) / 16; if (blocks > 256) blocks = 256;
-        hipLaunchKernelGGL(mlp_train_fwdbwd_kernel, dim3(blocks), dim3(1024), smem, (hipStream_t)stream, p, part ? fake : real, B,
-                           part ? B_real : 0, part ? 0.f : 1.f, 1.f / (float)B, acts, deltas, dlast, bce);
-        CGS_CHECK_LAUNCH("mlp_train_fwdbwd");
+        rc = mlp_launch<mlp_train_fwdbwd_kernel>(B, nlayers, "mlp2d_d_step", "mlp_train_fwdbwd", stream, p, part ? fake : real, B, part ? B_real : 0,
+                                                 part ? 0.f : 1.f, 1.f / (float)B, acts, deltas, dlast, bce);
+        if (rc) return rc;
     }
-    MlpTrainPtrs q;
-    for (int l = 0; l < MLP_MAX_LAYERS; ++l) {
-        q.w[l] = l < nlayers ? w[l] : nullptr; q.b[l] = l < nlayers ? b[l] : nullptr;
-        q.gw[l] = (gw && l < nlayers) ? gw[l] : nullptr; q.gb[l] = (gb && l < nlayers) ? gb[l] : nullptr;
-    }
-    hipLaunchKernelGGL(mlp_train_grad_kernel, dim3(nlayers + 1), dim3(1024), 0, (hipStream_t)stream, q, nlayers, nhidden, real, B_real, fake,
-                       B_fake, acts, deltas, dlast, bce, lr, loss);
+    hipLaunchKernelGGL(mlp_train_grad_kernel, dim3(nlayers + 1), dim3(1024), 0, (hipStream_t)stream, mlp2d_vars(w, b, gw, gb, nlayers), nlayers, nhidden,
+                       real, B_real, fake, B_fake, acts, deltas, dlast, bce, lr, loss);
     CGS_CHECK_LAUNCH("mlp_train_grad");
     return CGS_OK;
-}
-
-size_t cgs_mlp2d_wide_train_ws_bytes(int B_total, int nlayers, int nhidden) {
-    if (B_total <= 0 || nlayers < 2 || nlayers > MLP_MAX_LAYERS || nhidden <= 64 || nhidden > MLP_WIDE_MAX) return 0;
-    return cgs_mlp2d_wide_train_ws(B_total, nlayers, nhidden);
-}
-
-int cgs_mlp2d_wide_d_step(float* const* w, float* const* b, int nlayers, int nhidden, const float* real, int B_real, const float* fake,
-                          int B_fake, float lr, float* const* gw, float* const* gb, float* loss, void* ws, size_t ws_bytes, void* stream) {
-    MlpParams p;
-    int rc = mlp_fill(p, (const float* const*)w, (const float* const*)b, nlayers, nhidden, MLP_WIDE_MAX, "mlp2d_wide_d_step", 65);
-    if (rc) return rc;
-    if (B_real <= 0 || B_fake <= 0 || (long)B_real + B_fake > (1 << 24) || !real || !fake) return cgs_set_error(CGS_EINVAL, "mlp2d_wide_d_step: bad argument");
-    const size_t need = cgs_mlp2d_wide_train_ws_bytes(B_real + B_fake, nlayers, nhidden);
-    if (!ws || ws_bytes < need) return cgs_set_error(CGS_EWORKSPACE, "mlp2d_wide_d_step: workspace %zu < %zu bytes", ws_bytes, need);
-    return cgs_mlp2d_wide_train(w, b, nlayers, nhidden, real, B_real, fake, B_fake, lr, gw, gb, loss, ws, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -425,23 +343,22 @@ int cgs_mlp2d_wide_d_step(float* const* w, float* const* b, int nlayers, int nhi
 // ------------------------------------------------------------------------------------------------------------------
 #define GEN_WMAX 256          // at most 256 waves (partials) per layer; >= 8 samples per wave below that
 
+// (bcast above and rlane stay two: each kernel family keeps the broadcast it was built and measured on; one helper for both was not tried)
 __device__ __forceinline__ float rlane(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
-
-#define GEN_PBATCH 16          // partials fetched per round trip: the combine is a serial chain, its loads need not be
 
 // (mean, biased variance) of the unit `lane` from the W wave partials [W][2][64], in wave order.  Every wave is non-empty (gen_plan).
 __device__ void gen_combine(const float* __restrict__ part, int W, int chunk, int B, int lane, float& mean, float& var) {
     float n = 0.f, m = 0.f, M2 = 0.f;
-    for (int p0 = 0; p0 < W; p0 += GEN_PBATCH) {
-        float pm[GEN_PBATCH], pM[GEN_PBATCH];
+    for (int p0 = 0; p0 < W; p0 += MLP2D_PBATCH) {
+        float pm[MLP2D_PBATCH], pM[MLP2D_PBATCH];
 #pragma unroll
-        for (int q = 0; q < GEN_PBATCH; ++q) {
+        for (int q = 0; q < MLP2D_PBATCH; ++q) {
             const bool in = p0 + q < W;
             pm[q] = in ? part[(size_t)(p0 + q) * 128 + lane] : 0.f;
             pM[q] = in ? part[(size_t)(p0 + q) * 128 + 64 + lane] : 0.f;
         }
 #pragma unroll
-        for (int q = 0; q < GEN_PBATCH; ++q) {
+        for (int q = 0; q < MLP2D_PBATCH; ++q) {
             if (p0 + q >= W) break;
             const float nb = (float)min(chunk, B - (p0 + q) * chunk);
             const float nab = n + nb, d = pm[q] - m;
@@ -456,21 +373,18 @@ __device__ void gen_combine(const float* __restrict__ part, int W, int chunk, in
 // (sum dxhat, sum dxhat*xhat) of the unit `lane` from the W wave partials, in wave order
 __device__ void gen_sum2(const float* __restrict__ part, int W, int lane, float& s1, float& s2) {
     s1 = 0.f; s2 = 0.f;
-    for (int p0 = 0; p0 < W; p0 += GEN_PBATCH) {
-        float a[GEN_PBATCH], b[GEN_PBATCH];
+    for (int p0 = 0; p0 < W; p0 += MLP2D_PBATCH) {
+        float a[MLP2D_PBATCH], b[MLP2D_PBATCH];
 #pragma unroll
-        for (int q = 0; q < GEN_PBATCH; ++q) {
+        for (int q = 0; q < MLP2D_PBATCH; ++q) {
             const bool in = p0 + q < W;
             a[q] = in ? part[(size_t)(p0 + q) * 128 + lane] : 0.f;
             b[q] = in ? part[(size_t)(p0 + q) * 128 + 64 + lane] : 0.f;
         }
 #pragma unroll
-        for (int q = 0; q < GEN_PBATCH; ++q) { s1 += a[q]; s2 += b[q]; }
+        for (int q = 0; q < MLP2D_PBATCH; ++q) { s1 += a[q]; s2 += b[q]; }
     }
 }
-
-__device__ __forceinline__ float gen_xhat(float a, float mean, float rstd) { return (a - mean) * rstd; }
-__device__ __forceinline__ float gen_bn_relu(float a, float mean, float rstd, float g, float b) { return fmaxf(fmaf(gen_xhat(a, mean, rstd), g, b), 0.f); }
 
 struct GenFwd {
     const float* w; const float* b;                    // dense layer l: [din][dout], [dout]
@@ -528,7 +442,7 @@ __global__ __launch_bounds__(256) void gen_fwd_kernel(GenFwd a) {
             sum += acc;
             continue;
         }
-        const float h = lane < nh ? gen_bn_relu(a.pre_in[(size_t)s * 64 + lane], mean, rstd, gam, bet) : 0.f;
+        const float h = lane < nh ? mlp2d_bn_relu(mlp2d_xhat(a.pre_in[(size_t)s * 64 + lane], mean, rstd), gam, bet) : 0.f;
         if (!last) {
             float acc = bias;
 #pragma unroll
@@ -595,7 +509,7 @@ __global__ __launch_bounds__(256) void gen_bwd_kernel(GenBwd a) {
             dh = fmaf(a.gplug[2 * s + 1], wr[1], a.gplug[2 * s] * wr[0]);
         } else {
             const size_t o = (size_t)s * 64 + lane;
-            const float xh = on ? gen_xhat(a.pre_u[o], mu, ru) : 0.f;
+            const float xh = on ? mlp2d_xhat(a.pre_u[o], mu, ru) : 0.f;
             const float da = on ? ru * (a.dbuf_u[o] - c1 - xh * c2) : 0.f;        // tf FusedBatchNormGrad, training
             a.dbuf_u[o] = da;
             if (!a.has_low) continue;
@@ -606,7 +520,7 @@ __global__ __launch_bounds__(256) void gen_bwd_kernel(GenBwd a) {
         const size_t o = (size_t)s * 64 + lane;
         float dx = 0.f, xh = 0.f;
         if (on) {
-            xh = gen_xhat(a.pre_l[o], ml, rl);
+            xh = mlp2d_xhat(a.pre_l[o], ml, rl);
             dx = fmaf(xh, gl, bl) > 0.f ? dh * gl : 0.f;
         }
         a.dbuf_l[o] = dx;
@@ -618,9 +532,8 @@ __global__ __launch_bounds__(256) void gen_bwd_kernel(GenBwd a) {
 }
 
 struct GenGrad {
-    float* w[MLP_MAX_LAYERS]; float* b[MLP_MAX_LAYERS];
-    float* gw[MLP_MAX_LAYERS]; float* gb[MLP_MAX_LAYERS];           // may be null
-    const float* gamma[MLP_MAX_LAYERS - 1]; const float* beta[MLP_MAX_LAYERS - 1];
+    Mlp2dVars v;
+    const float* gamma[MLP2D_MAX_LAYERS - 1]; const float* beta[MLP2D_MAX_LAYERS - 1];
     const float* z; const float* gplug; const float* pre; const float* stats; const float* dbuf;
     int nlayers, nh, B;
     float lr;
@@ -629,8 +542,7 @@ struct GenGrad {
 // block l: dW_l = in_l^T da_l, db_l = column sums of da_l (in_0 = z, in_l = relu(BN(a_{l-1})) recomputed exactly as the forward did;
 // da of the last layer = grad_plugin), samples in tiles of 64 in a fixed order; then w -= lr*g in place.
 __global__ __launch_bounds__(1024) void gen_grad_kernel(GenGrad q) {
-    __shared__ float As[64][65];
-    __shared__ __attribute__((aligned(16))) float Ds[64][64];
+    __shared__ MlpGradTile T;
     const int t = threadIdx.x, l = blockIdx.x, nh = q.nh, B = q.B;
     const bool last = l == q.nlayers - 1;
     const int din = l == 0 ? 2 : nh, dout = last ? 2 : nh;
@@ -645,17 +557,17 @@ __global__ __launch_bounds__(1024) void gen_grad_kernel(GenGrad q) {
             float x = 0.f, d = 0.f;
             if (b < B) {
                 if (l == 0) { if (c < 2) x = q.z[2 * b + c]; }
-                else if (c < nh) x = gen_bn_relu(pin[(size_t)b * 64 + c], sl[c], sl[64 + c], q.gamma[l - 1][c], q.beta[l - 1][c]);
+                else if (c < nh) x = mlp2d_bn_relu(mlp2d_xhat(pin[(size_t)b * 64 + c], sl[c], sl[64 + c]), q.gamma[l - 1][c], q.beta[l - 1][c]);
                 if (last) { if (c < 2) d = q.gplug[2 * b + c]; }
                 else d = dl[(size_t)b * 64 + c];
             }
-            As[bb][c] = x; Ds[bb][c] = d;
+            T.As[bb][c] = x; T.Ds[bb][c] = d;
         }
         __syncthreads();
 #pragma unroll 8
         for (int bb = 0; bb < 64; ++bb) {
-            const float x = As[bb][i];
-            const float4 d = *(const float4*)&Ds[bb][j4];
+            const float x = T.As[bb][i];
+            const float4 d = *(const float4*)&T.Ds[bb][j4];
             acc[0] = fmaf(x, d.x, acc[0]); acc[1] = fmaf(x, d.y, acc[1]); acc[2] = fmaf(x, d.z, acc[2]); acc[3] = fmaf(x, d.w, acc[3]);
             accb[0] += d.x; accb[1] += d.y; accb[2] += d.z; accb[3] += d.w;
         }
@@ -666,12 +578,12 @@ __global__ __launch_bounds__(1024) void gen_grad_kernel(GenGrad q) {
         const int j = j4 + e;
         if (i < din && j < dout) {
             const size_t o = (size_t)i * dout + j;
-            if (q.gw[l]) q.gw[l][o] = acc[e];
-            if (q.lr != 0.f) q.w[l][o] = q.w[l][o] - q.lr * acc[e];
+            if (q.v.gw[l]) q.v.gw[l][o] = acc[e];
+            if (q.lr != 0.f) q.v.w[l][o] = q.v.w[l][o] - q.lr * acc[e];
         }
         if (i == 0 && j < dout) {
-            if (q.gb[l]) q.gb[l][j] = accb[e];
-            if (q.lr != 0.f) q.b[l][j] = q.b[l][j] - q.lr * accb[e];
+            if (q.v.gb[l]) q.v.gb[l][j] = accb[e];
+            if (q.lr != 0.f) q.v.b[l][j] = q.v.b[l][j] - q.lr * accb[e];
         }
     }
 }
@@ -684,31 +596,36 @@ static void gen_plan(int B, int& W, int& chunk) {
     W = cgs_ceil_div(B, chunk);
 }
 
-static size_t gen_ws_floats(int B, int nlayers, int with_backward) {
-    const size_t H = (size_t)(nlayers - 1);
-    return H * (size_t)B * 64 * (with_backward ? 2 : 1) + H * GEN_WMAX * 128 + H * 128;
-}
+// The workspace, H = nlayers - 1: pre [H][B][64] | part [H][GEN_WMAX][2][64] | stats [H][2][64] | the G step's dbuf [H][B][64]
+struct GenWs {
+    float* ws;
+    size_t H, npre, npart;      // floats of one layer's pre (or dbuf) and of its partials
+    GenWs(void* ws_, int B, int nlayers) : ws((float*)ws_), H(nlayers - 1), npre((size_t)B * 64), npart((size_t)GEN_WMAX * 128) {}
+    float* pre(int l) const { return ws + l * npre; }
+    float* part(int l) const { return ws + H * npre + l * npart; }
+    float* stats(int l) const { return ws + H * (npre + npart) + (size_t)l * 128; }
+    float* dbuf(int l) const { return ws + H * (npre + npart + 128) + l * npre; }
+    size_t floats(int with_backward) const { return H * (npre * (with_backward ? 2 : 1) + npart + 128); }
+};
 
-static int gen_forward(const MlpParams& p, const float* const* gamma, const float* const* beta, float* const* mm, float* const* mv,
-                       const float* z, float* x, int B, int train, float eps, float* bstat, float* ws, hipStream_t st) {
-    const int nl = p.nlayers, H = nl - 1;
+static size_t gen_ws_floats(int B, int nlayers, int with_backward) { return GenWs(nullptr, B, nlayers).floats(with_backward); }
+
+static int gen_forward(const Mlp2dParams& p, const float* const* gamma, const float* const* beta, float* const* mm, float* const* mv,
+                       const float* z, float* x, int B, int train, float eps, float* bstat, const GenWs& ws, hipStream_t st) {
+    const int nl = p.nlayers;
     int W, chunk;
     gen_plan(B, W, chunk);
-    float* pre = ws;
-    float* part = pre + (size_t)H * B * 64;
-    float* stats = part + (size_t)H * GEN_WMAX * 128;
     for (int l = 0; l < nl; ++l) {
         GenFwd a = {};
         a.w = p.w[l]; a.b = p.b[l];
         if (l > 0) {
             a.gamma = gamma[l - 1]; a.beta = beta[l - 1]; a.mmean = mm[l - 1]; a.mvar = mv[l - 1];
-            a.pre_in = pre + (size_t)(l - 1) * B * 64; a.part_in = part + (size_t)(l - 1) * GEN_WMAX * 128;
-            a.stats_in = stats + (size_t)(l - 1) * 128;
+            a.pre_in = ws.pre(l - 1); a.part_in = ws.part(l - 1); a.stats_in = ws.stats(l - 1);
             a.bstat = bstat ? bstat + (size_t)(l - 1) * 2 * p.nh : nullptr;
         } else {
             a.z = z;
         }
-        if (l < nl - 1) { a.pre_out = pre + (size_t)l * B * 64; a.part_out = part + (size_t)l * GEN_WMAX * 128; }
+        if (l < nl - 1) { a.pre_out = ws.pre(l); a.part_out = ws.part(l); }
         else a.x = x;
         a.l = l; a.nlayers = nl; a.nh = p.nh; a.B = B; a.W = W; a.chunk = chunk; a.train = train; a.eps = eps;
         hipLaunchKernelGGL(gen_fwd_kernel, dim3(cgs_ceil_div(W, 4)), dim3(256), 0, st, a);
@@ -720,44 +637,40 @@ static int gen_forward(const MlpParams& p, const float* const* gamma, const floa
 extern "C" {
 
 size_t cgs_mlp2d_gen_ws_bytes(int B, int nlayers, int with_backward) {
-    if (B <= 0 || nlayers < 2 || nlayers > MLP_MAX_LAYERS) return 0;
+    if (B <= 0 || nlayers < 2 || nlayers > MLP2D_MAX_LAYERS) return 0;
     return gen_ws_floats(B, nlayers, with_backward) * sizeof(float);
 }
 
 int cgs_mlp2d_gen_fwd(const float* const* w, const float* const* b, const float* const* gamma, const float* const* beta,
                       float* const* moving_mean, float* const* moving_variance, int nlayers, int nhidden, const float* z, float* x, int B,
                       int is_training, float eps, float* batch_stats, void* ws, size_t ws_bytes, void* stream) {
-    MlpParams p;
-    int rc = mlp_fill(p, w, b, nlayers, nhidden, 64, "mlp2d_gen_fwd");
+    int rc = mlp2d_check_net("mlp2d_gen_fwd", w, b, nlayers, nhidden, 1, MLP2D_NARROW_MAX_NH);
     if (rc) return rc;
     if (!x) return cgs_set_error(CGS_EINVAL, "mlp2d_gen_fwd: null output");
     rc = mlp2d_check_gen("mlp2d_gen_fwd", gamma, beta, moving_mean, moving_variance, nlayers, z, B, INT_MAX, is_training != 0, eps,
                          gen_ws_floats(B, nlayers, 0) * sizeof(float), ws, ws_bytes);
     if (rc) return rc;
-    return gen_forward(p, gamma, beta, moving_mean, moving_variance, z, x, B, is_training != 0, eps, is_training ? batch_stats : nullptr,
-                       (float*)ws, (hipStream_t)stream);
+    return gen_forward(mlp2d_params(w, b, nlayers, nhidden), gamma, beta, moving_mean, moving_variance, z, x, B, is_training != 0, eps,
+                       is_training ? batch_stats : nullptr, GenWs(ws, B, nlayers), (hipStream_t)stream);
 }
 
 int cgs_mlp2d_g_step(float* const* w, float* const* b, const float* const* gamma, const float* const* beta, float* const* moving_mean,
                      float* const* moving_variance, int nlayers, int nhidden, const float* z, const float* grad_plugin, int B, float eps,
                      float lr, float* const* gw, float* const* gb, float* x, void* ws, size_t ws_bytes, void* stream) {
-    MlpParams p;
-    int rc = mlp_fill(p, (const float* const*)w, (const float* const*)b, nlayers, nhidden, 64, "mlp2d_g_step");
+    int rc = mlp2d_check_net("mlp2d_g_step", (const float* const*)w, (const float* const*)b, nlayers, nhidden, 1, MLP2D_NARROW_MAX_NH);
     if (rc) return rc;
     if (!grad_plugin) return cgs_set_error(CGS_EINVAL, "mlp2d_g_step: null grad_plugin");
     rc = mlp2d_check_gen("mlp2d_g_step", gamma, beta, moving_mean, moving_variance, nlayers, z, B, INT_MAX, 1, eps,
                          gen_ws_floats(B, nlayers, 1) * sizeof(float), ws, ws_bytes);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    rc = gen_forward(p, gamma, beta, moving_mean, moving_variance, z, x, B, 1, eps, nullptr, (float*)ws, st);
+    const GenWs s(ws, B, nlayers);
+    rc = gen_forward(mlp2d_params((const float* const*)w, (const float* const*)b, nlayers, nhidden), gamma, beta, moving_mean, moving_variance, z, x, B,
+                     1, eps, nullptr, s, st);
     if (rc) return rc;
-    const int nl = nlayers, H = nl - 1;
+    const int nl = nlayers;
     int W, chunk;
     gen_plan(B, W, chunk);
-    float* pre = (float*)ws;
-    float* part = pre + (size_t)H * B * 64;
-    float* stats = part + (size_t)H * GEN_WMAX * 128;
-    float* dbuf = stats + (size_t)H * 128;
     // top: output -> layer nl-2; then layer u -> u-1 for u = nl-2 .. 1; then layer 0 alone (its da)
     for (int u = nl - 1; u >= 0; --u) {
         GenBwd a = {};
@@ -765,25 +678,20 @@ int cgs_mlp2d_g_step(float* const* w, float* const* b, const float* const* gamma
         a.w_up = w[u];
         if (a.top) a.gplug = grad_plugin;
         else {
-            a.part_u = part + (size_t)u * GEN_WMAX * 128; a.pre_u = pre + (size_t)u * B * 64; a.stats_u = stats + (size_t)u * 128;
-            a.dbuf_u = dbuf + (size_t)u * B * 64;
+            a.part_u = s.part(u); a.pre_u = s.pre(u); a.stats_u = s.stats(u); a.dbuf_u = s.dbuf(u);
         }
         if (a.has_low) {
             const int l = u - 1;
-            a.pre_l = pre + (size_t)l * B * 64; a.stats_l = stats + (size_t)l * 128; a.gamma_l = gamma[l]; a.beta_l = beta[l];
-            a.dbuf_l = dbuf + (size_t)l * B * 64; a.part_l = part + (size_t)l * GEN_WMAX * 128;
+            a.pre_l = s.pre(l); a.stats_l = s.stats(l); a.gamma_l = gamma[l]; a.beta_l = beta[l]; a.dbuf_l = s.dbuf(l); a.part_l = s.part(l);
         }
         a.nh = nhidden; a.B = B; a.W = W; a.chunk = chunk;
         hipLaunchKernelGGL(gen_bwd_kernel, dim3(cgs_ceil_div(W, 4)), dim3(256), 0, st, a);
         CGS_CHECK_LAUNCH("mlp2d_gen_bwd");
     }
     GenGrad q = {};
-    for (int l = 0; l < nl; ++l) {
-        q.w[l] = w[l]; q.b[l] = b[l];
-        q.gw[l] = gw ? gw[l] : nullptr; q.gb[l] = gb ? gb[l] : nullptr;
-        if (l < nl - 1) { q.gamma[l] = gamma[l]; q.beta[l] = beta[l]; }
-    }
-    q.z = z; q.gplug = grad_plugin; q.pre = pre; q.stats = stats; q.dbuf = dbuf;
+    q.v = mlp2d_vars(w, b, gw, gb, nl);
+    for (int l = 0; l < nl - 1; ++l) { q.gamma[l] = gamma[l]; q.beta[l] = beta[l]; }
+    q.z = z; q.gplug = grad_plugin; q.pre = s.pre(0); q.stats = s.stats(0); q.dbuf = s.dbuf(0);
     q.nlayers = nl; q.nh = nhidden; q.B = B; q.lr = lr;
     hipLaunchKernelGGL(gen_grad_kernel, dim3(nl), dim3(1024), 0, st, q);
     CGS_CHECK_LAUNCH("mlp2d_gen_grad");

@@ -1,20 +1,16 @@
-// What the kernels of the wide 2-D nets (64 < nhidden <= 256) share, each piece stated once:
+// What the kernels of the wide 2-D nets (64 < nhidden <= 256) share, each piece stated once (what the 64-unit
+// kernels share with them -- the net's pointers, the refiner's rule, xhat / bn_relu -- is in mlp2d_shared.h):
 //   the tile      the head of every tile kernel's LDS image (H, slab), the hidden -> hidden pass on the fp32 MFMA, the tile-size rule, the
 //                 launch of a tile kernel, and the walks every net takes through H: first layer, 4-lanes-per-row product, top gradient, H -> memory
-//   batch norm    xhat and relu(gamma xhat + beta), the (mean, rstd, gamma, beta) row, the batched walk over row-group partials
+//   batch norm    the (mean, rstd, gamma, beta) row and xhat / relu(gamma xhat + beta) on it, the batched walk over row-group partials
 //   gradients     the sample chunk, the dW product of a hidden -> hidden layer, the 16-in-flight column sums, the update kernel
 // The layout is described at the top of mlp2d_wide.hip.  mlp2d_wide.hip (score, refine) and mlp2d_wide_train.hip (D step) are the
 // discriminator; mlp2d_wide_gen.hip (forward) and mlp2d_wide_gstep.hip (G step) the generator.
 #pragma once
-#include "cgs_internal.h"
-#include "mlp2d_check.h"
+#include "mlp2d_shared.h"
 
-#define MLPW_MAX_LAYERS 6
-#define MLPW_MIN_NH 65
-#define MLPW_MAX_NH 256
 #define MLPW_THREADS 256
 #define MLPW_MAX_CHUNKS 16
-#define MLPW_PBATCH 16          // row-group partials fetched per round trip: their consumers are serial chains, their loads need not be
 
 // Sample chunk of the weight-gradient products (mlp2d_wide_train.hip, mlp2d_wide_gstep.hip): a function of the batch alone, at most
 // MLPW_MAX_CHUNKS chunks, a multiple of 128 samples
@@ -30,7 +26,7 @@ static int mlpw_wgrad_blocks(int nlayers, int nhp, int nchunks) {
 //   [(nl-1) nhp (db_l) | 2 nhp (dW_0) | nout nhp (dW_last, by column) | 4 (db_last [nout], then what the step adds: the D step's two loss sums)]
 static int mlpw_small_stride(int nlayers, int nhp, int nout) { return (nlayers + 1 + nout) * nhp + 4; }
 
-static bool mlpw_gen_shape_ok(int nlayers, int nhidden) { return mlp2d_shape_ok(nlayers, nhidden, MLPW_MIN_NH, MLPW_MAX_NH); }
+static bool mlpw_gen_shape_ok(int nlayers, int nhidden) { return mlp2d_shape_ok(nlayers, nhidden, MLP2D_WIDE_MIN_NH, MLP2D_MAX_NH); }
 
 // Workspace floats of the generator's training forward (mlp2d_wide_gen.hip: pre | part | stats), the first bytes of the G step's
 static size_t genw_ws_floats(int B, int nlayers, int nhp) {
@@ -38,12 +34,6 @@ static size_t genw_ws_floats(int B, int nlayers, int nhp) {
 }
 
 typedef float mlpw_f16 __attribute__((ext_vector_type(16)));
-
-struct MlpWParams {
-    const float* w[MLPW_MAX_LAYERS];   // layer l: [din_l][dout_l] row-major
-    const float* b[MLPW_MAX_LAYERS];
-    int nlayers, nh, nhp;              // nhp = nh rounded up to 32
-};
 
 // The head of every tile kernel's LDS image; each kernel family appends its own rows (MlpWLds below, GenWLds, GswLds)
 struct MlpWTileLds {
@@ -84,7 +74,7 @@ static size_t mlpw_smem(int T, int nlayers, int nhp) {
     return (mlpw_tile_floats(T, nhp) + (size_t)(nlayers - 1) * T * (nhp / 32) + 3 * nhp + 2 * T) * sizeof(float);
 }
 
-__device__ __forceinline__ void mlpw_load(const MlpWParams& p, const MlpWLds& L) {
+__device__ __forceinline__ void mlpw_load(const Mlp2dParams& p, const MlpWLds& L) {
     for (int j = threadIdx.x; j < p.nhp; j += MLPW_THREADS) {
         const bool in = j < p.nh;
         const int q = hpos(j);
@@ -278,7 +268,7 @@ __device__ __forceinline__ void mlpw_store_h(const MlpWTileLds& L, int nhp, floa
 
 // One evaluation for the tile's points L.xs: logit and d logit / dx of row tid >> 2 in every thread tid < 4 T (4 lanes per row).
 template <int T>
-__device__ __forceinline__ void mlpw_eval(const MlpWParams& p, const MlpWLds& L, float& logit, float& dldx0, float& dldx1) {
+__device__ __forceinline__ void mlpw_eval(const Mlp2dParams& p, const MlpWLds& L, float& logit, float& dldx0, float& dldx1) {
     const int nh = p.nh, nhp = p.nhp, nl = p.nlayers, MW = T * (nhp >> 5);      // MW: words of one layer's masks
     const bool own = threadIdx.x < 4 * T;
     __syncthreads();              // xs (and, on the first call, w1p / wlp) written; the previous evaluation's reads of H done
@@ -301,19 +291,12 @@ __device__ __forceinline__ void mlpw_eval(const MlpWParams& p, const MlpWLds& L,
     }
 }
 
-__device__ __forceinline__ float mlpw_sigmoid(float v) { return v >= 0.f ? 1.f / (1.f + expf(-v)) : expf(v) / (1.f + expf(v)); }
-
 // ---- batch norm on load (the generator) -----------------------------------------------------------------------------------------------------
 
-// The forward's xhat and h = relu(gamma xhat + beta).  Whatever recomputes an activation or a ReLU decision from a stored pre-activation
-// calls these two, so a decision (mlpw_bn_relu(..) > 0) never disagrees with the forward's.
-__device__ __forceinline__ float mlpw_xhat(float a, float mean, float rstd) { return (a - mean) * rstd; }
-__device__ __forceinline__ float mlpw_bn_relu(float xhat, float gamma, float beta) { return fmaxf(fmaf(xhat, gamma, beta), 0.f); }
-
 // bn [4][nhp]: (mean, rstd, gamma, beta) of a BN layer, unit j at index j
-__device__ __forceinline__ float mlpw_bn_xhat(float a, const float* bn, int nhp, int j) { return mlpw_xhat(a, bn[j], bn[nhp + j]); }
+__device__ __forceinline__ float mlpw_bn_xhat(float a, const float* bn, int nhp, int j) { return mlp2d_xhat(a, bn[j], bn[nhp + j]); }
 __device__ __forceinline__ float mlpw_bn_apply(float a, const float* bn, int nhp, int j) {
-    return mlpw_bn_relu(mlpw_bn_xhat(a, bn, nhp, j), bn[2 * nhp + j], bn[3 * nhp + j]);
+    return mlp2d_bn_relu(mlpw_bn_xhat(a, bn, nhp, j), bn[2 * nhp + j], bn[3 * nhp + j]);
 }
 
 // thread j < nhp: unit j's entries of bn.  A padded unit has no gamma or beta to read and takes zeros; its mean and rstd come in as 0.
@@ -323,17 +306,17 @@ __device__ __forceinline__ void mlpw_bn_row(float* bn, int nh, int nhp, int j, f
     bn[j] = mean; bn[nhp + j] = rstd; bn[2 * nhp + j] = in ? gamma[j] : 0.f; bn[3 * nhp + j] = in ? beta[j] : 0.f;
 }
 
-// Unit j's row-group partials part [G][NP][nhp], MLPW_PBATCH groups' loads in flight, handed to use(g, v[NP]) in ascending group order
+// Unit j's row-group partials part [G][NP][nhp], MLP2D_PBATCH groups' loads in flight, handed to use(g, v[NP]) in ascending group order
 template <int NP, class Use>
 __device__ __forceinline__ void mlpw_walk_partials(const float* __restrict__ part, int G, int nhp, int j, Use&& use) {
-    for (int g0 = 0; g0 < G; g0 += MLPW_PBATCH) {
-        float v[MLPW_PBATCH][NP];
+    for (int g0 = 0; g0 < G; g0 += MLP2D_PBATCH) {
+        float v[MLP2D_PBATCH][NP];
 #pragma unroll
-        for (int q = 0; q < MLPW_PBATCH; ++q)
+        for (int q = 0; q < MLP2D_PBATCH; ++q)
 #pragma unroll
             for (int k = 0; k < NP; ++k) v[q][k] = g0 + q < G ? part[((size_t)(g0 + q) * NP + k) * nhp + j] : 0.f;
 #pragma unroll
-        for (int q = 0; q < MLPW_PBATCH; ++q)
+        for (int q = 0; q < MLP2D_PBATCH; ++q)
             if (g0 + q < G) use(g0 + q, v[q]);
     }
 }
@@ -411,22 +394,6 @@ __device__ __forceinline__ void mlpw_walk_samples(int s0, int s1, Load&& load, U
     }
 }
 
-struct MlpWVars {
-    float* w[MLPW_MAX_LAYERS];
-    float* b[MLPW_MAX_LAYERS];
-    float* gw[MLPW_MAX_LAYERS];      // may be null
-    float* gb[MLPW_MAX_LAYERS];
-};
-
-static MlpWVars mlpw_vars(float* const* w, float* const* b, float* const* gw, float* const* gb, int nlayers) {
-    MlpWVars q;
-    for (int l = 0; l < MLPW_MAX_LAYERS; ++l) {
-        q.w[l] = l < nlayers ? w[l] : nullptr; q.b[l] = l < nlayers ? b[l] : nullptr;
-        q.gw[l] = (gw && l < nlayers) ? gw[l] : nullptr; q.gb[l] = (gb && l < nlayers) ? gb[l] : nullptr;
-    }
-    return q;
-}
-
 // elements of the update of a net with `nout` outputs; the D step (nout = 1) appends its two loss sums
 static __host__ __device__ int mlpw_update_elems(int nlayers, int nh, int nout) { return (nlayers - 2) * nh * nh + (nlayers + 1 + nout) * nh + nout + (nout == 1 ? 2 : 0); }
 
@@ -434,7 +401,7 @@ static __host__ __device__ int mlpw_update_elems(int nlayers, int nh, int nout) 
 // element e of [hidden -> hidden dW: (nl-2) nh nh | dW_0: 2 nh | dW_last: NOUT nh | db_l: (nl-1) nh | db_last: NOUT | NOUT = 1: loss: 2],
 // the small ones where mlpw_small_stride puts them
 template <int NOUT>
-__global__ __launch_bounds__(256) void mlpw_update_kernel(MlpWVars q, const float* __restrict__ pw, const float* __restrict__ ps, int nchunks,
+__global__ __launch_bounds__(256) void mlpw_update_kernel(Mlp2dVars q, const float* __restrict__ pw, const float* __restrict__ ps, int nchunks,
                                                           int sstride, int nlayers, int nh, int nhp, float lr, float* __restrict__ loss) {
     const int nhid = nlayers - 1, nhh = nh * nh, nbig = (nlayers - 2) * nhh, tail = (nhid + 2 + NOUT) * nhp;
     const int total = mlpw_update_elems(nlayers, nh, NOUT);
@@ -477,7 +444,7 @@ __global__ __launch_bounds__(256) void mlpw_update_kernel(MlpWVars q, const floa
 }
 
 template <int NOUT>
-static int mlpw_update(const char* who, const MlpWVars& q, const float* pw, const float* ps, int nchunks, int nlayers, int nh, int nhp, float lr,
+static int mlpw_update(const char* who, const Mlp2dVars& q, const float* pw, const float* ps, int nchunks, int nlayers, int nh, int nhp, float lr,
                        float* loss, hipStream_t st) {
     const int total = mlpw_update_elems(nlayers, nh, NOUT);
     hipLaunchKernelGGL(mlpw_update_kernel<NOUT>, dim3(cgs_ceil_div(total, 256)), dim3(256), 0, st, q, pw, ps, nchunks,
@@ -521,9 +488,4 @@ static int mlpw_launch(int T, int B, size_t smem, const char* who, const char* w
 template <auto K32, auto K64, class... Args>
 static int mlpw_launch_tile(int T, int B, size_t smem, const char* who, const char* what, hipStream_t st, const Args&... args) {
     return T == 32 ? mlpw_launch<K32>(32, B, smem, who, what, st, args...) : mlpw_launch<K64>(64, B, smem, who, what, st, args...);
-}
-
-static void mlpw_fill(MlpWParams& p, const float* const* w, const float* const* b, int nlayers, int nh) {
-    for (int l = 0; l < MLPW_MAX_LAYERS; ++l) { p.w[l] = l < nlayers ? w[l] : nullptr; p.b[l] = l < nlayers ? b[l] : nullptr; }
-    p.nlayers = nlayers; p.nh = nh; p.nhp = cgs_round_up(nh, 32);
 }

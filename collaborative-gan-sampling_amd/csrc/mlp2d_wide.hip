@@ -25,7 +25,7 @@
 
 // sigmoid [B] and saliency [B,2] = inv_batch * (sigmoid - 1) * d logit / dx for the tile blockIdx.x
 template <int T>
-__global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void mlp_saliency_wide_kernel(MlpWParams p, const float* __restrict__ x, float* __restrict__ sig,
+__global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void mlp_saliency_wide_kernel(Mlp2dParams p, const float* __restrict__ x, float* __restrict__ sig,
                                                                          float* __restrict__ sal, int B, float inv_batch) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const MlpWLds L = mlpw_lds<T>(smem, p.nlayers, p.nhp);
@@ -37,16 +37,16 @@ __global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void mlp_saliency_wi
     mlpw_eval<T>(p, L, logit, d0, d1);
     const long s = row0 + (tid >> 2);
     if (tid < 4 * T && (tid & 3) == 0 && s < B) {
-        const float sg = mlpw_sigmoid(logit);
+        const float sg = sigmoid_stable(logit);
         sig[s] = sg;
         if (sal) { sal[2 * s] = inv_batch * (sg - 1.f) * d0; sal[2 * s + 1] = inv_batch * (sg - 1.f) * d1; }
     }
 }
 
-// refine2d_kernel of mlp2d.hip for a tile: the 4 lanes of a row all carry that sample's state; lane 0 of them posts the moved point
-// to xs and stores.  The update statements are refine2d_kernel's.
+// refine2d_kernel of mlp2d.hip for a tile: the 4 lanes of a row all carry that sample's Refine2dState; lane 0 of them posts the moved
+// point to xs and stores.
 template <int T>
-__global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void refine2d_wide_kernel(MlpWParams p, const float* __restrict__ x_in, float real_mean_host,
+__global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void refine2d_wide_kernel(Mlp2dParams p, const float* __restrict__ x_in, float real_mean_host,
                                                                      const float* __restrict__ real_mean_dev, float inv_batch, int steps,
                                                                      float rate, int method, float* __restrict__ best_x,
                                                                      float* __restrict__ best_step, float* __restrict__ traj, int B) {
@@ -60,48 +60,23 @@ __global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void refine2d_wide_k
     float x0 = 0.f, x1 = 0.f;
     if (own && s < B) { x0 = x_in[2 * s]; x1 = x_in[2 * s + 1]; }
     if (own && (tid & 3) == 0) { L.xs[2 * (tid >> 2)] = x0; L.xs[2 * (tid >> 2) + 1] = x1; }
-    float logit = 0.f, d0 = 0.f, d1 = 0.f, g0 = 0.f, g1 = 0.f, loss = 0.f;
-    float bx0 = x0, bx1 = x1, bl = 0.f, bs = 0.f;
-    float m0 = 0.f, m1 = 0.f, v0 = 0.f, v1 = 0.f, ll = 0.f;
-    // refine2d_kernel's loop turned so that the evaluation stands once in the code: pass i evaluates the point of step i (i = 0: the
-    // input), then takes step i + 1 from it
+    Refine2dState r(x0, x1);
+    float logit = 0.f, d0 = 0.f, d1 = 0.f;
     for (int i = 0; ; ++i) {
-#pragma clang fp contract(off)
         mlpw_eval<T>(p, L, logit, d0, d1);
-        const float sg = mlpw_sigmoid(logit);
-        g0 = inv_batch * (sg - 1.f) * d0; g1 = inv_batch * (sg - 1.f) * d1;
-        loss = real_mean - sg;                                     // refiner_cpu.py:28
-        if (i == 0) bl = loss;
-        else if (bl - loss > 0.f) { bl = loss; bx0 = x0; bx1 = x1; bs = (float)i; }              // refiner_cpu.py:58-61
-        if (traj && lead) { traj[((size_t)s * (steps + 1) + i) * 2] = x0; traj[((size_t)s * (steps + 1) + i) * 2 + 1] = x1; }
+        r.seen(i, logit, d0, d1, inv_batch, real_mean);
+        if (traj && lead) r.record(traj, (size_t)s, steps, i);
         if (i == steps) break;
-        if (method == 0) {
-            x0 -= rate * g0; x1 -= rate * g1;
-        } else if (method == 1) {
-            const float a0 = rate * g0, a1 = rate * g1;
-            m0 = i == 0 ? a0 : 0.9f * m0 + a0; m1 = i == 0 ? a1 : 0.9f * m1 + a1;
-            x0 -= m0; x1 -= m1;
-        } else {                                                   // ladam, policy.py:39-61
-            if (i == 0) { m0 = g0; m1 = g1; v0 = g0 * g0; v1 = g1 * g1; ll = loss; }
-            else {
-                m0 = 0.9f * m0 + 0.1f * g0; m1 = 0.9f * m1 + 0.1f * g1;        // (1. - 0.9) rounds to 0.1f in float32
-                v0 = 0.5f * v0 + 0.5f * (g0 * g0); v1 = 0.5f * v1 + 0.5f * (g1 * g1);
-                ll = 0.5f * ll + 0.5f * loss;
-            }
-            const float c = fmaxf(ll + 0.5f, 0.f);
-            const float rs = c * c;
-            x0 -= rate * m0 / (sqrtf(v0) + 1e-8f) * rs; x1 -= rate * m1 / (sqrtf(v1) + 1e-8f) * rs;
-        }
-        if (own && (tid & 3) == 0) { L.xs[2 * (tid >> 2)] = x0; L.xs[2 * (tid >> 2) + 1] = x1; }
+        r.step(i, method, rate);
+        if (own && (tid & 3) == 0) { L.xs[2 * (tid >> 2)] = r.x0; L.xs[2 * (tid >> 2) + 1] = r.x1; }
     }
-    if (lead) { best_x[2 * s] = bx0; best_x[2 * s + 1] = bx1; best_step[s] = bs; }
+    if (lead) { best_x[2 * s] = r.bx0; best_x[2 * s + 1] = r.bx1; best_step[s] = r.bs; }
 }
 
 // the callers (mlp2d.hip) have checked every argument; 64 < nh <= 256
 int cgs_mlp2d_wide_saliency(const float* const* w, const float* const* b, int nlayers, int nh, const float* x, float* sig, float* sal, int B,
                             float inv_batch, hipStream_t st) {
-    MlpWParams p;
-    mlpw_fill(p, w, b, nlayers, nh);
+    const Mlp2dParams p = mlp2d_params(w, b, nlayers, nh);
     const int T = mlpw_tile(B);
     return mlpw_launch_tile<mlp_saliency_wide_kernel<32>, mlp_saliency_wide_kernel<64>>(
         T, B, mlpw_smem(T, nlayers, p.nhp), "mlp2d_sigmoid_saliency", "mlp2d_sigmoid_saliency", st, p, x, sig, sal, B, inv_batch);
@@ -110,8 +85,7 @@ int cgs_mlp2d_wide_saliency(const float* const* w, const float* const* b, int nl
 int cgs_refine2d_wide(const float* const* w, const float* const* b, int nlayers, int nh, const float* x, float mean_host,
                       const float* mean_dev, float inv_batch, int steps, float rate, int method, float* best_x, float* best_step,
                       float* traj, int B, hipStream_t st) {
-    MlpWParams p;
-    mlpw_fill(p, w, b, nlayers, nh);
+    const Mlp2dParams p = mlp2d_params(w, b, nlayers, nh);
     const int T = mlpw_tile(B);
     return mlpw_launch_tile<refine2d_wide_kernel<32>, refine2d_wide_kernel<64>>(T, B, mlpw_smem(T, nlayers, p.nhp), "refine2d", "refine2d", st, p, x,
                                                                                 mean_host, mean_dev, inv_batch, steps, rate, method, best_x,

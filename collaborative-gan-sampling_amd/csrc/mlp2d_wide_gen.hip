@@ -44,9 +44,9 @@ struct GenWLayer {
 };
 
 struct GenWNet {                                       // inference mode: the whole net
-    const float* w[MLPW_MAX_LAYERS]; const float* b[MLPW_MAX_LAYERS];
-    const float* gamma[MLPW_MAX_LAYERS - 1]; const float* beta[MLPW_MAX_LAYERS - 1];
-    const float* mmean[MLPW_MAX_LAYERS - 1]; const float* mvar[MLPW_MAX_LAYERS - 1];
+    const float* w[MLP2D_MAX_LAYERS]; const float* b[MLP2D_MAX_LAYERS];
+    const float* gamma[MLP2D_MAX_LAYERS - 1]; const float* beta[MLP2D_MAX_LAYERS - 1];
+    const float* mmean[MLP2D_MAX_LAYERS - 1]; const float* mvar[MLP2D_MAX_LAYERS - 1];
     const float* z; float* x;
     int nlayers, nh, nhp, B;
     float eps;
@@ -244,7 +244,7 @@ int cgs_mlp2d_wide_gen_fwd(const float* const* w, const float* const* b, const f
                            float* const* moving_mean, float* const* moving_variance, int nlayers, int nhidden, const float* z, float* x,
                            int B, int is_training, float eps, float* batch_stats, void* ws, size_t ws_bytes, void* stream) {
     const char* who = "mlp2d_wide_gen_fwd";
-    int rc = mlp2d_check_net(who, w, b, nlayers, nhidden, MLPW_MIN_NH, MLPW_MAX_NH);
+    int rc = mlp2d_check_net(who, w, b, nlayers, nhidden, MLP2D_WIDE_MIN_NH, MLP2D_MAX_NH);
     if (rc) return rc;
     if (!x) return cgs_set_error(CGS_EINVAL, "%s: null output", who);
     const int train = is_training != 0, nhp = cgs_round_up(nhidden, 32), H = nlayers - 1, G = cgs_ceil_div(B, 32);

@@ -15,7 +15,7 @@
 // One workgroup of 4 waves per tile of T = mlpw_tile(B) samples in the first three kinds of launch.
 //
 // Epilogue for layer l (H holds dh_l): xhat = (a - mean) rstd and the ReLU decision gamma xhat + beta > 0 are recomputed from pre and stats
-// by mlpw_xhat and mlpw_bn_relu, the forward's own functions, so a mask never disagrees with the forward's; dxhat = decision ? dh gamma : 0 goes to dbuf
+// by mlp2d_xhat and mlp2d_bn_relu, the forward's own functions, so a mask never disagrees with the forward's; dxhat = decision ? dh gamma : 0 goes to dbuf
 // [nl-1][B][nhp] in natural unit order (padded units: exact zeros; rows past B: not stored), and every group of 32 consecutive rows leaves
 // (sum dxhat, sum dxhat xhat) per unit, one thread per (group, unit) walking the rows in ascending order: the forward's groups.
 // Launch u adds the ceil(B / 32) partials of layer u in ascending group order, one unit per thread, and overwrites dxhat_u with da_u in place.
@@ -27,7 +27,7 @@
 // forward's xhat.
 //
 // h_{l-1} = relu(BN(a_{l-1})) is NOT stored: the weight-gradient launch recomputes it on load from pre and stats (a lane's column is fixed,
-// so mean, rstd, gamma, beta are four registers per column: GswBnCol), again by mlpw_xhat and mlpw_bn_relu.
+// so mean, rstd, gamma, beta are four registers per column: GswBnCol), again by mlp2d_xhat and mlp2d_bn_relu.
 //
 // Determinism: groups of 32 rows and chunks of mlpw_chunk(B) samples are functions of B alone; every sum walks its terms in ascending
 // order; the MFMA chains are k-ordered.  So every output is a function of the inputs and B alone, not of T or of the CU count.  No atomics.
@@ -105,7 +105,7 @@ __device__ __forceinline__ void gsw_load_up(const GswLayer& a, float* up) {
 
 // tf FusedBatchNormGrad, training: da = rstd (dxhat - mean(dxhat) - xhat mean(dxhat xhat)), xhat the forward's, centred (see the top)
 __device__ __forceinline__ float gsw_da(float a, float dx, const float* up, int nhp, int j) {
-    const float ru = up[nhp + j], xh = mlpw_xhat(a, up[j], ru);
+    const float ru = up[nhp + j], xh = mlp2d_xhat(a, up[j], ru);
     return ru * (dx - up[2 * nhp + j] - (xh - up[4 * nhp + j]) * up[3 * nhp + j]);
 }
 
@@ -136,7 +136,7 @@ __device__ __forceinline__ void gsw_epilogue(const GswLayer& a, const GswLds& L,
         float dx = 0.f, xh = 0.f;
         if (row < rows && j < nh) {
             xh = mlpw_bn_xhat(a.pre_l[(size_t)(row0 + row) * nhp + j], L.bn, nhp, j);
-            dx = mlpw_bn_relu(xh, L.bn[2 * nhp + j], L.bn[3 * nhp + j]) > 0.f ? *hp * L.bn[2 * nhp + j] : 0.f;      // the forward's h > 0
+            dx = mlp2d_bn_relu(xh, L.bn[2 * nhp + j], L.bn[3 * nhp + j]) > 0.f ? *hp * L.bn[2 * nhp + j] : 0.f;      // the forward's h > 0
         }
         *hp = dx; X[row * nhp + j] = xh;
         if (row < rows) a.dbuf_l[(size_t)(row0 + row) * nhp + j] = dx;
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(MLPW_THREADS) void gsw_first_kernel(GswLayer a) {
 
 struct GswGrad {
     const float* pre; const float* stats; const float* dbuf;        // [H][B][nhp], [H][2][nhp], [H][B][nhp] (da)
-    const float* gamma[MLPW_MAX_LAYERS - 1]; const float* beta[MLPW_MAX_LAYERS - 1];
+    const float* gamma[MLP2D_MAX_LAYERS - 1]; const float* beta[MLP2D_MAX_LAYERS - 1];
     const float* z; const float* gplug;
     float* pw; float* ps;
     int nlayers, nh, nhp, B, chunk, nchunks, sstride;
@@ -221,7 +221,7 @@ struct GswBnCol {
         in = on && col < q.nh;
         m = in ? S[col] : 0.f; r = in ? S[q.nhp + col] : 0.f; g = in ? q.gamma[l][col] : 0.f; e = in ? q.beta[l][col] : 0.f;
     }
-    __device__ __forceinline__ float h(float a) const { return mlpw_bn_relu(mlpw_xhat(a, m, r), g, e); }
+    __device__ __forceinline__ float h(float a) const { return mlp2d_bn_relu(mlp2d_xhat(a, m, r), g, e); }
 };
 
 // blocks [0, nmfma): mlpw_wgrad_mfma, the A fragment h = relu(BN(a)) recomputed from the pre-activations on load.
@@ -288,7 +288,7 @@ int cgs_mlp2d_wide_g_step(float* const* w, float* const* b, const float* const* 
                           float* const* moving_variance, int nlayers, int nhidden, const float* z, const float* grad_plugin, int B, float eps,
                           float lr, float* const* gw, float* const* gb, float* x, void* ws, size_t ws_bytes, void* stream) {
     const char* who = "mlp2d_wide_g_step";
-    int rc = mlp2d_check_net(who, (const float* const*)w, (const float* const*)b, nlayers, nhidden, MLPW_MIN_NH, MLPW_MAX_NH);
+    int rc = mlp2d_check_net(who, (const float* const*)w, (const float* const*)b, nlayers, nhidden, MLP2D_WIDE_MIN_NH, MLP2D_MAX_NH);
     if (rc) return rc;
     if (!grad_plugin) return cgs_set_error(CGS_EINVAL, "%s: null grad_plugin", who);
     const int nl = nlayers, nhp = cgs_round_up(nhidden, 32), H = nl - 1, G = cgs_ceil_div(B, 32);
@@ -340,7 +340,7 @@ int cgs_mlp2d_wide_g_step(float* const* w, float* const* b, const float* const* 
     const int nmfma = mlpw_wgrad_blocks(nl, nhp, q.nchunks);
     hipLaunchKernelGGL(gsw_wgrad_kernel, dim3(nmfma + q.nchunks * H), dim3(MLPW_THREADS), 0, st, q, nmfma);
     CGS_CHECK_LAUNCH(who);
-    return mlpw_update<2>(who, mlpw_vars(w, b, gw, gb, nl), pw, ps, q.nchunks, nl, nhidden, nhp, lr, nullptr, st);
+    return mlpw_update<2>(who, mlp2d_vars(w, b, gw, gb, nl), pw, ps, q.nchunks, nl, nhidden, nhp, lr, nullptr, st);
 }
 
 }  // extern "C"

@@ -57,7 +57,7 @@ static MlpWTrainWs mlpw_train_ws(float* ws, int Bt, int nlayers, int nhp) {
 }
 
 template <int T>
-__global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void mlpw_train_kernel(MlpWParams p, const float* __restrict__ x, int B, int part0,
+__global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void mlpw_train_kernel(Mlp2dParams p, const float* __restrict__ x, int B, int part0,
                                                                   float target, float scale, MlpWTrainWs ws) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const MlpWLds L = mlpw_lds<T>(smem, p.nlayers, p.nhp);
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(MLPW_THREADS, T == 32 ? 2 : 1) void mlpw_train_kern
         float v[1];
         mlpw_rowdot<1>(L, L.wlp, nhp, v);
         const float logit = v[0] + p.b[nl - 1][0];
-        const float seed = scale * (mlpw_sigmoid(logit) - target);        // d (scale * BCE(logit, target)) / d logit
+        const float seed = scale * (sigmoid_stable(logit) - target);        // d (scale * BCE(logit, target)) / d logit
         if ((tid & 3) == 0) {
             L.xs[row] = seed;                                              // the points are spent: xs carries the seeds to the top gradient
             if (row < rows) {
@@ -160,24 +160,34 @@ __global__ __launch_bounds__(MLPW_THREADS) void mlpw_wgrad_kernel(MlpWTrainWs ws
     }
 }
 
-size_t cgs_mlp2d_wide_train_ws(int Bt, int nlayers, int nh) { return mlpw_train_ws_floats(Bt, nlayers, cgs_round_up(nh, 32)) * sizeof(float); }
+extern "C" {
 
-// the caller (mlp2d.hip) has checked every argument and the workspace size; 64 < nh <= 256
-int cgs_mlp2d_wide_train(float* const* w, float* const* b, int nlayers, int nh, const float* real, int B_real, const float* fake, int B_fake,
-                         float lr, float* const* gw, float* const* gb, float* loss, void* ws_, hipStream_t st) {
-    MlpWParams p;
-    mlpw_fill(p, (const float* const*)w, (const float* const*)b, nlayers, nh);
+size_t cgs_mlp2d_wide_train_ws_bytes(int B_total, int nlayers, int nhidden) {
+    if (B_total <= 0 || !mlp2d_shape_ok(nlayers, nhidden, MLP2D_WIDE_MIN_NH, MLP2D_MAX_NH)) return 0;
+    return mlpw_train_ws_floats(B_total, nlayers, cgs_round_up(nhidden, 32)) * sizeof(float);
+}
+
+int cgs_mlp2d_wide_d_step(float* const* w, float* const* b, int nlayers, int nhidden, const float* real, int B_real, const float* fake,
+                          int B_fake, float lr, float* const* gw, float* const* gb, float* loss, void* ws_, size_t ws_bytes, void* stream) {
+    int rc = mlp2d_check_net("mlp2d_wide_d_step", (const float* const*)w, (const float* const*)b, nlayers, nhidden, MLP2D_WIDE_MIN_NH, MLP2D_MAX_NH);
+    if (rc) return rc;
+    if (B_real <= 0 || B_fake <= 0 || (long)B_real + B_fake > (1 << 24) || !real || !fake) return cgs_set_error(CGS_EINVAL, "mlp2d_wide_d_step: bad argument");
+    const size_t need = cgs_mlp2d_wide_train_ws_bytes(B_real + B_fake, nlayers, nhidden);
+    if (!ws_ || ws_bytes < need) return cgs_set_error(CGS_EWORKSPACE, "mlp2d_wide_d_step: workspace %zu < %zu bytes", ws_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    const Mlp2dParams p = mlp2d_params((const float* const*)w, (const float* const*)b, nlayers, nhidden);
     const int Bt = B_real + B_fake, nhp = p.nhp, nhid = nlayers - 1;
     const MlpWTrainWs ws = mlpw_train_ws((float*)ws_, Bt, nlayers, nhp);
     for (int part = 0; part < 2; ++part) {      // real rows (target 1) then fake rows (target 0); each loss term is a MEAN
         const int B = part ? B_fake : B_real, part0 = part ? B_real : 0, T = mlpw_tile(B);
-        const int rc = mlpw_launch_tile<mlpw_train_kernel<32>, mlpw_train_kernel<64>>(T, B, mlpw_smem(T, nlayers, nhp), "mlp2d_wide_d_step", "mlpw_train",
-                                                                                      st, p, part ? fake : real, B, part0, part ? 0.f : 1.f,
-                                                                                      1.f / (float)B, ws);
+        rc = mlpw_launch_tile<mlpw_train_kernel<32>, mlpw_train_kernel<64>>(T, B, mlpw_smem(T, nlayers, nhp), "mlp2d_wide_d_step", "mlpw_train", st,
+                                                                                p, part ? fake : real, B, part0, part ? 0.f : 1.f, 1.f / (float)B, ws);
         if (rc) return rc;
     }
     const int nmfma = mlpw_wgrad_blocks(nlayers, nhp, ws.nchunks);
     hipLaunchKernelGGL(mlpw_wgrad_kernel, dim3(nmfma + ws.nchunks * nhid), dim3(MLPW_THREADS), 0, st, ws, nlayers, nhp, nmfma, real, B_real, fake);
     CGS_CHECK_LAUNCH("mlpw_wgrad");
-    return mlpw_update<1>("mlpw_update", mlpw_vars(w, b, gw, gb, nlayers), ws.pw, ws.ps, ws.nchunks, nlayers, nh, nhp, lr, loss, st);
+    return mlpw_update<1>("mlpw_update", mlp2d_vars(w, b, gw, gb, nlayers), ws.pw, ws.ps, ws.nchunks, nlayers, nhidden, nhp, lr, loss, st);
 }
+
+}  // extern "C"
