@@ -182,19 +182,10 @@ int cgs_convt_quad_launch(const CgsLayer& L, int B, const float* in, const float
 int cgs_convt_smalln_launch(const CgsLayer& L, int B, const float* in, const float* w, const float* bias,
                             float* out, int epilogue, hipStream_t s);
 
-// fused epilogue math shared by the conv-family kernels (device code only)
+// fused epilogue math shared by the conv-family kernels (device code only): the element epilogue of smallc.h with ocml's tanhf, every mode
 #ifdef __HIPCC__
-__device__ __forceinline__ float epilogue_apply(float v, int mode, float a, float b, float aux) {
-    switch (mode) {
-        case CGS_EPI_LRELU: return fmaxf(v, 0.2f * v);
-        case CGS_EPI_AFFINE_RELU: return fmaxf(fmaf(a, v, b), 0.f);
-        case CGS_EPI_TANH: return tanhf(v);
-        case CGS_EPI_RELU_BWD_AFFINE: return aux > 0.f ? v * a : 0.f;
-        case CGS_EPI_LRELU_BWD: return aux > 0.f ? v : 0.2f * v;
-        case CGS_EPI_TANH_BWD: return v * (1.f - aux * aux);
-        default: return v;
-    }
-}
+#include "smallc.h"
+__device__ __forceinline__ float epilogue_apply(float v, int mode, float a, float b, float aux) { return epilogue_elem<EPI_TANHF>(v, mode, a, b, aux); }
 
 // The element arithmetic of norm + lrelu (bn.hip; the norm-backward statistics of igemm_epilogue.h), each formula once:
 //   y  = lrelu(fma(x, scale, shift))                     scale = gamma * invstd, shift = beta - mean * scale
@@ -270,6 +261,25 @@ __device__ __forceinline__ void refine_update1(float g, float rate, float alpha,
             smem_done_[smem_dev_] = true;                                                                               \
         }                                                                                                               \
     } while (0)
+
+// CGS_LAUNCH_T(kernel, (template, args), grid, block, smem, stream, kernel args...): launches kernel<template, args> and notes its name for
+// cgs_last_kernel() as rocprofv3 prints it, "kernel<template, args>" -- the argument list stands once, so the name cannot drift from the launch.
+#define CGS_TARGS_(...) __VA_ARGS__
+#define CGS_STR_(...) #__VA_ARGS__
+#define CGS_STR(...) CGS_STR_(__VA_ARGS__)
+#define CGS_LAUNCH_T(kernel, targs, grid, block, smem, stream, ...)                                                     \
+    do {                                                                                                                \
+        hipLaunchKernelGGL((kernel<CGS_TARGS_ targs>), grid, block, smem, stream, __VA_ARGS__);                         \
+        cgs_note_kernel(#kernel "<" CGS_STR(CGS_TARGS_ targs) ">");                                                     \
+    } while (0)
+
+// Persistent blocks, each a contiguous run of tiles (device side: block_run): ceil(tiles / slots) tiles a block, but never 2 or 3 -- a run
+// of >= 4 amortises what a block loads once, and a launch too small for that (< 4 tiles for each of 256 CUs) keeps one tile per block.
+static inline void cgs_persistent_run(long tiles, long slots, long* per, long* blocks) {
+    *per = (tiles + slots - 1) / slots;
+    if (*per < 4) *per = tiles >= 4 * 256 ? 4 : 1;
+    *blocks = (tiles + *per - 1) / *per;
+}
 
 // the 2-D discriminator at 64 < nhidden <= 256 (mlp2d_wide.hip); arguments already checked by the entry points of mlp2d.hip
 int cgs_mlp2d_wide_saliency(const float* const* w, const float* const* b, int nlayers, int nh, const float* x, float* sig, float* sal, int B,

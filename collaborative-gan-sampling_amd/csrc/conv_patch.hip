@@ -11,7 +11,6 @@
 #include "cgs_internal.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct PatchParams {
     const float* in;      // [B,Hin,Win,Cred]
@@ -31,6 +30,10 @@ struct PatchParams {
 
 static constexpr int TR = 8, TC = 16;      // output tile (rows x cols) = 128 GEMM rows
 static constexpr int PBN = 64;             // output channels per block
+// LDS and per-thread budgets, kernels and launcher alike
+static constexpr int LDE = 32 + 4;                       // floats per row of a wave's [32 rows][32 cols (+4)] epilogue staging tile
+static constexpr int STAGE_FLOATS = 4 * 32 * LDE;        // ... of the block's four waves
+static constexpr int PATCH_PLD = 10;                     // patch floats a thread of conv_patch_kernel stages: ceil(max patch floats (21 x 37 x 4 = 3108) / 256)
 
 __global__ void pack_patch_weights_kernel(const float* __restrict__ w, float* __restrict__ wk, int K, int Kp, int N, int Np) {
     const int total = Kp * Np;
@@ -45,7 +48,6 @@ __global__ void pack_patch_weights_kernel(const float* __restrict__ w, float* __
 template <int EPI>
 __device__ __forceinline__ void patch_rows(const PatchParams& p, const float* E, int b, int oy0, int ox0, int wm, int tm, int n, int rsub,
                                            int c4, f32x4 bias, f32x4 ea, f32x4 eb) {
-    constexpr int LDE = 32 + 4;
 #pragma unroll
     for (int it = 0; it < 4; ++it) {                   // 32 rows, 8 rows per pass (8 lanes x float4 per row)
         const int lrow = it * 8 + rsub;
@@ -80,24 +82,21 @@ __global__ __launch_bounds__(256, 2) void conv_patch_kernel(PatchParams p, int t
     float* Bs = smem;                                   // [Kp][PBN]
     float* Ps = smem + (size_t)p.Kp * PBN;               // [2][PH][pitch]
     int* koff_t = (int*)(Ps + (size_t)2 * patch_f);       // [Kp] patch offset of reduction index k
-    constexpr int LDE = 32 + 4;
     float* E = (float*)(koff_t + p.Kp) + (threadIdx.x >> 6) * 32 * LDE;     // this wave's [32 rows][32 cols (+4)] staging tile (half its rows at a time)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, h = lane >> 5, j = lane & 31;
 
     const int tiles_x = p.Wout / TC, tiles_y = p.Hout / TR;
     const int nblk_n = p.Np / PBN;
-    const int t_begin = blockIdx.x * tiles_per_block;
-    const int t_end = t_begin + tiles_per_block < tiles_total ? t_begin + tiles_per_block : tiles_total;
-    if (t_begin >= t_end) return;
+    int t_begin, t_end;
+    if (!block_run(tiles_per_block, tiles_total, t_begin, t_end)) return;
 
-    const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.in, 0, (int)((unsigned)p.B * (unsigned)p.Hin * (unsigned)p.Win * (unsigned)p.Cred * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.in, (unsigned)p.B * (unsigned)p.Hin * (unsigned)p.Win * (unsigned)p.Cred * 4u);
     const int rowf = p.PW * p.Cred;                      // valid floats per patch row
     const int rowlen = p.Win * p.Cred;
     // a patch row is one contiguous run of the NHWC image row.  The element -> (patch row, column) split of this thread's
     // loads is the same for every tile: done once
-    constexpr int PLD = 10;                               // ceil(max patch floats (21 x 37 x 4 = 3108) / 256) -> checked on the host
+    constexpr int PLD = PATCH_PLD;
     int l_pr[PLD], l_e[PLD];
     {
         const float inv_rowf = 1.0f / (float)rowf;
@@ -105,11 +104,10 @@ __global__ __launch_bounds__(256, 2) void conv_patch_kernel(PatchParams p, int t
 #pragma unroll
         for (int u = 0; u < PLD; ++u) {
             const int q = tid + 256 * u;
-            int pr = (int)((float)q * inv_rowf);          // q / rowf for q < 2^20 up to one off ...
-            if (pr * rowf > q) --pr;                       // ... fixed here
-            if ((pr + 1) * rowf <= q) ++pr;
+            int e;
+            const int pr = patch_split(q, rowf, inv_rowf, e);
             l_pr[u] = q < total ? pr : -1;
-            l_e[u] = q - pr * rowf;
+            l_e[u] = e;
         }
     }
     float pv[PLD];
@@ -128,7 +126,7 @@ __global__ __launch_bounds__(256, 2) void conv_patch_kernel(PatchParams p, int t
         _Pragma("unroll") for (int u = 0; u < PLD; ++u) {                                          \
             const int iy = iy0_ + l_pr[u], col = col0_ + l_e[u];                                   \
             const bool ok = l_pr[u] >= 0 && (unsigned)iy < (unsigned)p.Hin && (unsigned)col < (unsigned)rowlen; \
-            const unsigned off = ok ? (unsigned)(((b_) * p.Hin + iy) * rowlen + col) * 4u : 0xFFFFFFF0u; \
+            const unsigned off = ok ? (unsigned)(((b_) * p.Hin + iy) * rowlen + col) * 4u : BUFFER_OOB; \
             pv[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(in_rsrc, off, 0, 0)); \
         }                                                                                          \
     } while (0)
@@ -238,9 +236,7 @@ __global__ __launch_bounds__(256, 2) void conv_patch_kernel(PatchParams p, int t
         for (int tm = 0; tm < 2; ++tm) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) E[((r & 3) + 8 * (r >> 2) + 4 * h) * LDE + j] = acc[tm][r];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             if (n < p.N) {
                 switch (p.epilogue) {
                     case CGS_EPI_NONE: patch_rows<CGS_EPI_NONE>(p, E, b, oy0, ox0, wm, tm, n, rsub, c4, bias, ea, eb); break;
@@ -252,9 +248,7 @@ __global__ __launch_bounds__(256, 2) void conv_patch_kernel(PatchParams p, int t
                     default: patch_rows<CGS_EPI_TANH_BWD>(p, E, b, oy0, ox0, wm, tm, n, rsub, c4, bias, ea, eb); break;
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the next staging writes must not pass these reads
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
         }
         if (more) { b = nb_; oy0 = noy0; ox0 = nox0; n0 = nn0; }
     }
@@ -306,8 +300,7 @@ __device__ __forceinline__ void patch2_store(const PatchParams& p, __amdgpu_buff
 }
 
 // the same store with relu' / lrelu' taken from the sign mask: nw = lane L's un-shuffled word of pixel L of the wave's 4 x 16
-// pixels.  Register r of row tile tm is pixel 32 tm + (r & 3) + 8 (r >> 2) in lanes 0-31 and that + 4 in lanes 32-63, and a
-// lane's channel is its index in the half: {readlane(nw, pixel), readlane(nw, pixel + 4)} IS the 64-bit lane mask of "aux > 0".
+// pixels.  Register r of row tile tm is pixel 32 tm + (r & 3) + 8 (r >> 2) in lanes 0-31 and that + 4 in lanes 32-63 (sign_lane_positive).
 template <int EPI>
 __device__ __forceinline__ void patch2_store_signs(const PatchParams& p, __amdgpu_buffer_rsrc_t out_rsrc, const f32x16 (&acc)[2],
                                                    unsigned base, unsigned rowstride, float ea, unsigned nw) {
@@ -318,8 +311,7 @@ __device__ __forceinline__ void patch2_store_signs(const PatchParams& p, __amdgp
         for (int r = 0; r < 16; ++r) {
             const int row = (r & 3) + 8 * (r >> 2);
             const unsigned o = base + (unsigned)(2 * tm + row / TC) * rowstride + (unsigned)(row % TC) * pixb;
-            const unsigned lo = __builtin_amdgcn_readlane(nw, 32 * tm + row), hi = __builtin_amdgcn_readlane(nw, 32 * tm + row + 4);
-            const bool pos = __builtin_amdgcn_inverse_ballot_w64(((unsigned long long)hi << 32) | lo);
+            const bool pos = sign_lane_positive(nw, 32 * tm + row);
             const float v = acc[tm][r];
             const float y = EPI == CGS_EPI_RELU_BWD_AFFINE ? (pos ? v * ea : 0.f) : (pos ? v : 0.2f * v);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y), out_rsrc, o, 0, 0);
@@ -344,7 +336,6 @@ __global__ __launch_bounds__(256, AUXM == 1 ? 2 : 4) void conv_patch2_kernel(Pat
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int patch_f = p.PH * p.pitch;
     float* Ps = smem;                                    // [2][PH][pitch]
-    constexpr int LDE = 32 + 4;
     float* E = Ps + (size_t)2 * patch_f + (threadIdx.x >> 6) * 32 * LDE;     // AUXP: this wave's [32 rows][32 cols (+4)] staging tile
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, h = lane >> 5, j = lane & 31;
@@ -352,17 +343,14 @@ __global__ __launch_bounds__(256, AUXM == 1 ? 2 : 4) void conv_patch2_kernel(Pat
 
     const int tiles_x = p.Wout / TC, tiles_y = p.Hout / TR;
     const int tiles_per_n = p.B * tiles_x * tiles_y;     // tile id = n-tile * tiles_per_n + (image, tile row, tile col): a block's run
-    const int t_begin = blockIdx.x * tiles_per_block;    // of tiles stays inside one n-tile except at a boundary (weights reloaded there)
-    const int t_end = t_begin + tiles_per_block < tiles_total ? t_begin + tiles_per_block : tiles_total;
-    if (t_begin >= t_end) return;
+    int t_begin, t_end;                                  // of tiles stays inside one n-tile except at a boundary (weights reloaded there)
+    if (!block_run(tiles_per_block, tiles_total, t_begin, t_end)) return;
 
-    const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.in, 0, (int)((unsigned)p.B * (unsigned)p.Hin * (unsigned)p.Win * (unsigned)p.Cred * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.in, (unsigned)p.B * (unsigned)p.Hin * (unsigned)p.Win * (unsigned)p.Cred * 4u);
     const unsigned out_bytes = (unsigned)p.B * (unsigned)p.Hout * (unsigned)p.Wout * (unsigned)p.N * 4u;
-    const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, (int)out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t aux_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ep_aux ? p.ep_aux : p.out), 0, (int)out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t sg_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.aux_signs ? (const void*)p.aux_signs : (const void*)p.out), 0,
-                                                                             (int)(out_bytes >> 5), 0x00020000);     // one word per 32 floats
+    const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.out, out_bytes);
+    const __amdgpu_buffer_rsrc_t aux_rsrc = buffer_rsrc(p.ep_aux ? p.ep_aux : p.out, out_bytes);
+    const __amdgpu_buffer_rsrc_t sg_rsrc = buffer_rsrc(p.aux_signs ? (const void*)p.aux_signs : (const void*)p.out, out_bytes >> 5);     // one word per 32 floats
     const unsigned sg_plane_b = (unsigned)p.B * (unsigned)p.Hout * (unsigned)p.Wout * 4u;                            // bytes of one 32-channel plane
     const int rowf = p.PW * p.Cred;                      // valid floats per patch row
     const int rowlen = p.Win * p.Cred;
@@ -380,10 +368,8 @@ __global__ __launch_bounds__(256, AUXM == 1 ? 2 : 4) void conv_patch2_kernel(Pat
 #pragma unroll
         for (int u = 0; u < PLD; ++u) {
             const int q = tid + 256 * u;
-            int pr = (int)((float)q * inv_rowf);
-            if (pr * rowf > q) --pr;
-            if ((pr + 1) * rowf <= q) ++pr;
-            const int e = q - pr * rowf;
+            int e;
+            const int pr = patch_split(q, rowf, inv_rowf, e);
             l_dst[u] = q < total ? pr * p.pitch + e : -1;
             l_src[u] = (pr * rowlen + e) * 4;
             const unsigned f = q < total ? (unsigned)(pr < row_lo) | ((unsigned)(pr >= row_hi) << 1) | ((unsigned)(e < col_lo) << 2) | ((unsigned)(e >= col_hi) << 3) : 15u;
@@ -411,7 +397,7 @@ __global__ __launch_bounds__(256, AUXM == 1 ? 2 : 4) void conv_patch2_kernel(Pat
                                ((ox0_) == 0 ? 0x44444444u : 0u) | ((ox0_) == p.Wout - TC ? 0x88888888u : 0u) | 0u;   \
         const unsigned bad_ = (l_flags & edge_) | (l_flags & (l_flags >> 1) & (l_flags >> 2) & (l_flags >> 3) & 0x11111111u);   /* (all four flags: no element) */ \
         _Pragma("unroll") for (int u = 0; u < PLD; ++u) {                                          \
-            const unsigned off = ((bad_ >> (4 * u)) & 15u) == 0u ? (unsigned)(org_ + l_src[u]) : 0xFFFFFFF0u; \
+            const unsigned off = ((bad_ >> (4 * u)) & 15u) == 0u ? (unsigned)(org_ + l_src[u]) : BUFFER_OOB; \
             pv[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(in_rsrc, off, 0, 0)); \
         }                                                                                          \
     } while (0)
@@ -550,9 +536,7 @@ __global__ __launch_bounds__(256, AUXM == 1 ? 2 : 4) void conv_patch2_kernel(Pat
                 for (int tm = 0; tm < 2; ++tm) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) E[((r & 3) + 8 * (r >> 2) + 4 * h) * LDE + j] = acc[tm][r];
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_lds_sync();
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int lrow = q * 8 + rsub;
@@ -568,9 +552,7 @@ __global__ __launch_bounds__(256, AUXM == 1 ? 2 : 4) void conv_patch2_kernel(Pat
                             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, y), out_rsrc,
                                                                    ob + (unsigned)(2 * tm + lrow / TC) * rowstride + (unsigned)(lrow % TC) * (unsigned)p.N * 4u, 0, 0);
                     }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_lds_sync();
                 }
             } else if (nj < p.N) {
                 switch (p.epilogue) {
@@ -622,12 +604,12 @@ int cgs_conv_patch_ok(const CgsLayer& L, int epilogue) {
     (void)epilogue;
     return L.Cb <= 4 && L.sh == L.sw && (L.sh == 1 || L.sh == 2) && (L.Hs % TR) == 0 && (L.Ws % TC) == 0 && (L.Cs % 4) == 0 &&
            L.kh * L.kw * L.Cb <= 160 && L.kh <= 7 && L.kw <= 7 &&
-           (L.sh * (TR - 1) + L.kh) * (L.sh * (TC - 1) + L.kw) * L.Cb <= 10 * 256;
+           (L.sh * (TR - 1) + L.kh) * (L.sh * (TC - 1) + L.kw) * L.Cb <= PATCH_PLD * 256;
 }
 
 int cgs_conv_patch_T_ok(const CgsLayer& L) {
     return L.Cs <= 4 && L.sh == 1 && L.sw == 1 && (L.Hb % TR) == 0 && (L.Wb % TC) == 0 && (L.Cb % 4) == 0 &&
-           L.kh * L.kw * L.Cs <= 160 && L.kh <= 7 && L.kw <= 7 && ((TR - 1) + L.kh) * ((TC - 1) + L.kw) * L.Cs <= 10 * 256;
+           L.kh * L.kw * L.Cs <= 160 && L.kh <= 7 && L.kw <= 7 && ((TR - 1) + L.kh) * ((TC - 1) + L.kw) * L.Cs <= PATCH_PLD * 256;
 }
 
 size_t cgs_conv_patch_ws_floats(const CgsLayer& L, bool dirT) {
@@ -675,23 +657,20 @@ int cgs_conv_patch_launch(const CgsLayer& L, bool dirT, int B, const float* in, 
         }
         const bool auxp = epilogue >= CGS_EPI_RELU_BWD_AFFINE;
         const bool sgn = auxp && aux_signs != nullptr;
-        const size_t smem2 = ((size_t)2 * p.PH * p.pitch + ((auxp && !sgn) ? (size_t)4 * 32 * 36 : 0)) * sizeof(float);
+        const size_t smem2 = ((size_t)2 * p.PH * p.pitch + ((auxp && !sgn) ? (size_t)STAGE_FLOATS : 0)) * sizeof(float);
         CGS_SMEM_ATTR(96 * 1024, "conv_patch2", conv_patch2_kernel<5, 16, 15, 8, 0>);
         CGS_SMEM_ATTR(96 * 1024, "conv_patch2 (aux)", conv_patch2_kernel<5, 16, 15, 8, 1>);
         CGS_SMEM_ATTR(96 * 1024, "conv_patch2 (signs)", conv_patch2_kernel<5, 16, 15, 8, 2>);
-        if (smem2 > 96 * 1024 || p.PH * p.PW * p.Cred > 8 * 256) return cgs_set_error(CGS_EINVAL, "conv_patch: patch too large");
+        if (smem2 > 96 * 1024 || p.PH * p.PW * p.Cred > 8 * 256) return cgs_set_error(CGS_EINVAL, "conv_patch: patch too large");      // (8 = PLD, the fourth template argument)
         const long tiles2 = (long)B * (p.Hout / TR) * (p.Wout / TC) * (p.Np / PBN);
         if (tiles2 == 0) return CGS_OK;
         if (tiles2 > 0x7fffffffL) return cgs_set_error(CGS_EINVAL, "conv_patch: grid too large");
-        const long slots = (auxp && !sgn) ? 512 : 1024;         // persistent blocks: two (fp32 aux-prefetch form) or four per CU
-        long per2 = (tiles2 + slots - 1) / slots;
-        if (per2 < 4) per2 = tiles2 >= 4 * 256 ? 4 : 1;
-        const unsigned nblk2 = (unsigned)((tiles2 + per2 - 1) / per2);
-        if (sgn) hipLaunchKernelGGL((conv_patch2_kernel<5, 16, 15, 8, 2>), dim3(nblk2), dim3(256), smem2, s, p, (int)tiles2, (int)per2);
-        else if (auxp) hipLaunchKernelGGL((conv_patch2_kernel<5, 16, 15, 8, 1>), dim3(nblk2), dim3(256), smem2, s, p, (int)tiles2, (int)per2);
-        else hipLaunchKernelGGL((conv_patch2_kernel<5, 16, 15, 8, 0>), dim3(nblk2), dim3(256), smem2, s, p, (int)tiles2, (int)per2);
+        long per2, nblk2;
+        cgs_persistent_run(tiles2, (auxp && !sgn) ? 512 : 1024, &per2, &nblk2);       // two (fp32 aux-prefetch form) or four blocks per CU
+#define PATCH2_LAUNCH(AUXM_) CGS_LAUNCH_T(conv_patch2_kernel, (5, 16, 15, 8, AUXM_), dim3((unsigned)nblk2), dim3(256), smem2, s, p, (int)tiles2, (int)per2)
+        if (sgn) PATCH2_LAUNCH(2); else if (auxp) PATCH2_LAUNCH(1); else PATCH2_LAUNCH(0);
+#undef PATCH2_LAUNCH
         CGS_CHECK_LAUNCH("conv_patch2");
-        cgs_note_kernel(sgn ? "conv_patch2_kernel<5, 16, 15, 8, 2>" : auxp ? "conv_patch2_kernel<5, 16, 15, 8, 1>" : "conv_patch2_kernel<5, 16, 15, 8, 0>");
         return CGS_OK;
     }
     if (!prepacked) {
@@ -702,30 +681,28 @@ int cgs_conv_patch_launch(const CgsLayer& L, bool dirT, int B, const float* in, 
             hipLaunchKernelGGL(pack_patch_weights_kernel, dim3(cgs_ceil_div(p.Kp * p.Np, 256)), dim3(256), 0, s, w, ws, p.K, p.Kp, p.N, p.Np);
         CGS_CHECK_LAUNCH("pack_patch_weights");
     }
-    const size_t smem = ((size_t)p.Kp * PBN + (size_t)2 * p.PH * p.pitch + p.Kp + (size_t)4 * 32 * 36) * sizeof(float);
+    const size_t smem = ((size_t)p.Kp * PBN + (size_t)2 * p.PH * p.pitch + p.Kp + (size_t)STAGE_FLOATS) * sizeof(float);
     CGS_SMEM_ATTR(96 * 1024, "conv_patch", conv_patch_kernel<0, 1, 1>);
-    if (smem > 96 * 1024 || p.PH * p.PW * p.Cred > 10 * 256) return cgs_set_error(CGS_EINVAL, "conv_patch: patch too large");
+    if (smem > 96 * 1024 || p.PH * p.PW * p.Cred > PATCH_PLD * 256) return cgs_set_error(CGS_EINVAL, "conv_patch: patch too large");
     const long tiles = (long)B * (p.Hout / TR) * (p.Wout / TC) * (p.Np / PBN);
     if (tiles == 0) return CGS_OK;
     if (tiles > 0x7fffffffL) return cgs_set_error(CGS_EINVAL, "conv_patch: grid too large");
-    // persistent blocks: two per CU, each a contiguous run of tiles (>= 4, so the weight slab load is amortised);
-    // small launches keep one tile per block and simply fill the GPU
-    long per = (tiles + 511) / 512;
-    if (per < 4) per = tiles >= 4 * 256 ? 4 : 1;
-    const long blocks = (tiles + per - 1) / per;
+    // two blocks per CU; a run of >= 4 tiles amortises the weight slab load
+    long per, blocks;
+    cgs_persistent_run(tiles, 512, &per, &blocks);
     // the two fixed geometries of config 5: 7x7x3 stride 1 (RGB stem, and the backward-data of the RGB head), 4x4x3 stride 2 (PatchGAN stem)
+#define PATCH_LAUNCH(...) CGS_LAUNCH_T(conv_patch_kernel, (__VA_ARGS__), dim3((unsigned)blocks), dim3(256), smem, s, p, (int)tiles, (int)per)
     if (p.K == 147 && p.kw * p.Cred == 21 && p.pitch == 67) {
         CGS_SMEM_ATTR(96 * 1024, "conv_patch <147>", conv_patch_kernel<147, 21, 67>);
-        hipLaunchKernelGGL((conv_patch_kernel<147, 21, 67>), dim3((unsigned)blocks), dim3(256), smem, s, p, (int)tiles, (int)per);
-        cgs_note_kernel("conv_patch_kernel<147, 21, 67>");
+        PATCH_LAUNCH(147, 21, 67);
     } else if (p.K == 48 && p.kw * p.Cred == 12 && p.pitch == 103) {
         CGS_SMEM_ATTR(96 * 1024, "conv_patch <48>", conv_patch_kernel<48, 12, 103>);
-        hipLaunchKernelGGL((conv_patch_kernel<48, 12, 103>), dim3((unsigned)blocks), dim3(256), smem, s, p, (int)tiles, (int)per);
-        cgs_note_kernel("conv_patch_kernel<48, 12, 103>");
+        PATCH_LAUNCH(48, 12, 103);
     } else {
         hipLaunchKernelGGL((conv_patch_kernel<0, 1, 1>), dim3((unsigned)blocks), dim3(256), smem, s, p, (int)tiles, (int)per);
-        cgs_note_kernel("conv_patch_kernel");
+        cgs_note_kernel("conv_patch_kernel");      // (the general form goes by its bare name)
     }
+#undef PATCH_LAUNCH
     CGS_CHECK_LAUNCH("conv_patch");
     return CGS_OK;
 }

@@ -88,10 +88,8 @@ __global__ __launch_bounds__(256, 2) void conv_smalln_f_kernel(SmallNFParams p) 
     float* o = p.out + ((size_t)(b * p.H + oy0 + py) * p.W + ox0 + px) * N;
 #pragma unroll
     for (int n = 0; n < N; ++n) {
-        float v = (acc[n].x + acc[n].y) + (p.bias ? p.bias[n] : 0.f);
-        if (p.epilogue == CGS_EPI_TANH) v = tanhf(v);
-        else if (p.epilogue == CGS_EPI_LRELU) v = fmaxf(v, 0.2f * v);
-        o[n] = v;
+        const float v = (acc[n].x + acc[n].y) + (p.bias ? p.bias[n] : 0.f);
+        o[n] = epilogue_elem<EPI_TANHF, EPI_MODES_T_FWD>(v, p.epilogue, 1.f, 0.f, 0.f);
     }
 }
 

@@ -13,11 +13,7 @@
 // A fragments are read straight from global memory (each lane one float4 = 4 consecutive ci of its
 // row; the K order inside a 16-channel chunk is permuted identically for A and B so no shuffle is
 // needed); the packed weights (37 KB for 9 x 64 x 16) sit in LDS for the whole block.
-#include <stdio.h>
-
 #include "cgs_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct QuadParams {
     const float* in;     // [B,Hs,Ws,Cs]
@@ -106,12 +102,7 @@ __global__ __launch_bounds__(256) void convt_quad_mfma_kernel(QuadParams p) {
         // B fragment: k-quad (it*4 + g), column i
         const f32x4 fb = *(const f32x4*)(Bs + ((size_t)(it * 4 + g) * 16 + i) * 4);
 #pragma unroll
-        for (int t = 0; t < MT; ++t) {
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[t].x, fb.x, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[t].y, fb.y, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[t].z, fb.z, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[t].w, fb.w, acc[t], 0, 0, 0);
-        }
+        for (int t = 0; t < MT; ++t) mfma16x4(acc[t], a_cur[t], fb);
 #pragma unroll
         for (int t = 0; t < MT; ++t) a_cur[t] = a_nxt[t];
     }
@@ -135,12 +126,8 @@ __global__ __launch_bounds__(256) void convt_quad_mfma_kernel(QuadParams p) {
             const int rr = rem / p.Ws, cc = rem - rr * p.Ws;
             float v = acc[t][r] + bias;
             const size_t o = ((size_t)(b * 2 * p.Hs + 2 * rr + py) * (2 * p.Ws) + 2 * cc + px) * p.N + n;
-            if (p.epilogue == CGS_EPI_TANH) v = tanhf(v);
-            else if (p.epilogue == CGS_EPI_LRELU) v = fmaxf(v, 0.2f * v);
-            else if (p.epilogue == CGS_EPI_TANH_BWD) { const float y = p.ep_aux[o]; v *= (1.f - y * y); }
-            else if (p.epilogue == CGS_EPI_LRELU_BWD) v = p.ep_aux[o] > 0.f ? v : 0.2f * v;
-            else if (p.epilogue == CGS_EPI_RELU_BWD_AFFINE) v = p.ep_aux[o] > 0.f ? v * ea : 0.f;
-            p.out[o] = v;
+            const float y = p.epilogue >= CGS_EPI_RELU_BWD_AFFINE ? p.ep_aux[o] : 0.f;
+            p.out[o] = epilogue_elem<EPI_TANHF, EPI_MODES_T_FWD | EPI_MODES_BWD>(v, p.epilogue, ea, 0.f, y);
         }
 }
 
@@ -155,39 +142,39 @@ __global__ __launch_bounds__(256) void convt_quad_mfma_kernel(QuadParams p) {
 // Persistent: a block copies the packed weights to LDS ONCE and walks a contiguous run of tiles (image-major: the tiles of an
 // image follow each other, so their halo rows are re-read from this CU's L1 / this XCD's L2 instead of from HBM); the patch
 // pipeline runs across tile boundaries (chunk 0 of the next tile is fetched under the last chunk's MFMAs of this one).
-// tanh(x) = 1 - 2 / (exp(2x) + 1) on the hardware exp2 / rcp (5 VALU ops; ocml's tanhf is ~25, and every VALU op of this epilogue
-// costs matrix time on its SIMD): absolute error <= 2.4e-7 over the whole range (1 ulp of exp2 and rcp at results <= 1), +-1 at +-inf
-__device__ __forceinline__ float fast_tanh(float x) {
-    const float t = __builtin_amdgcn_exp2f(x * 2.885390081777927f);      // exp(2x); inf for large x -> rcp 0 -> 1, 0 for very negative x -> -1
-    return 1.f - 2.f * __builtin_amdgcn_rcpf(t + 1.f);
-}
-
 // NYX = 3: the 3 x 3 neighbourhood of a 5 x 5 (or 4 x 4) stride-2 layer at compile time -- every LDS fragment address is then the
 // lane's base plus an instruction immediate; NYX = 0: neighbourhood from the parameters.
+// The block's LDS, kernel and launcher alike: packed weights [K/4][16][4] | patch [2][PH][PW][16] (the epilogue stages in a patch buffer)
+struct QuadLds {
+    static constexpr int PL = 6;                           // float4 of a patch a thread stages: ceil(10*34*4 / 256), ceil(18*18*4 / 256)
+    static constexpr int th(int tw) { return 256 / tw; }   // tile height (quads) of a tile tw wide
+    static constexpr int ph(int tw, int ny) { return th(tw) + ny - 1; }      // patch rows / cols (pixels)
+    static constexpr int pw(int tw, int nx) { return tw + nx - 1; }
+    static constexpr int patch_f4(int ph, int pw) { return ph * pw * 4; }    // float4 per 16-channel patch
+};
+
 template <int NPAD, int TW, int NYX>   // NPAD = N (<= 4); TW = tile width in quads (32 or 16), tile height 256 / TW
 __global__ __launch_bounds__(256, 2) void convt_quad_lds_kernel(QuadParams p, int tiles_total, int tiles_per_block) {
-    constexpr int TH = 256 / TW;
+    constexpr int TH = QuadLds::th(TW);
     constexpr int QR = TH / 4;                              // quad rows per wave (2 or 4)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, i = lane & 15;
     const int ny = NYX ? NYX : p.ny, nx = NYX ? NYX : p.nx;
     const int K = ny * nx * p.Cs;
-    const int PH = TH + ny - 1, PW = TW + nx - 1;          // patch rows / cols (pixels)
-    const int patch_f4 = PH * PW * 4;                      // float4 per 16-channel patch
+    const int PH = QuadLds::ph(TW, ny), PW = QuadLds::pw(TW, nx);
+    const int patch_f4 = QuadLds::patch_f4(PH, PW);
     float* Bs = smem;                                      // [K/4][16][4]
     float* Ps = smem + (size_t)K * 16;                     // [2][PH][PW][16]
-    const int t_begin = blockIdx.x * tiles_per_block;
-    const int t_end = t_begin + tiles_per_block < tiles_total ? t_begin + tiles_per_block : tiles_total;
-    if (t_begin >= t_end) return;
+    int t_begin, t_end;
+    if (!block_run(tiles_per_block, tiles_total, t_begin, t_end)) return;
     for (int q = tid; q < K * 4; q += 256) ((f32x4*)Bs)[q] = ((const f32x4*)p.wq)[q];
 
     const int tiles_x = (p.Ws + TW - 1) / TW, tiles_y = (p.Hs + TH - 1) / TH;
     const int tpi = tiles_x * tiles_y;
 
-    const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.in, 0, (int)((unsigned)p.B * (unsigned)p.Hs * (unsigned)p.Ws * (unsigned)p.Cs * 4u), 0x00020000);
-    constexpr int PL = 6;                                  // float4 staged per thread: ceil(10*34*4 / 256), ceil(18*18*4 / 256)
+    const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.in, (unsigned)p.B * (unsigned)p.Hs * (unsigned)p.Ws * (unsigned)p.Cs * 4u);
+    constexpr int PL = QuadLds::PL;
     f32x4 st[PL];
     int l_pr[PL], l_pc[PL];                                // this thread's patch elements (pixel row / col inside the patch), -2^20 = none
     unsigned l_src[PL];                                    // ... and their byte offset relative to the patch origin pixel, chunk 0
@@ -218,7 +205,7 @@ __global__ __launch_bounds__(256, 2) void convt_quad_lds_kernel(QuadParams p, in
     do {                                                                                                    \
         const unsigned org_ = (unsigned)(((((b_) * p.Hs + (r0_) + p.dmin_y) * p.Ws + (c0_) + p.dmin_x) * p.Cs + (ch_) * 16) * 4);   /* scalar */ \
         _Pragma("unroll") for (int u = 0; u < PL; ++u) {                                                    \
-            const unsigned off = (okmask >> u) & 1u ? org_ + l_src[u] : 0xFFFFFFF0u;                        \
+            const unsigned off = (okmask >> u) & 1u ? org_ + l_src[u] : BUFFER_OOB;                        \
             st[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off, 0, 0));   \
         }                                                                                                   \
     } while (0)
@@ -267,12 +254,7 @@ __global__ __launch_bounds__(256, 2) void convt_quad_lds_kernel(QuadParams p, in
                         fa[tt] = *(const f32x4*)(P + ((size_t)(pr * PW + pc) * 4 + g) * 4);
                     }
 #pragma unroll
-                    for (int tt = 0; tt < 4; ++tt) {
-                        acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[tt].x, fb.x, acc[tt], 0, 0, 0);
-                        acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[tt].y, fb.y, acc[tt], 0, 0, 0);
-                        acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[tt].z, fb.z, acc[tt], 0, 0, 0);
-                        acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[tt].w, fb.w, acc[tt], 0, 0, 0);
-                    }
+                    for (int tt = 0; tt < 4; ++tt) mfma16x4(acc[tt], fa[tt], fb);
                 }
             if (fetch) { STORE_PATCH(buf ^ 1); }
             __syncthreads();
@@ -292,9 +274,7 @@ __global__ __launch_bounds__(256, 2) void convt_quad_lds_kernel(QuadParams p, in
                     E[(2 * (TW == 32 ? (tt >> 1) : tt) + py) * rowf + (2 * c + px) * N + n] = acc[tt][r] + bias;
                 }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const int f4_per_row = rowf / 4;                       // 48 for N = 3, TW = 32
         const int live_f = 2 * (p.Ws - c0 < TW ? p.Ws - c0 : TW) * N;      // floats of a tile row that lie inside the image
         for (int q = lane; q < 2 * QR * f4_per_row; q += 64) {
@@ -378,36 +358,40 @@ __global__ void pack_rows_weights_kernel(const float* __restrict__ w, float* __r
 // 319 algorithmic on dcgan64's g_h4).  4: 6 input rows per 4 pairs -- a quarter fewer loads, 1.5 reads per row instead of 2 -- for
 // twice the accumulators (64 VGPRs; the launch runs two blocks = 4 waves per SIMD anyway, so 128 VGPRs are there).
 // AUXE: the *_BWD epilogues (an aux tensor of the output's shape); compiled apart so that the forward form carries no aux registers.
+// A block's LDS, kernel and launcher alike: packed weights [kh*Cs/4][16][4] | NWV staging tiles | Tg, Tb [NU][64][4] | Tq [NU][64].
+// Staging of one output row pair: [2 rows][SP pixels = -2 .. 16 MT][SL floats]; the pixels < 0 and >= Ws and the columns >= 16 stay
+// zero, so the gather needs no bounds: its three terms are the lane's base address + instruction immediates.
+struct RowsLds {
+    static constexpr int NWV = 8, SL = 20;                                          // waves per block, floats per staged pixel
+    static constexpr int sp(int mt) { return mt * 16 + 3; }
+    static constexpr int sw(int mt) { return 2 * sp(mt) * SL; }                     // floats of a wave's staging tile
+    static constexpr int nu(int n, int mt) { return (2 * (2 * mt * 16 * n / 4) + 63) / 64; }      // float4 of a row pair per lane
+    static constexpr size_t floats(size_t wfl, int n, int mt) { return wfl + (size_t)NWV * sw(mt) + (size_t)nu(n, mt) * 64 * 9; }
+};
+
 template <int N, int MT, bool S5, int NP, bool AUXE>   // N output channels, MT 16-pixel tiles per input row (Ws <= 16 * MT)
 __global__ __launch_bounds__(512, 4) void convt_rows_kernel(RowsParams p, int tasks_total, int tasks_per_block) {
     const int kh = S5 ? 5 : p.kh, pt = S5 ? 1 : p.pt, dmin_y = S5 ? -1 : p.dmin_y, ny = S5 ? 3 : p.ny;
     constexpr int NYO = 2 * NP;                             // output rows per task
-    constexpr int NWV = 8;                                  // waves per block
-    // staging of one output row pair: [2 rows][pixel -2 .. ROWS][SL floats]; the pixels < 0 and >= Ws and the columns >= 16 stay
-    // zero, so the gather needs no bounds: its three terms are the lane's base address + instruction immediates
-    constexpr int ROWS = MT * 16, SL = 20, SP = ROWS + 3;
-    constexpr int SW = 2 * SP * SL;
-    constexpr int NU = (2 * (2 * ROWS * N / 4) + 63) / 64;  // float4 of a row pair per lane
+    constexpr int NWV = RowsLds::NWV, SL = RowsLds::SL, SP = RowsLds::sp(MT), SW = RowsLds::sw(MT), NU = RowsLds::nu(N, MT);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (tells the compiler it is wave-uniform: task indices, row offsets and descriptors stay in SGPRs)
     const int g = lane >> 4, i = lane & 15;
     float* Wl = smem;
     float* S = smem + (size_t)kh * p.Cs * 16 + (size_t)wave * SW;
-    const int t_begin = blockIdx.x * tasks_per_block;
-    const int t_end = t_begin + tasks_per_block < tasks_total ? t_begin + tasks_per_block : tasks_total;
-    if (t_begin >= t_end) return;
+    int t_begin, t_end;
+    if (!block_run(tasks_per_block, tasks_total, t_begin, t_end)) return;
     for (int q = tid; q < kh * p.Cs * 4; q += 64 * NWV) ((f32x4*)Wl)[q] = ((const f32x4*)p.wp)[q];
     for (int q = lane; q < SW; q += 64) S[q] = 0.f;
     __syncthreads();
 
-    const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.in, 0, (int)((unsigned)p.B * (unsigned)p.Hs * (unsigned)p.Ws * (unsigned)p.Cs * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t null_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.in, (unsigned)p.B * (unsigned)p.Hs * (unsigned)p.Ws * (unsigned)p.Cs * 4u);
+    const __amdgpu_buffer_rsrc_t null_rsrc = buffer_rsrc_empty(p.in);
     // loop-invariant per-lane part of the A addresses: pixel (16m + i), channels 4g.. (past the row -> out of range -> zeros)
     unsigned coff[MT];
 #pragma unroll
-    for (int m = 0; m < MT; ++m) coff[m] = 16 * m + i < p.Ws ? (unsigned)(((16 * m + i) * p.Cs + 4 * g) * 4) : 0xFFFFFFF0u;
+    for (int m = 0; m < MT; ++m) coff[m] = 16 * m + i < p.Ws ? (unsigned)(((16 * m + i) * p.Cs + 4 * g) * 4) : BUFFER_OOB;
     // gather plan of this lane: float4 q = lane + 64u of a row pair -> output row yr, floats 4xq..4xq+3 of that row; each float
     // (X, n) sums Q[yr][c][(kx, n)] over kx = kx0, kx0 + 2, kx0 + 4 with kx0 = (X + pl) & 1 and 2c = X + pl - kx: one step in kx
     // is one pixel down and 2N columns up, a constant stride, and every out-of-range term lands on a zero of the staging tile
@@ -552,9 +536,7 @@ __global__ __launch_bounds__(512, 4) void convt_rows_kernel(RowsParams p, int ta
                     S[(2 + 16 * m + 4 * g + r) * SL + i] = acc[2 * hp][m][r];
                     S[(SP + 2 + 16 * m + 4 * g + r) * SL + i] = acc[2 * hp + 1][m][r];
                 }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
                 if (gq[u] < 0) continue;
@@ -584,9 +566,7 @@ __global__ __launch_bounds__(512, 4) void convt_rows_kernel(RowsParams p, int ta
                 }
                 *(f32x4*)(p.out + o_pair + gq[u]) = v;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
         }
     }
 }
@@ -600,8 +580,11 @@ static int rows_mt(const CgsLayer& L) {
     return L.Ws <= 16 ? 1 : 2;
 }
 
-static void quad_range(int k, int pad, int& lo, int& hi) {
-    lo = 1 << 20; hi = -(1 << 20);
+
+// the neighbourhood of a quad along one axis: input offsets d = (parity + pad - tap) / 2 over the pairs of matching parity -> lowest d, count
+static void quad_range(int k, int pad, int& lo, int& n) {
+    int hi = -(1 << 20);
+    lo = 1 << 20;
     for (int par = 0; par < 2; ++par)
         for (int kk = 0; kk < k; ++kk)
             if (((par + pad - kk) & 1) == 0) {
@@ -609,156 +592,131 @@ static void quad_range(int k, int pad, int& lo, int& hi) {
                 if (d < lo) lo = d;
                 if (d > hi) hi = d;
             }
+    n = hi - lo + 1;
+}
+
+// ... of a layer, into p; pt / pl = TF 'SAME' padding before the first pixel.  -> bytes of the quad forms' packed weight image [ny*nx*Cs][16]
+static size_t quad_geom(const CgsLayer& L, QuadParams& p, int& pt, int& pl) {
+    pt = cgs_same_pad_before(L.Hb, L.kh, 2); pl = cgs_same_pad_before(L.Wb, L.kw, 2);
+    quad_range(L.kh, pt, p.dmin_y, p.ny);
+    quad_range(L.kw, pl, p.dmin_x, p.nx);
+    return (size_t)p.ny * p.nx * L.Cs * 16 * sizeof(float);
 }
 
 size_t cgs_convt_quad_ws_floats_bound(int kh, int kw, int Cs) {
     return (size_t)((kh + 1) / 2 + 1) * ((kw + 1) / 2 + 1) * Cs * 16;
 }
 
-// the quad form keeps the whole packed weight image [ny*nx*Cs][16] in LDS: large kernels x many channels do not fit
+// the quad forms keep the whole packed weight image in LDS: large kernels x many channels do not fit
+static constexpr size_t QUAD_WEIGHT_BYTES_MAX = 150 * 1024;
 bool cgs_convt_quad_fits(const CgsLayer& L) {
-    const int pt = cgs_same_pad_before(L.Hb, L.kh, 2), pl = cgs_same_pad_before(L.Wb, L.kw, 2);
-    int dy0, hy, dx0, hx;
-    quad_range(L.kh, pt, dy0, hy);
-    quad_range(L.kw, pl, dx0, hx);
-    return (size_t)(hy - dy0 + 1) * (hx - dx0 + 1) * L.Cs * 16 * sizeof(float) <= 150 * 1024;
+    QuadParams p;
+    int pt, pl;
+    return quad_geom(L, p, pt, pl) <= QUAD_WEIGHT_BYTES_MAX;
 }
 
-int cgs_convt_quad_launch(const CgsLayer& L, int B, const float* in, const float* w, const float* bias, float* out,
-                          int epilogue, const float* ep_a, const float* ep_aux, float* ws, size_t ws_bytes, int prepacked,
-                          hipStream_t s) {
-    QuadParams p;
-    p.in = in; p.wq = ws; p.bias = bias; p.out = out; p.ep_a = ep_a; p.ep_aux = ep_aux;
-    p.B = B; p.Hs = L.Hs; p.Ws = L.Ws; p.Cs = L.Cs; p.N = L.Cb; p.epilogue = epilogue;
-    const int pt = cgs_same_pad_before(L.Hb, L.kh, 2), pl = cgs_same_pad_before(L.Wb, L.kw, 2);
-    int hy, hx;
-    quad_range(L.kh, pt, p.dmin_y, hy);
-    quad_range(L.kw, pl, p.dmin_x, hx);
-    p.ny = hy - p.dmin_y + 1; p.nx = hx - p.dmin_x + 1;
-    if ((long)B * L.Hs * L.Ws * L.Cs * 4 > 0x7fffffffL) return cgs_set_error(CGS_EINVAL, "convt_quad: input exceeds 2 GiB (split the batch)");
-    // the taps kernel reads the raw weights and the input as float4: a view at an unaligned offset keeps the packed rows / quad forms below
-    const bool taps_aligned = !(((uintptr_t)w | (uintptr_t)in) & 15);
-    if (cgs_convt_taps_ok(L) && taps_aligned) return cgs_convt_taps_launch(L, B, in, w, bias, out, epilogue, ep_a, ep_aux, s);      // (reads the unpacked weights)
-    if (const int mt = rows_mt(L)) {
-        RowsParams r;
-        r.in = in; r.wp = ws; r.bias = bias; r.out = out; r.ep_a = ep_a; r.ep_aux = ep_aux;
-        r.B = B; r.Hs = L.Hs; r.Ws = L.Ws; r.Cs = L.Cs; r.kh = L.kh; r.kw = L.kw; r.pt = pt; r.pl = pl;
-        r.dmin_y = p.dmin_y; r.ny = p.ny; r.epilogue = epilogue;
-        const size_t wfl = (size_t)L.kh * L.Cs * 16;
-        if (!ws || ws_bytes < wfl * sizeof(float)) return cgs_set_error(CGS_EWORKSPACE, "convt_rows: workspace %zu < %zu bytes", ws_bytes, wfl * sizeof(float));
-        if (!prepacked) {
-            hipLaunchKernelGGL(pack_rows_weights_kernel, dim3((unsigned)((wfl + 255) / 256)), dim3(256), 0, s, w, ws, L.kh, L.kw, L.Cb, L.Cs);
-            CGS_CHECK_LAUNCH("pack_rows_weights");
-        }
-        const bool s5 = L.kh == 5 && L.Cs == 64 && pt == 1 && p.dmin_y == -1 && p.ny == 3;
-        // output row pairs per task: the forward 5x5 64 -> 3 layers run the tall form (with an aux epilogue its 64 accumulators + the
-        // aux values do not fit 128 VGPRs: 35 spilled registers)
-        const bool tall_ok = s5 && L.Cb == 3 && L.Hs >= 8 && epilogue < CGS_EPI_RELU_BWD_AFFINE;
-        const int np = tall_ok ? 4 : 2;
-        const long tasks = (long)B * ((L.Hs + np - 1) / np);
-        if (tasks == 0) return CGS_OK;
-        // persistent blocks of 8 independent waves, two per CU; a block's waves walk neighbouring row pairs of a contiguous run
-        long blocks = (tasks + 7) / 8;
-        if (blocks > 512) blocks = 512;
-        long per = (tasks + blocks - 1) / blocks;
-        per = (per + 7) / 8 * 8;
-        blocks = (tasks + per - 1) / per;
-        const int nu = (2 * (2 * mt * 16 * L.Cb / 4) + 63) / 64;
-        const size_t smem = (wfl + (size_t)8 * (2 * (mt * 16 + 3) * 20) + (size_t)nu * 64 * 9) * sizeof(float);
-#define ROWS_LAUNCH(NN, MM, SS, PP)                                                                                  \
-    if (epilogue >= CGS_EPI_RELU_BWD_AFFINE) ROWS_LAUNCH_(NN, MM, SS, PP, true) else ROWS_LAUNCH_(NN, MM, SS, PP, false)
-#define ROWS_LAUNCH_(NN, MM, SS, PP, AA)                                                                             \
-    {                                                                                                              \
-        static bool done_[64] = {};                                                                                \
-        int dv_ = 0;                                                                                               \
-        (void)hipGetDevice(&dv_);                                                                                  \
-        dv_ &= 63;                                                                                                 \
-        if (!done_[dv_]) {                                                                                         \
-            hipError_t e = hipFuncSetAttribute((const void*)convt_rows_kernel<NN, MM, SS, PP, AA>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            if (e != hipSuccess) return cgs_set_error(CGS_ELAUNCH, "convt_rows smem attr: %s", hipGetErrorString(e)); \
-            done_[dv_] = true;                                                                                     \
-        }                                                                                                          \
-        hipLaunchKernelGGL((convt_rows_kernel<NN, MM, SS, PP, AA>), dim3((unsigned)blocks), dim3(512), smem, s, r, (int)tasks, (int)per); \
+// Rows form.  Persistent blocks of 8 independent waves, two per CU (512 blocks), each a contiguous run of tasks.  Not cgs_persistent_run:
+// a run is a whole number of rounds of the block's 8 waves, however short.
+static int rows_launch(const CgsLayer& L, const QuadParams& q, int mt, int pt, int pl, const float* w, size_t ws_bytes, int prepacked, hipStream_t s) {
+    RowsParams r;
+    r.in = q.in; r.wp = q.wq; r.bias = q.bias; r.out = q.out; r.ep_a = q.ep_a; r.ep_aux = q.ep_aux;
+    r.B = q.B; r.Hs = L.Hs; r.Ws = L.Ws; r.Cs = L.Cs; r.kh = L.kh; r.kw = L.kw; r.pt = pt; r.pl = pl;
+    r.dmin_y = q.dmin_y; r.ny = q.ny; r.epilogue = q.epilogue;
+    const size_t wfl = (size_t)L.kh * L.Cs * 16;
+    if (!r.wp || ws_bytes < wfl * sizeof(float)) return cgs_set_error(CGS_EWORKSPACE, "convt_rows: workspace %zu < %zu bytes", ws_bytes, wfl * sizeof(float));
+    if (!prepacked) {
+        hipLaunchKernelGGL(pack_rows_weights_kernel, dim3((unsigned)((wfl + 255) / 256)), dim3(256), 0, s, w, (float*)q.wq, L.kh, L.kw, L.Cb, L.Cs);      // (wq is the caller's workspace)
+        CGS_CHECK_LAUNCH("pack_rows_weights");
     }
-        if (L.Cb == 3) {
-            if (mt == 1) { if (s5 && np == 4) ROWS_LAUNCH_(3, 1, true, 4, false) else if (s5) ROWS_LAUNCH(3, 1, true, 2) else ROWS_LAUNCH(3, 1, false, 2) }
-            else { if (s5 && np == 4) ROWS_LAUNCH_(3, 2, true, 4, false) else if (s5) ROWS_LAUNCH(3, 2, true, 2) else ROWS_LAUNCH(3, 2, false, 2) }
-        } else {
-            if (mt == 1) ROWS_LAUNCH(1, 1, false, 2) else ROWS_LAUNCH(1, 2, false, 2)
-        }
+    const bool auxe = r.epilogue >= CGS_EPI_RELU_BWD_AFFINE;
+    const bool s5 = L.Cb == 3 && L.kh == 5 && L.Cs == 64 && pt == 1 && r.dmin_y == -1 && r.ny == 3;
+    // output row pairs per task: the forward 5x5 64 -> 3 layers run the tall form (with an aux epilogue its 64 accumulators + the
+    // aux values do not fit 128 VGPRs: 35 spilled registers)
+    const bool tall = s5 && L.Hs >= 8 && !auxe;
+    const long tasks = (long)r.B * ((L.Hs + (tall ? 3 : 1)) / (tall ? 4 : 2));
+    if (tasks == 0) return CGS_OK;
+    long blocks = (tasks + RowsLds::NWV - 1) / RowsLds::NWV;
+    if (blocks > 512) blocks = 512;
+    const long per = ((tasks + blocks - 1) / blocks + RowsLds::NWV - 1) / RowsLds::NWV * RowsLds::NWV;
+    blocks = (tasks + per - 1) / per;
+    const size_t smem = RowsLds::floats(wfl, L.Cb, mt) * sizeof(float);
+#define ROWS_LAUNCH_(NN, MM, SS, PP, AA)                                                                           \
+    {                                                                                                              \
+        CGS_SMEM_ATTR(160 * 1024, "convt_rows", convt_rows_kernel<NN, MM, SS, PP, AA>);                            \
+        CGS_LAUNCH_T(convt_rows_kernel, (NN, MM, SS, PP, AA), dim3((unsigned)blocks), dim3(512), smem, s, r, (int)tasks, (int)per); \
+    }
+#define ROWS_LAUNCH(NN, MM, SS) if (auxe) ROWS_LAUNCH_(NN, MM, SS, 2, true) else ROWS_LAUNCH_(NN, MM, SS, 2, false)
+#define ROWS_LAUNCH_MT(MM)                                                                                         \
+    if (L.Cb == 1) ROWS_LAUNCH(1, MM, false) else if (tall) ROWS_LAUNCH_(3, MM, true, 4, false)                    \
+    else if (s5) ROWS_LAUNCH(3, MM, true) else ROWS_LAUNCH(3, MM, false)
+    if (mt == 1) { ROWS_LAUNCH_MT(1) } else { ROWS_LAUNCH_MT(2) }
+#undef ROWS_LAUNCH_MT
 #undef ROWS_LAUNCH
 #undef ROWS_LAUNCH_
-        CGS_CHECK_LAUNCH("convt_rows");
-        static thread_local char name[48];
-        snprintf(name, sizeof(name), "convt_rows_kernel<%d, %d, %s, %d, %s>", L.Cb, mt, (s5 && L.Cb == 3) ? "true" : "false", np,
-                 epilogue >= CGS_EPI_RELU_BWD_AFFINE ? "true" : "false");       // as rocprofv3 prints it
-        cgs_note_kernel(name);
-        return CGS_OK;
-    }
-    const size_t K = (size_t)p.ny * p.nx * L.Cs;
-    const size_t need = K * 16 * sizeof(float);
-    if (!ws || ws_bytes < need) return cgs_set_error(CGS_EWORKSPACE, "convt_quad: workspace %zu < %zu bytes", ws_bytes, need);
-    if (need > 150 * 1024) return cgs_set_error(CGS_EINVAL, "convt_quad: packed weights (%zu B) exceed LDS", need);
-    if (!prepacked) {
-        hipLaunchKernelGGL(pack_quad_weights_kernel, dim3((unsigned)((K * 16 + 255) / 256)), dim3(256), 0, s, w, ws, L.kh, L.kw,
-                           L.Cb, L.Cs, pt, pl, p.dmin_y, p.ny, p.dmin_x, p.nx);
-        CGS_CHECK_LAUNCH("pack_quad_weights");
-    }
-    const long total_q = (long)B * L.Hs * L.Ws;
-    if (total_q == 0) return CGS_OK;
-    // LDS-patch variant: 8 x 32 quad tiles, or 16 x 16 (clipped at the edges) for grids that are not whole 8 x 32 tiles;
-    // needs 16-byte aligned output rows
-    if (p.ny <= 3 && p.nx <= 3 && ((2 * L.Ws * L.Cb) % 4) == 0 && ((32 * L.Cb) % 4) == 0) {
-        const bool wide = (L.Ws % 32) == 0 && (L.Hs % 8) == 0;
-        const bool nyx3 = p.ny == 3 && p.nx == 3;
-        const int TWr = wide ? 32 : 16, THr = 256 / TWr;
-        const int PH = THr + p.ny - 1, PW = TWr + p.nx - 1;
-        const size_t smem = need + (size_t)2 * PH * PW * 16 * sizeof(float);
-        const long tiles = (long)B * cgs_ceil_div(L.Hs, THr) * cgs_ceil_div(L.Ws, TWr);
-        // persistent blocks: two per CU, each a contiguous run of tiles (the 37 KB weight image is copied to LDS once per block);
-        // small launches keep one tile per block
-        long per = (tiles + 511) / 512;
-        if (per < 4) per = tiles >= 4 * 256 ? 4 : 1;
-        const long blocks = (tiles + per - 1) / per;
+    CGS_CHECK_LAUNCH("convt_rows");
+    return CGS_OK;
+}
+
+// LDS-patch form: TW x 256 / TW quad tiles; two persistent blocks per CU (the 37 KB weight image is copied to LDS once per block)
+static int quad_lds_launch(const CgsLayer& L, const QuadParams& p, int TW, size_t smem, hipStream_t s) {
+    const bool wide = TW == 32, nyx3 = p.ny == 3 && p.nx == 3;
+    const long tiles = (long)p.B * cgs_ceil_div(L.Hs, QuadLds::th(TW)) * cgs_ceil_div(L.Ws, TW);
+    long per, blocks;
+    cgs_persistent_run(tiles, 512, &per, &blocks);
 #define QUAD_LDS_LAUNCH(NN, TT, YX)                                                                                \
     {                                                                                                              \
         CGS_SMEM_ATTR(160 * 1024, "convt_quad_lds", convt_quad_lds_kernel<NN, TT, YX>);                            \
-        hipLaunchKernelGGL((convt_quad_lds_kernel<NN, TT, YX>), dim3((unsigned)blocks), dim3(256), smem, s, p, (int)tiles, (int)per); \
+        CGS_LAUNCH_T(convt_quad_lds_kernel, (NN, TT, YX), dim3((unsigned)blocks), dim3(256), smem, s, p, (int)tiles, (int)per); \
     }
 #define QUAD_LDS_CASE(NN)                                                                                          \
     case NN:                                                                                                       \
         if (wide && nyx3) QUAD_LDS_LAUNCH(NN, 32, 3) else if (wide) QUAD_LDS_LAUNCH(NN, 32, 0)                     \
         else if (nyx3) QUAD_LDS_LAUNCH(NN, 16, 3) else QUAD_LDS_LAUNCH(NN, 16, 0)                                  \
         break;
-        if (smem <= 160 * 1024 && (size_t)4 * 256 * L.Cb <= (size_t)2 * PH * PW * 16) {
-            switch (L.Cb) {
-                QUAD_LDS_CASE(1) QUAD_LDS_CASE(2) QUAD_LDS_CASE(3) QUAD_LDS_CASE(4)
-                default: return cgs_set_error(CGS_EINVAL, "convt_quad: N=%d", L.Cb);
-            }
+    switch (L.Cb) {
+        QUAD_LDS_CASE(1) QUAD_LDS_CASE(2) QUAD_LDS_CASE(3) QUAD_LDS_CASE(4)
+        default: return cgs_set_error(CGS_EINVAL, "convt_quad: N=%d", L.Cb);
+    }
 #undef QUAD_LDS_CASE
 #undef QUAD_LDS_LAUNCH
-            CGS_CHECK_LAUNCH("convt_quad_lds");
-            static thread_local char name[48];
-            snprintf(name, sizeof(name), "convt_quad_lds_kernel<%d, %d, %d>", L.Cb, TWr, nyx3 ? 3 : 0);       // as rocprofv3 prints it
-            cgs_note_kernel(name);
-            return CGS_OK;
-        }
-    }
-    constexpr int MT = 4;
-    static bool attr_done[64] = {};       // per device: the attribute belongs to the device's code object
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    dev_ &= 63;
-    if (!attr_done[dev_]) {
-        hipError_t e = hipFuncSetAttribute((const void*)convt_quad_mfma_kernel<MT>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) return cgs_set_error(CGS_ELAUNCH, "convt_quad smem attr: %s", hipGetErrorString(e));
-        attr_done[dev_] = true;
-    }
-    const long total = (long)B * L.Hs * L.Ws;
-    if (total == 0) return CGS_OK;
-    const long blocks = (total + 64 * MT - 1) / (64 * MT);
-    hipLaunchKernelGGL(convt_quad_mfma_kernel<MT>, dim3((unsigned)blocks), dim3(256), need, s, p);
-    CGS_CHECK_LAUNCH("convt_quad_mfma");
-    cgs_note_kernel("convt_quad_mfma_kernel<4>");
+    CGS_CHECK_LAUNCH("convt_quad_lds");
     return CGS_OK;
+}
+
+// global-load form: any neighbourhood, any row alignment; a block = 4 waves x 4 tiles of 16 quads
+static int quad_mfma_launch(const QuadParams& p, size_t need, hipStream_t s) {
+    CGS_SMEM_ATTR(QUAD_WEIGHT_BYTES_MAX, "convt_quad_mfma", convt_quad_mfma_kernel<4>);
+    const long blocks = ((long)p.B * p.Hs * p.Ws + 64 * 4 - 1) / (64 * 4);
+    CGS_LAUNCH_T(convt_quad_mfma_kernel, (4), dim3((unsigned)blocks), dim3(256), need, s, p);
+    CGS_CHECK_LAUNCH("convt_quad_mfma");
+    return CGS_OK;
+}
+
+// The chooser: taps (convt_taps.hip; it reads the raw weights and the input as float4 -- a view at an unaligned offset keeps the packed
+// forms) -> rows -> the quad forms on their packed image: LDS patch (8 x 32 quad tiles, or 16 x 16 clipped at the edges for grids that are not
+// whole 8 x 32 tiles; a neighbourhood <= 3 x 3, 16-byte aligned output rows, staging rows inside a patch buffer) -> global loads
+int cgs_convt_quad_launch(const CgsLayer& L, int B, const float* in, const float* w, const float* bias, float* out,
+                          int epilogue, const float* ep_a, const float* ep_aux, float* ws, size_t ws_bytes, int prepacked,
+                          hipStream_t s) {
+    if ((long)B * L.Hs * L.Ws * L.Cs * 4 > 0x7fffffffL) return cgs_set_error(CGS_EINVAL, "convt_quad: input exceeds 2 GiB (split the batch)");
+    if (cgs_convt_taps_ok(L) && !(((uintptr_t)w | (uintptr_t)in) & 15)) return cgs_convt_taps_launch(L, B, in, w, bias, out, epilogue, ep_a, ep_aux, s);
+    QuadParams p;
+    p.in = in; p.wq = ws; p.bias = bias; p.out = out; p.ep_a = ep_a; p.ep_aux = ep_aux;
+    p.B = B; p.Hs = L.Hs; p.Ws = L.Ws; p.Cs = L.Cs; p.N = L.Cb; p.epilogue = epilogue;
+    int pt, pl;
+    const size_t need = quad_geom(L, p, pt, pl);
+    if (const int mt = rows_mt(L)) return rows_launch(L, p, mt, pt, pl, w, ws_bytes, prepacked, s);
+    if (!ws || ws_bytes < need) return cgs_set_error(CGS_EWORKSPACE, "convt_quad: workspace %zu < %zu bytes", ws_bytes, need);
+    if (need > QUAD_WEIGHT_BYTES_MAX) return cgs_set_error(CGS_EINVAL, "convt_quad: packed weights (%zu B) exceed LDS", need);
+    if (!prepacked) {
+        hipLaunchKernelGGL(pack_quad_weights_kernel, dim3((unsigned)((need / sizeof(float) + 255) / 256)), dim3(256), 0, s, w, ws, L.kh, L.kw,
+                           L.Cb, L.Cs, pt, pl, p.dmin_y, p.ny, p.dmin_x, p.nx);
+        CGS_CHECK_LAUNCH("pack_quad_weights");
+    }
+    if ((long)B * L.Hs * L.Ws == 0) return CGS_OK;
+    const int TW = (L.Ws % 32) == 0 && (L.Hs % 8) == 0 ? 32 : 16;
+    const size_t patch = (size_t)QuadLds::patch_f4(QuadLds::ph(TW, p.ny), QuadLds::pw(TW, p.nx)) * 4, smem = need + 2 * patch * sizeof(float);
+    if (p.ny <= 3 && p.nx <= 3 && ((2 * L.Ws * L.Cb) % 4) == 0 && smem <= 160 * 1024 && (size_t)4 * 256 * L.Cb <= 2 * patch)
+        return quad_lds_launch(L, p, TW, smem, s);
+    return quad_mfma_launch(p, need, s);
 }

@@ -76,10 +76,8 @@ __global__ __launch_bounds__(256) void convt_smalln_kernel(SmallNParams p) {
         for (int px = 0; px < 2; ++px)
 #pragma unroll
             for (int n = 0; n < N; ++n) {
-                float v = acc[py][px][n] + (p.bias ? p.bias[n] : 0.f);
-                if (p.epilogue == CGS_EPI_TANH) v = tanhf(v);
-                else if (p.epilogue == CGS_EPI_LRELU) v = fmaxf(v, 0.2f * v);
-                o[px * N + n] = v;
+                const float v = acc[py][px][n] + (p.bias ? p.bias[n] : 0.f);
+                o[px * N + n] = epilogue_elem<EPI_TANHF, EPI_MODES_T_FWD>(v, p.epilogue, 1.f, 0.f, 0.f);
             }
     }
 }

@@ -16,11 +16,7 @@
 // then both staged -- the output row pair (2 x 2Ws <= 64 floats: one per lane) as four LDS reads in a fixed order (deterministic).
 // The weights need no packing: lane (g, i) reads w[(ky, kx) = i][ci = 16 j + 4 g ..] as one float4 per 16-channel chunk and keeps them
 // in registers.  Every input element is read from HBM once (plus a one-row halo per task), every output written once.
-#include <stdio.h>
-
 #include "cgs_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct TapsParams {
     const float* in;     // [B,Hs,Ws,Cs]
@@ -33,11 +29,6 @@ struct TapsParams {
     int rb;              // input rows per task
     int epilogue;
 };
-
-__device__ __forceinline__ float taps_tanh(float x) {      // tanh on exp2 / rcp (5 VALU ops, |error| <= 2.4e-7; see convt_quad.hip)
-    const float t = __builtin_amdgcn_exp2f(x * 2.885390081777927f);
-    return 1.f - 2.f * __builtin_amdgcn_rcpf(t + 1.f);
-}
 
 template <int NCH>      // 16-channel chunks of the input: Cs = 16 * NCH
 __global__ __launch_bounds__(256) void convt_taps_kernel(TapsParams p, int tasks_total) {
@@ -55,10 +46,9 @@ __global__ __launch_bounds__(256) void convt_taps_kernel(TapsParams p, int tasks
     for (int j = 0; j < NCH; ++j) fb[j] = *(const f32x4*)(p.w + (size_t)i * p.Cs + 16 * j + 4 * g);
     const float bias = p.bias ? p.bias[0] : 0.f;
     const float ea = (p.epilogue == CGS_EPI_RELU_BWD_AFFINE && p.ep_a) ? p.ep_a[0] : 1.f;
-    const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.in, 0, (int)((unsigned)p.B * (unsigned)p.Hs * (unsigned)p.Ws * (unsigned)p.Cs * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t null_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, 0, 0x00020000);
-    const unsigned coff = i < p.Ws ? (unsigned)((i * p.Cs + 4 * g) * 4) : 0xFFFFFFF0u;      // pixel i of a row, channels 4 g .. of a chunk
+    const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.in, (unsigned)p.B * (unsigned)p.Hs * (unsigned)p.Ws * (unsigned)p.Cs * 4u);
+    const __amdgpu_buffer_rsrc_t null_rsrc = buffer_rsrc_empty(p.in);
+    const unsigned coff = i < p.Ws ? (unsigned)((i * p.Cs + 4 * g) * 4) : BUFFER_OOB;      // pixel i of a row, channels 4 g .. of a chunk
     // gather plan of this lane: output (row yr of the pair, column X): the two row taps and the two column taps
     const int yr = lane >> 5, X = lane & 31;
     const int W2 = 2 * p.Ws;
@@ -70,9 +60,7 @@ __global__ __launch_bounds__(256) void convt_taps_kernel(TapsParams p, int tasks
     const int offAA = (cp + 1) * SLP + kyA * 4 + kxA, offAB = (cB + 1) * SLP + kyA * 4 + kxB;      // inside the slot of row r'
     const int offBA = (cp + 1) * SLP + kyB * 4 + kxA, offBB = (cB + 1) * SLP + kyB * 4 + kxB;      // inside the slot of row r' + drB
     const int tasks_per_img = (p.Hs + p.rb - 1) / p.rb;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     for (int t = blockIdx.x * 4 + wave; t < tasks_total; t += gridDim.x * 4) {
         const int b = t / tasks_per_img, ra = (t - b * tasks_per_img) * p.rb;
@@ -90,34 +78,21 @@ __global__ __launch_bounds__(256) void convt_taps_kernel(TapsParams p, int tasks
             if (r < re) TAPS_LOAD(a_nxt, r + 1);
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int j = 0; j < NCH; ++j) {
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[j].x, fb[j].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[j].y, fb[j].y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[j].z, fb[j].z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[j].w, fb[j].w, acc, 0, 0, 0);
-            }
+            for (int j = 0; j < NCH; ++j) mfma16x4(acc, a_cur[j], fb[j]);
             // C/D layout of 16x16x4: column (tap) = lane & 15, row (pixel c) = 4 g + reg
             const int slot = (r + 3) % 3;
             float* Sr = S + slot * (SPX * SLP);
 #pragma unroll
             for (int e = 0; e < 4; ++e) Sr[(4 * g + e + 1) * SLP + i] = acc[e];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             const int rp = r - 1;                                           // rows rp - 1, rp, rp + 1 = r are staged now
             if (rp >= ra && X < W2) {
                 const float* SA = S + ((rp + 3) % 3) * (SPX * SLP);
                 const float* SB = S + ((rp + drB + 3) % 3) * (SPX * SLP);
                 float v = (((bias + SA[offAA]) + SA[offAB]) + SB[offBA]) + SB[offBB];      // a fixed order
                 const size_t o = ((size_t)(b * 2 * p.Hs + 2 * rp + yr)) * W2 + X;
-                if (p.epilogue == CGS_EPI_TANH) v = taps_tanh(v);
-                else if (p.epilogue == CGS_EPI_LRELU) v = fmaxf(v, 0.2f * v);
-                else if (p.epilogue >= CGS_EPI_RELU_BWD_AFFINE) {
-                    const float y = p.ep_aux[o];
-                    if (p.epilogue == CGS_EPI_TANH_BWD) v *= (1.f - y * y);
-                    else if (p.epilogue == CGS_EPI_LRELU_BWD) v = y > 0.f ? v : 0.2f * v;
-                    else v = y > 0.f ? v * ea : 0.f;
-                }
+                if (p.epilogue >= CGS_EPI_RELU_BWD_AFFINE) v = epilogue_elem<EPI_FAST_TANH, EPI_MODES_BWD>(v, p.epilogue, ea, 0.f, p.ep_aux[o]);
+                else v = epilogue_elem<EPI_FAST_TANH, EPI_MODES_T_FWD>(v, p.epilogue, 1.f, 0.f, 0.f);
                 p.out[o] = v;
             }
             // (the slot written next, (r + 1) % 3, holds row r - 2: its last reads are the ones just issued by this same wave, and
@@ -152,16 +127,15 @@ int cgs_convt_taps_launch(const CgsLayer& L, int B, const float* in, const float
     if (tasks > 0x7fffffffL) return cgs_set_error(CGS_EINVAL, "convt_taps: grid too large");
     long blocks = (tasks + 3) / 4;
     if (blocks > 2048) blocks = 2048;
+#define TAPS_LAUNCH(NCH_) CGS_LAUNCH_T(convt_taps_kernel, (NCH_), dim3((unsigned)blocks), dim3(256), 0, s, p, (int)tasks)
     switch (L.Cs / 16) {
-        case 1: hipLaunchKernelGGL((convt_taps_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, s, p, (int)tasks); break;
-        case 2: hipLaunchKernelGGL((convt_taps_kernel<2>), dim3((unsigned)blocks), dim3(256), 0, s, p, (int)tasks); break;
-        case 4: hipLaunchKernelGGL((convt_taps_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, s, p, (int)tasks); break;
-        default: hipLaunchKernelGGL((convt_taps_kernel<8>), dim3((unsigned)blocks), dim3(256), 0, s, p, (int)tasks); break;
+        case 1: TAPS_LAUNCH(1); break;
+        case 2: TAPS_LAUNCH(2); break;
+        case 4: TAPS_LAUNCH(4); break;
+        default: TAPS_LAUNCH(8); break;
     }
+#undef TAPS_LAUNCH
     CGS_CHECK_LAUNCH("convt_taps");
-    static thread_local char name[32];
-    snprintf(name, sizeof(name), "convt_taps_kernel<%d>", L.Cs / 16);
-    cgs_note_kernel(name);
     return CGS_OK;
 }
 
@@ -199,13 +173,11 @@ __global__ __launch_bounds__(256) void conv_taps_kernel(TapsFParams p, int tiles
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int h = lane >> 5, j = lane & 31;
     const long M = (long)p.B * p.Hs * p.Ws;
-    const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.in, 0, (int)((unsigned)p.B * (unsigned)p.Hb * (unsigned)p.Wb * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.in, (unsigned)p.B * (unsigned)p.Hb * (unsigned)p.Wb * 4u);
     const unsigned out_bytes = (unsigned)(M * p.N * 4);
-    const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, (int)out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t aux_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ep_aux ? p.ep_aux : p.out), 0, (int)out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t sg_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.aux_signs ? (const void*)p.aux_signs : (const void*)p.out), 0, (int)(out_bytes >> 5), 0x00020000);
+    const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.out, out_bytes);
+    const __amdgpu_buffer_rsrc_t aux_rsrc = buffer_rsrc(p.ep_aux ? p.ep_aux : p.out, out_bytes);
+    const __amdgpu_buffer_rsrc_t sg_rsrc = buffer_rsrc(p.aux_signs ? (const void*)p.aux_signs : (const void*)p.out, out_bytes >> 5);      // one word per 32 floats
     // B operand: step s, k index h -> tap 2 s + h; column j of tile tn
     float fbw[8][NT];
 #pragma unroll
@@ -231,7 +203,7 @@ __global__ __launch_bounds__(256) void conv_taps_kernel(TapsFParams p, int tiles
         _Pragma("unroll") for (int s = 0; s < 8; ++s) {                                                   \
             const int iy_ = 2 * r_ + (s >> 1) - p.pt, ix_ = 2 * c_ + 2 * (s & 1) + h - p.pl;               \
             const bool ok_ = live_ && (unsigned)iy_ < (unsigned)p.Hb && (unsigned)ix_ < (unsigned)p.Wb;   \
-            const unsigned off_ = ok_ ? (unsigned)(((b_ * p.Hb + iy_) * p.Wb + ix_) * 4) : 0xFFFFFFF0u;   \
+            const unsigned off_ = ok_ ? (unsigned)(((b_ * p.Hb + iy_) * p.Wb + ix_) * 4) : BUFFER_OOB;   \
             dst[s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(in_rsrc, off_, 0, 0)); \
         }                                                                                                 \
     } while (0)
@@ -282,18 +254,13 @@ __global__ __launch_bounds__(256) void conv_taps_kernel(TapsFParams p, int tiles
                 float v = acc[tn][r];
                 if constexpr (AUXM == 2) {
                     // rows `row` (lanes 0-31) and row + 4 (lanes 32-63) of tile tn: lane (tn & 1) * 32 + pixel holds that pixel's word
-                    const unsigned src = nw[tn >> 1];
-                    const unsigned lo = __builtin_amdgcn_readlane(src, 32 * (tn & 1) + row), hi = __builtin_amdgcn_readlane(src, 32 * (tn & 1) + row + 4);
-                    const bool pos = __builtin_amdgcn_inverse_ballot_w64(((unsigned long long)hi << 32) | lo);
+                    const bool pos = sign_lane_positive(nw[tn >> 1], 32 * (tn & 1) + row);
                     v = p.epilogue == CGS_EPI_RELU_BWD_AFFINE ? (pos ? v * ea[tn] : 0.f) : (pos ? v : 0.2f * v);
                 } else if constexpr (AUXM == 1) {
                     const float y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(aux_rsrc, o, 0, 0));
-                    v = p.epilogue == CGS_EPI_RELU_BWD_AFFINE ? (y > 0.f ? v * ea[tn] : 0.f)
-                      : p.epilogue == CGS_EPI_LRELU_BWD ? (y > 0.f ? v : 0.2f * v) : v * (1.f - y * y);
+                    v = epilogue_elem<EPI_FAST_TANH, EPI_MODES_BWD>(v, p.epilogue, ea[tn], 0.f, y);
                 } else {
-                    v = p.epilogue == CGS_EPI_LRELU ? fmaxf(v, 0.2f * v)
-                      : p.epilogue == CGS_EPI_AFFINE_RELU ? fmaxf(fmaf(ea[tn], v, eb[tn]), 0.f)
-                      : p.epilogue == CGS_EPI_TANH ? taps_tanh(v) : v;
+                    v = epilogue_elem<EPI_FAST_TANH, EPI_MODES_ALL & ~EPI_MODES_BWD>(v, p.epilogue, ea[tn], eb[tn], 0.f);
                 }
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), out_rsrc, o, 0, 0);      // (rows past M: past num_records, dropped)
             }
@@ -329,7 +296,7 @@ int cgs_conv_taps_launch(const CgsLayer& L, int B, const float* in, const float*
     if (blocks > 2048) blocks = 2048;               // persistent: 8 blocks of 4 independent waves per CU
     const int nt = L.Cs / 32;
     const int auxm = epilogue >= CGS_EPI_RELU_BWD_AFFINE ? (aux_signs ? 2 : 1) : 0;
-#define TAPSF_LAUNCH(NT_, AM_) hipLaunchKernelGGL((conv_taps_kernel<NT_, AM_>), dim3((unsigned)blocks), dim3(256), 0, s, p, (int)tiles)
+#define TAPSF_LAUNCH(NT_, AM_) CGS_LAUNCH_T(conv_taps_kernel, (NT_, AM_), dim3((unsigned)blocks), dim3(256), 0, s, p, (int)tiles)
 #define TAPSF_CASE(NT_) case NT_: if (auxm == 2) TAPSF_LAUNCH(NT_, 2); else if (auxm == 1) TAPSF_LAUNCH(NT_, 1); else TAPSF_LAUNCH(NT_, 0); break;
     switch (nt) {
         TAPSF_CASE(1) TAPSF_CASE(2) TAPSF_CASE(3)
@@ -338,8 +305,5 @@ int cgs_conv_taps_launch(const CgsLayer& L, int B, const float* in, const float*
 #undef TAPSF_CASE
 #undef TAPSF_LAUNCH
     CGS_CHECK_LAUNCH("conv_taps");
-    static thread_local char name[32];
-    snprintf(name, sizeof(name), "conv_taps_kernel<%d, %d>", nt, auxm);
-    cgs_note_kernel(name);
     return CGS_OK;
 }

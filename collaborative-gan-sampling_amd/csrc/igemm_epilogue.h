@@ -11,7 +11,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // SG: also leave the SIGN MASK of the stored values (p.sign_out; N % 32 == 0): the activation gradient of the layer above needs
 // one bit per element, not the fp32 tensor.  A row's 4-channel lanes sit in consecutive lanes, so v_cmp of element e over the
 // wave (ballot) holds, in the 8 bits starting at (lane & ~7), channels 4q + e (q = 0..7) of this lane's 32-channel group:
-// word = sum_e byte_e << 8e, i.e. bit 8 * (c % 4) + (c % 32) / 4 <-> channel c; the lane with (lane & 7) == 0 stores it into
+// word = sum_e byte_e << 8e (the word layout and its consumers: smallc.h, "sign masks"); the lane with (lane & 7) == 0 stores it into
 // the group's plane (one word per pixel, pixels contiguous: the consumer reads a tile row's words as one coalesced run).
 template <int EPI, int ROWS, int RPP, int LDE, bool SG>
 __device__ __forceinline__ void epilogue_rows_signs(const IgemmParams& p, const float* E, const int* rowpix_tile, int rsub, int c4,
