@@ -27,17 +27,13 @@
 //   offset + k >= capacity are dropped; the unclipped number of selected rows is left in *total.
 //
 // Two launches.  1. compact_scan_kernel, one block: a thread counts a contiguous run of rows, the 256 counts are scanned in thread
-// order, the thread writes the indices of its selected rows to list[] from its offset on.  2. compact_gather_kernel: dst row k <- src
-// row list[k] in 16-byte pieces (4-byte if the row length or a pointer does not allow it); a row shorter than a block shares the block
-// with its neighbours (256 / pieces rows per block), a longer one spans blocks: every store is coalesced and no lane idles for a 2-float row.
-#include "cgs_internal.h"
+// order, the thread writes the indices of its selected rows to list[] from its offset on.  2. rows_gather_kernel (rows.h, which also holds the launch
+// plan and the pool limits) with CompactedRows: dst row k <- src row list[k].
+#include "rows.h"
 
 #pragma clang fp contract(off)
 
-#define DRS_THREADS 256
-#define DRS_MAX_N 0x40000000L
-#define DRS_MAX_GROUPS (1 << 20)
-#define DRS_MAX_ROW (1 << 22)
+#define DRS_THREADS ROWS_THREADS
 #define DRS_LO 1e-14
 #define DRS_HI (1 - 1e-14)
 
@@ -233,40 +229,32 @@ __global__ __launch_bounds__(DRS_THREADS) void compact_scan_kernel(const unsigne
     if (t == DRS_THREADS - 1) total[0] = (int)incl;
 }
 
-// pieces: V per row; rows_per_block > 0: rows this short share a block (thread t: row t / pieces, piece t % pieces); 0: a row spans gridDim.y blocks
-template <typename V>
-__global__ __launch_bounds__(DRS_THREADS) void compact_gather_kernel(const V* __restrict__ src, const int* __restrict__ list, const int* __restrict__ total,
-                                                                     long room, int pieces, int rows_per_block, V* __restrict__ dst) {
-    const int t = threadIdx.x;
-    const long cnt = total[0] < room ? total[0] : room;
-    long k;
-    int c;
-    if (rows_per_block > 0) {
-        const int r = t / pieces;
-        if (r >= rows_per_block) return;
-        c = t - r * pieces;
-        k = (long)blockIdx.x * rows_per_block + r;
-    } else {
-        c = blockIdx.y * DRS_THREADS + t;
-        if (c >= pieces) return;
-        k = blockIdx.x;
+// the compaction's rows for rows_gather_kernel: the first min(total, room) entries of the scan's list, to dst (the offset is in the pointer)
+struct CompactedRows {
+    const int* list;
+    const int* total;
+    long room;
+    __device__ bool span(long long& at, long long& cnt) const {
+        at = 0;
+        cnt = total[0] < room ? total[0] : room;
+        return true;
     }
-    if (k >= cnt) return;
-    dst[(size_t)k * pieces + c] = src[(size_t)list[k] * pieces + c];
-}
-
-static bool drs_shape_ok(long b, long groups) { return b >= 1 && groups >= 1 && groups <= DRS_MAX_GROUPS && b * groups <= DRS_MAX_N; }
+    __device__ bool row(long long k, long long& r) const {
+        r = list[k];
+        return true;
+    }
+};
 
 extern "C" {
 
 size_t cgs_drs_ws_bytes(int b, int groups) {
-    if (!drs_shape_ok(b, groups)) return 0;
+    if (!rows_batches_ok(b, groups)) return 0;
     return (size_t)(1 + (long)groups + (long)b * groups) * sizeof(double);
 }
 
 int cgs_drs_decide(const float* sig, int b, int groups, const double* uniforms, double epsilon, double shift_percent, double* state, double* bounds,
                    double* P, unsigned char* mask, int* counts, void* ws, size_t ws_bytes, void* stream) {
-    if (!drs_shape_ok(b, groups) || !(shift_percent <= 100.0) || !(epsilon > 0.0))
+    if (!rows_batches_ok(b, groups) || !(shift_percent <= 100.0) || !(epsilon > 0.0))
         return cgs_set_error(CGS_EINVAL, "drs_decide: needs 1 <= b, 1 <= groups <= 2^20, b * groups <= 2^30, shift_percent <= 100 (negative: none), epsilon > 0 "
                              "(b=%d groups=%d shift_percent=%g epsilon=%g)", b, groups, shift_percent, epsilon);
     if (!sig || !uniforms || !state || !mask || !counts) return cgs_set_error(CGS_EINVAL, "drs_decide: null sig / uniforms / state / mask / counts");
@@ -292,7 +280,7 @@ int cgs_drs_decide(const float* sig, int b, int groups, const double* uniforms, 
 }
 
 int cgs_drs_set_max(const float* sig, int n, double* state, void* stream) {
-    if (n < 1 || n > DRS_MAX_N) return cgs_set_error(CGS_EINVAL, "drs_set_max: needs 1 <= n <= 2^30 (n=%d)", n);
+    if (n < 1 || n > ROWS_MAX_N) return cgs_set_error(CGS_EINVAL, "drs_set_max: needs 1 <= n <= 2^30 (n=%d)", n);
     if (!sig || !state) return cgs_set_error(CGS_EINVAL, "drs_set_max: null sig / state");
     hipLaunchKernelGGL(drs_set_max_kernel, dim3(1), dim3(DRS_THREADS), 0, (hipStream_t)stream, sig, n, state);
     CGS_CHECK_LAUNCH("drs_set_max");
@@ -300,13 +288,13 @@ int cgs_drs_set_max(const float* sig, int n, double* state, void* stream) {
 }
 
 size_t cgs_compact_rows_ws_bytes(int n) {
-    if (n < 1 || n > DRS_MAX_N) return 0;
+    if (n < 1 || n > ROWS_MAX_N) return 0;
     return (size_t)n * sizeof(int);
 }
 
 int cgs_compact_rows(const float* src, int n, int row, const unsigned char* mask, const unsigned char* take_all, int groups, float* dst, long long offset,
                      long long capacity, int* total, void* ws, size_t ws_bytes, void* stream) {
-    if (n < 0 || n > DRS_MAX_N || row < 1 || row > DRS_MAX_ROW || (long)n * row > (1L << 40) || offset < 0 || capacity < 0 || groups < 1 || (n > 0 && n % groups != 0))
+    if (!rows_source_ok(n, row) || offset < 0 || capacity < 0 || groups < 1 || (n > 0 && n % groups != 0))
         return cgs_set_error(CGS_EINVAL, "compact_rows: needs 0 <= n <= 2^30 in whole groups, 1 <= row <= 2^22, n * row <= 2^40, offset >= 0, capacity >= 0 "
                              "(n=%d row=%d groups=%d offset=%lld capacity=%lld)", n, row, groups, offset, capacity);
     if (!total) return cgs_set_error(CGS_EINVAL, "compact_rows: null total");
@@ -324,16 +312,7 @@ int cgs_compact_rows(const float* src, int n, int row, const unsigned char* mask
     const long room = capacity > offset ? (long)(capacity - offset) : 0;
     const long most = room < n ? room : n;                          // rows the gather can have to write
     if (most == 0) return CGS_OK;
-    float* out = dst + (size_t)offset * row;
-    const bool wide = row % 4 == 0 && (((uintptr_t)src | (uintptr_t)out) & 15) == 0;
-    const int pieces = wide ? row / 4 : row;
-    const int per = pieces <= DRS_THREADS ? DRS_THREADS / pieces : 0;
-    const dim3 grid(per ? (unsigned)((most + per - 1) / per) : (unsigned)most, per ? 1u : (unsigned)cgs_ceil_div(pieces, DRS_THREADS));
-    if (wide)
-        hipLaunchKernelGGL(compact_gather_kernel<float4>, grid, dim3(DRS_THREADS), 0, s, (const float4*)src, (const int*)ws, (const int*)total, room, pieces, per,
-                           (float4*)out);
-    else
-        hipLaunchKernelGGL(compact_gather_kernel<float>, grid, dim3(DRS_THREADS), 0, s, src, (const int*)ws, (const int*)total, room, pieces, per, out);
+    rows_gather_launch(src, dst + (size_t)offset * row, row, most, CompactedRows{(const int*)ws, total, room}, s);
     CGS_CHECK_LAUNCH("compact_rows");
     return CGS_OK;
 }

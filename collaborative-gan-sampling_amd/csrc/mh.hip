@@ -19,14 +19,11 @@
 // emission k stands at visit first + a0 + k (T + 1) and takes the last move at or before it (a binary search in the positions).  No
 // atomics, no floating-point sum: a rerun from the same state is bit-equal.  Contraction is off; the division is the correctly rounded
 // one and fp32 denormals are kept (the build has no fast-math): the reference's numpy arithmetic does both.
-#include "cgs_internal.h"
+#include "rows.h"
 
 #pragma clang fp contract(off)
 
-#define MH_THREADS 256
-#define MH_MAX_N 0x40000000L
-#define MH_MAX_GROUPS (1 << 20)
-#define MH_MAX_ROW (1 << 22)
+#define MH_THREADS ROWS_THREADS
 
 // ws: b ints, the move positions of the segment at hand
 __global__ __launch_bounds__(MH_THREADS) void mh_walk_kernel(const float* __restrict__ sig, int b, int groups, const double* __restrict__ uniforms, int T,
@@ -120,47 +117,36 @@ __global__ __launch_bounds__(MH_THREADS) void mh_walk_kernel(const float* __rest
     }
 }
 
-// dst[span[0] + k] = src[rows[k]], k < min(span[1], listed_max), while span[0] + k < capacity.
-// pieces: V per row; rows_per_block > 0: rows this short share a block (thread t: row t / pieces, piece t % pieces); 0: a row spans gridDim.y blocks
-template <typename V>
-__global__ __launch_bounds__(MH_THREADS) void mh_gather_kernel(const V* __restrict__ src, int n, const int* __restrict__ rows, int listed_max,
-                                                               const long long* __restrict__ span, long long capacity, int pieces, int rows_per_block,
-                                                               V* __restrict__ dst) {
-    const int t = threadIdx.x;
-    const long long at = span[0];
-    long long cnt = span[1] < listed_max ? span[1] : listed_max;
-    if (at < 0) return;
-    if (cnt > capacity - at) cnt = capacity - at;
-    long long k;
-    int c;
-    if (rows_per_block > 0) {
-        const int r = t / pieces;
-        if (r >= rows_per_block) return;
-        c = t - r * pieces;
-        k = (long long)blockIdx.x * rows_per_block + r;
-    } else {
-        c = blockIdx.y * MH_THREADS + t;
-        if (c >= pieces) return;
-        k = blockIdx.x;
+// the walk's rows for rows_gather_kernel: dst[span[0] + k] = src[rows[k]], k < min(span[1], listed_max), while span[0] + k < capacity; an index
+// outside the source copies nothing
+struct WalkedRows {
+    const int* rows;
+    const long long* span_io;
+    int n, listed_max;
+    long long capacity;
+    __device__ bool span(long long& at, long long& cnt) const {
+        at = span_io[0];
+        cnt = span_io[1] < listed_max ? span_io[1] : listed_max;
+        if (at < 0) return false;
+        if (cnt > capacity - at) cnt = capacity - at;
+        return true;
     }
-    if (k >= cnt) return;
-    const int r = rows[k];
-    if (r < 0 || r >= n) return;
-    dst[(size_t)(at + k) * pieces + c] = src[(size_t)r * pieces + c];
-}
-
-static bool mh_shape_ok(long b, long groups) { return b >= 1 && groups >= 1 && groups <= MH_MAX_GROUPS && b * groups <= MH_MAX_N; }
+    __device__ bool row(long long k, long long& r) const {
+        r = rows[k];
+        return r >= 0 && r < n;
+    }
+};
 
 extern "C" {
 
 size_t cgs_mh_ws_bytes(int b, int groups) {
-    if (!mh_shape_ok(b, groups)) return 0;
+    if (!rows_batches_ok(b, groups)) return 0;
     return (((size_t)b * sizeof(int)) + 7) & ~(size_t)7;
 }
 
 int cgs_mh_walk(const float* sig, int b, int groups, const double* uniforms, int T, int B, const unsigned char* take_all, double* state, long long* fill,
                 long long capacity, int* rows, int* counts, long long* span, void* ws, size_t ws_bytes, void* stream) {
-    if (!mh_shape_ok(b, groups) || T < 0 || B < 0 || capacity < 0)
+    if (!rows_batches_ok(b, groups) || T < 0 || B < 0 || capacity < 0)
         return cgs_set_error(CGS_EINVAL, "mh_walk: needs 1 <= b, 1 <= groups <= 2^20, b * groups <= 2^30, T >= 0, B >= 0, capacity >= 0 "
                              "(b=%d groups=%d T=%d B=%d capacity=%lld)", b, groups, T, B, capacity);
     if (!sig || !uniforms || !state || !fill || !rows || !counts || !span)
@@ -176,23 +162,14 @@ int cgs_mh_walk(const float* sig, int b, int groups, const double* uniforms, int
 
 int cgs_gather_rows(const float* src, int n, int row, const int* rows, int listed_max, const long long* span, float* dst, long long capacity,
                     void* stream) {
-    if (n < 0 || n > MH_MAX_N || row < 1 || row > MH_MAX_ROW || (long)n * row > (1L << 40) || listed_max < 0 || listed_max > MH_MAX_N || capacity < 0)
+    if (!rows_source_ok(n, row) || listed_max < 0 || listed_max > ROWS_MAX_N || capacity < 0)
         return cgs_set_error(CGS_EINVAL, "gather_rows: needs 0 <= n <= 2^30, 1 <= row <= 2^22, n * row <= 2^40, 0 <= listed_max <= 2^30, capacity >= 0 "
                              "(n=%d row=%d listed_max=%d capacity=%lld)", n, row, listed_max, capacity);
     if (!span) return cgs_set_error(CGS_EINVAL, "gather_rows: null span");
     const long most = capacity < listed_max ? (long)capacity : (long)listed_max;     // rows the gather can have to write
     if (n == 0 || most == 0) return CGS_OK;
     if (!src || !rows || !dst) return cgs_set_error(CGS_EINVAL, "gather_rows: null src / rows / dst");
-    const bool wide = row % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
-    const int pieces = wide ? row / 4 : row;
-    const int per = pieces <= MH_THREADS ? MH_THREADS / pieces : 0;
-    const dim3 grid(per ? (unsigned)((most + per - 1) / per) : (unsigned)most, per ? 1u : (unsigned)cgs_ceil_div(pieces, MH_THREADS));
-    hipStream_t s = (hipStream_t)stream;
-    if (wide)
-        hipLaunchKernelGGL(mh_gather_kernel<float4>, grid, dim3(MH_THREADS), 0, s, (const float4*)src, n, rows, listed_max, span, capacity, pieces, per,
-                           (float4*)dst);
-    else
-        hipLaunchKernelGGL(mh_gather_kernel<float>, grid, dim3(MH_THREADS), 0, s, src, n, rows, listed_max, span, capacity, pieces, per, dst);
+    rows_gather_launch(src, dst, row, most, WalkedRows{rows, span, n, listed_max, capacity}, (hipStream_t)stream);
     CGS_CHECK_LAUNCH("gather_rows");
     return CGS_OK;
 }

@@ -11,6 +11,84 @@ import numpy as np
 MIN_EFFICIENCY = 0.2     # nsgan/GAN.py:18
 
 
+class _FillCounter:
+    """The counter rule of the reference's fill loops, stated once (nsgan/GAN.py:311-346,348-376,398-426; synthetic/main.py:149-169,
+    182-202,229-253).  ``cnt`` rows accepted, ``cnt_propose`` proposals made: the first pass's ``eval_size`` proposals are the counter's
+    start (``start``).  While ``cnt_propose < max_propose`` a batch goes through the sampler; past that budget (GAN.py:283,323,357,410)
+    it is taken whole.  ``productive_only`` (main.py:163-169,196-202,245-251): a batch that yields nothing is not counted as proposed."""
+
+    def __init__(self, eval_size, min_efficiency=None, productive_only=False):
+        self.eval_size, self.productive_only = eval_size, productive_only
+        self.cnt, self.cnt_propose = 0, eval_size
+        self.max_propose = eval_size / min_efficiency if min_efficiency else float("inf")
+
+    def start(self, n):
+        """The first pass (``base``) yielded n rows."""
+        self.cnt = n
+
+    def through(self):
+        """Does the batch at hand go through the sampler (True), or is it taken whole?"""
+        return self.cnt_propose < self.max_propose
+
+    def through_ahead(self, i, b):
+        """``through()`` for the i-th batch of b proposals after the first pass, known before any batch is counted: every batch moves
+        the proposal counter by b (GAN.py:339,375,426; not so with ``productive_only``, whose loops do not draw ahead)."""
+        return self.eval_size + i * b < self.max_propose
+
+    def add(self, n, proposed):
+        """A batch of ``proposed`` proposals yielded n rows (taken whole: n = proposed) -> is the pool full?"""
+        self.cnt += n
+        if n > 0 or not self.productive_only:
+            self.cnt_propose += proposed
+        return self.cnt >= self.eval_size
+
+    def add_round(self, counts, b):
+        """``add`` for a round's batches of b in order, up to the one that fills the pool -> its index, None if the round does not."""
+        for j, n in enumerate(counts):
+            if self.add(int(n), b):
+                return j
+        return None
+
+    @property
+    def full(self):
+        return self.cnt >= self.eval_size
+
+    @property
+    def efficiency(self):
+        return self.cnt / self.cnt_propose
+
+
+def _host_fill(name, seed, accepted, propose, score, eval_size, base, min_efficiency, count_only_productive, max_rounds):
+    """The one-batch-at-a-time fill loop both host legs run.  ``seed()`` seeds the sampler; ``accepted(batch, sigmoids)`` -> the rows of
+    the batch it lets through."""
+    C = _FillCounter(eval_size, min_efficiency, count_only_productive)
+    out = None
+    seed()
+    if base is not None:
+        acc = accepted(base[0], base[1])
+        if acc.shape[0] > 0:
+            out = np.empty((eval_size,) + acc.shape[1:], dtype=acc.dtype)
+            k = min(acc.shape[0], eval_size)
+            out[:k] = acc[:k]
+        C.start(acc.shape[0])
+    rounds = 0
+    while not C.full:
+        rounds += 1
+        if rounds > max_rounds:
+            raise RuntimeError("%s: no sample accepted in %d rounds" % (name, max_rounds))
+        batch = propose()
+        B = batch.shape[0]
+        if out is None:
+            out = np.empty((eval_size,) + batch.shape[1:], dtype=np.float32)
+        acc = accepted(batch, score(batch)) if C.through() else batch               # (else: too inefficient, take the batch as is)
+        n = acc.shape[0]
+        if n > 0:
+            k = min(n, eval_size - C.cnt)
+            out[C.cnt:C.cnt + k] = acc[:k]
+        C.add(n, B)
+    return out, C.efficiency
+
+
 def collaborate(propose, score, mh_sampler, eval_size, real_sigmoid_mean, base=None, min_efficiency=None,
                 count_only_productive=False, max_rounds=100000):
     """Fill ``eval_size`` accepted samples.
@@ -19,44 +97,12 @@ def collaborate(propose, score, mh_sampler, eval_size, real_sigmoid_mean, base=N
     score(batch)         -> discriminator sigmoids [B, 1]               (fake_sigmoids)
     base                 -> optional (samples, sigmoids) for the first MH pass (nsgan uses the *standard* samples
                             there, nsgan/GAN.py:402, quirk Q10; synthetic uses the refined evaluation batch)
-    min_efficiency       -> nsgan/GAN.py:283,410: once proposals exceed eval_size / min_efficiency, stop rejecting
+    min_efficiency       -> nsgan/GAN.py:283,410: once the proposals exceed eval_size over min_efficiency, stop rejecting
                             and take whole batches
     count_only_productive-> synthetic/main.py:251: the proposal counter only advances for batches that yielded samples
     Returns (samples [eval_size, ...], efficiency = accepted / proposed)."""
-    out, cnt, cnt_propose = None, 0, eval_size
-    mh_sampler.set_score_curr(real_sigmoid_mean)                                   # nsgan/GAN.py:401
-    if base is not None:
-        acc = mh_sampler.sampling(base[0], base[1])
-        if acc.shape[0] > 0:
-            out = np.empty((eval_size,) + acc.shape[1:], dtype=acc.dtype)
-            k = min(acc.shape[0], eval_size)
-            out[:k] = acc[:k]
-        cnt = acc.shape[0]
-    max_propose = eval_size / min_efficiency if min_efficiency else float("inf")
-    rounds = 0
-    while cnt < eval_size:
-        rounds += 1
-        if rounds > max_rounds:
-            raise RuntimeError("collaborate: no sample accepted in %d rounds" % max_rounds)
-        batch = propose()
-        B = batch.shape[0]
-        if out is None:
-            out = np.empty((eval_size,) + batch.shape[1:], dtype=np.float32)
-        if cnt_propose < max_propose:
-            acc = mh_sampler.sampling(batch, score(batch))
-            n = acc.shape[0]
-            if n > 0:
-                k = min(n, eval_size - cnt)
-                out[cnt:cnt + k] = acc[:k]
-            cnt += n
-            if n > 0 or not count_only_productive:
-                cnt_propose += B
-        else:                                                                       # too inefficient: take the batch as is
-            k = min(B, eval_size - cnt)
-            out[cnt:cnt + k] = batch[:k]
-            cnt += B
-            cnt_propose += B
-    return out, cnt / cnt_propose
+    return _host_fill("collaborate", lambda: mh_sampler.set_score_curr(real_sigmoid_mean), mh_sampler.sampling,    # nsgan/GAN.py:401
+                      propose, score, eval_size, base, min_efficiency, count_only_productive, max_rounds)
 
 
 def engine_proposer(engine, steps, rate, rng=None, **refine_kw):
@@ -173,23 +219,27 @@ class FusedProposer:
         with self.torch.cuda.stream(self.streams[k]):
             moments.update(self.feat_dev[k], rows)
 
-    def real_moments(self, x, moments):
-        """Add D's features of a real evaluation set to ``moments``, ``batch`` samples per set of batch statistics like ``score_real``
-        (same padding of a last partial round; the padding batches are left out).  Returns ``moments``."""
+    def _real_rounds(self, x, each):
+        """A real evaluation set in rounds of ``G`` whole batches: ``each(i, m, round)`` on slot 0's stream with the round starting at
+        x[i] as a device tensor, of which the first m rows are x's -- a last partial round is padded with repeats of whole batches."""
         torch = self.torch
         n = self.b * self.G
         N = x.shape[0]
         if N % self.b:
             raise ValueError(f"{N} real samples are not whole batches of {self.b}")
-        e = self.engines[0]
         for i in range(0, N, n):
             xb = np.asarray(x[i:i + n], dtype=np.float32)
             m = xb.shape[0]
             if m < n:
                 xb = np.concatenate([xb] + [xb[:self.b]] * ((n - m) // self.b))
             with torch.cuda.stream(self.streams[0]):
-                _, f = e.score_with_features(torch.from_numpy(np.ascontiguousarray(xb)).to(self.dev))
-                moments.update(f, None if m == n else np.arange(m))
+                each(i, m, torch.from_numpy(np.ascontiguousarray(xb)).to(self.dev))
+
+    def real_moments(self, x, moments):
+        """Add D's features of a real evaluation set to ``moments``, ``batch`` samples per set of batch statistics like ``score_real``
+        (same padding of a last partial round; the padding batches are left out).  Returns ``moments``."""
+        e, n = self.engines[0], self.b * self.G
+        self._real_rounds(x, lambda i, m, xd: moments.update(e.score_with_features(xd)[1], None if m == n else np.arange(m)))
         return moments
 
     def score_real(self, x, chunk=None, calibration=None):
@@ -197,24 +247,125 @@ class FusedProposer:
         (``G`` batches per launch; x.shape[0] must be a multiple of ``batch``; a last partial round is padded with repeats
         of whole batches, whose scores are dropped).  ``calibration`` (a metrics.CalibrationStats, optional): the same scores, padding
         left out, are added to it with label 1 on the device (``sigmoid_real`` of nsgan/GAN.py:287-289)."""
-        torch = self.torch
-        n = self.b * self.G
-        N = x.shape[0]
-        if N % self.b:
-            raise ValueError(f"{N} real samples are not whole batches of {self.b}")
-        out = np.empty((N, 1), dtype=np.float32)
         e = self.engines[0]
-        for i in range(0, N, n):
-            xb = np.asarray(x[i:i + n], dtype=np.float32)
-            m = xb.shape[0]
-            if m < n:
-                xb = np.concatenate([xb] + [xb[:self.b]] * ((n - m) // self.b))
-            with torch.cuda.stream(self.streams[0]):
-                s = e.score(torch.from_numpy(np.ascontiguousarray(xb)).to(self.dev))
-                if calibration is not None:
-                    calibration.update(s[:m], 1)
-                out[i:i + m] = s.cpu().numpy()[:m]
+        out = np.empty((x.shape[0], 1), dtype=np.float32)
+
+        def each(i, m, xd):
+            s = e.score(xd)
+            if calibration is not None:
+                calibration.update(s[:m], 1)
+            out[i:i + m] = s.cpu().numpy()[:m]
+        self._real_rounds(x, each)
         return out
+
+
+_UNIFORM = lambda b: np.random.uniform(0, 1, size=b)                    # idpsampler.py:50, one per proposal
+_RAND = lambda b: np.random.rand(b)                                     # rejector.py:33, one per proposal
+
+
+def _draw_round(counter, drawn, G, b, zdim, draw, blank=None):
+    """One round of G logical batches of b from the global numpy stream, consumed per batch as the reference's loop consumes it
+    (nsgan/GAN.py:321-323,355-357,408-410): the z draw; then, if the batch will go through the sampler -- known ahead from ``drawn``, the
+    batches drawn before this round (``counter.through_ahead``) -- the leg's per-proposal ``draw(b)``, else ``blank`` and no draw; then a
+    snapshot of the stream, where the one-batch-at-a-time loop stands after this batch.
+    -> (z [G * b, zdim] fp32, the uniforms per batch, the take-whole flag per batch, the stream state after each batch)"""
+    zs, us, flags, states = [], [], [], []
+    for i in range(drawn, drawn + G):
+        zs.append(np.random.uniform(-1, 1, [b, zdim]).astype(np.float32))
+        through = counter.through_ahead(i, b)
+        us.append(draw(b) if through else blank)
+        flags.append(not through)
+        states.append(np.random.get_state())
+    return np.concatenate(zs), us, flags, states
+
+
+class _FusedFill:
+    """What the fused loops share around their per-round work: the argument checks, the counter, the rounds drawn ahead and in flight, the
+    tail; and, for the loops whose pool stays on the device (``pools=True``), the pool with D's features (``moments``) and scores
+    (``calibration``) of its rows beside it, and the event that orders a round's device work behind the round before, whichever stream
+    that ran on.  ``name``: the public function, for its messages; ``draw`` / ``blank``: ``_draw_round``'s."""
+
+    def __init__(self, name, proposer, eval_size, base, min_efficiency, max_rounds, moments, draw, blank=None, base_form="samples", pools=False,
+                 calibration=None):
+        if moments is not None:
+            if proposer.feat_dev is None:
+                raise ValueError(f"{name}(moments=...) needs FusedProposer(features=True)")
+            if base is not None and len(base) != 3:
+                raise ValueError(f"{name}(moments=...): base must carry features too, as ({base_form}, sigmoids, features)")
+        self.name, self.proposer, self.max_rounds, self.draw, self.blank = name, proposer, max_rounds, draw, blank
+        self.moments, self.calibration = moments, calibration
+        self.counter = _FillCounter(eval_size, min_efficiency)
+        self.drawn = self.rounds = 0                   # logical batches drawn so far; rounds taken
+        self.pending = []                              # rounds in flight: whatever ``launch`` returned, the slot first
+        self.final_state = self.pool = self.chain = None
+        self.t_wait = self.t_chain = 0.0
+        if pools:
+            import torch
+            self.torch = torch
+            new = lambda *row: torch.empty((eval_size,) + row, dtype=torch.float32, device=proposer.dev)
+            self.pool = new(*proposer.engines[0].A["img"])
+            self.feat_pool = new(proposer.feat_width) if moments is not None else None
+            self.sig_pool = new(1) if calibration is not None else None
+
+    def next_round(self, launch):
+        """The head of the loop: keep ``depth`` rounds in flight -- ``launch(z, uniforms, flags, states)`` queues one just drawn and
+        returns what the loop will want of it, the slot first -- and hand out the oldest."""
+        self.rounds += 1
+        if self.rounds > self.max_rounds:
+            raise RuntimeError("%s: no sample accepted in %d rounds" % (self.name, self.max_rounds))
+        P = self.proposer
+        while len(self.pending) < P.depth:
+            drawn = _draw_round(self.counter, self.drawn, P.G, P.b, P.zdim, self.draw, self.blank)
+            self.drawn += P.G
+            self.pending.append(launch(*drawn))
+        return self.pending.pop(0)
+
+    def count_round(self, counts, states):
+        """Count a round's batches -> the one that fills the pool (the stream will be rewound to where the reference's loop stands after
+        it), or None."""
+        j = self.counter.add_round(counts, self.proposer.b)
+        if j is not None:
+            self.final_state = states[j]
+        return j
+
+    def on_device(self, x):
+        torch = self.torch
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        return t.to(self.proposer.dev, torch.float32).contiguous()
+
+    def base_sources(self, base):
+        """-> (samples, sigmoids, features or None) of ``base`` on the device"""
+        return self.on_device(base[0]), self.on_device(base[1]), self.on_device(base[2]) if self.moments is not None else None
+
+    def slot_sources(self, slot):
+        P = self.proposer
+        return P.img_dev[slot], P.sig_dev[slot], P.feat_dev[slot] if self.moments is not None else None
+
+    def into_pools(self, imgs, sigs, feats):
+        """-> the (source, pool) pairs a round's rows are copied along"""
+        return [(src, pool) for src, pool in ((imgs, self.pool), (feats, self.feat_pool), (sigs, self.sig_pool)) if pool is not None]
+
+    def chain_behind(self, stream):
+        self.chain = self.torch.cuda.Event()
+        self.chain.record(stream)
+
+    def finish(self, stats, **seconds):
+        """The tail -> the efficiency."""
+        C, P = self.counter, self.proposer
+        for entry in self.pending:                     # rounds drawn ahead that the reference's loop never reaches: drained, discarded
+            P.result(entry[0])
+        if self.final_state is not None:
+            np.random.set_state(self.final_state)      # the global stream where the one-batch-at-a-time loop leaves it
+        if self.pool is not None:
+            self.torch.cuda.current_stream(P.dev).wait_event(self.chain)
+            if self.moments is not None:
+                self.moments.update(self.feat_pool)
+            if self.calibration is not None:
+                self.calibration.update(self.sig_pool, 0)
+        if stats is not None:
+            proposed = C.cnt_propose - C.eval_size
+            stats.update(rounds=self.rounds, proposed=proposed, discarded_batches=self.drawn - proposed // P.b, **seconds)
+        return C.efficiency
 
 
 def collaborate_fused(proposer, mh_sampler, eval_size, real_sigmoid_mean, base=None, min_efficiency=None, max_rounds=100000, stats=None,
@@ -227,13 +378,9 @@ def collaborate_fused(proposer, mh_sampler, eval_size, real_sigmoid_mean, base=N
     into the result are added to it on the device, one update per round; ``base`` must then be (images, sigmoids, features).  The
     samples, the efficiency and every draw are those of the run without it."""
     import time
-    if moments is not None:
-        if proposer.feat_dev is None:
-            raise ValueError("collaborate_fused(moments=...) needs FusedProposer(features=True)")
-        if base is not None and len(base) != 3:
-            raise ValueError("collaborate_fused(moments=...): base must carry features too, as (images, sigmoids, features)")
-    b, G = proposer.b, proposer.G
-    out, cnt, cnt_propose = None, 0, eval_size
+    F = _FusedFill("collaborate_fused", proposer, eval_size, base, min_efficiency, max_rounds, moments, _UNIFORM, base_form="images")
+    b, G, C = proposer.b, proposer.G, F.counter
+    out = None
     mh_sampler.set_score_curr(real_sigmoid_mean)                                   # nsgan/GAN.py:401
     if base is not None:
         if moments is None:
@@ -249,42 +396,19 @@ def collaborate_fused(proposer, mh_sampler, eval_size, real_sigmoid_mean, base=N
                 import torch
                 f = base[2] if isinstance(base[2], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(base[2], dtype=np.float32))
                 moments.update(f.to(proposer.dev), np.asarray(base_rows[:k], dtype=np.int64))
-        cnt = acc.shape[0]
-    max_propose = eval_size / min_efficiency if min_efficiency else float("inf")
-    t_chain = t_wait = 0.0
-    drawn = 0                                          # logical batches drawn so far: batch i meets cnt_propose = eval_size + i*b
-    pending = []                                       # rounds in flight: (slot, uniforms per logical batch, RNG state after each)
-
-    def launch_round():
-        nonlocal drawn
-        zs, us, states = [], [], []
-        for _ in range(G):
-            zs.append(np.random.uniform(-1, 1, [b, proposer.zdim]).astype(np.float32))          # nsgan/GAN.py:408
-            through_chain = eval_size + drawn * b < max_propose                                 # :410, known ahead: +b per iteration (:426)
-            us.append(np.random.uniform(0, 1, size=b) if through_chain else None)               # idpsampler.py:50, one per proposal
-            states.append(np.random.get_state())
-            drawn += 1
-        pending.append((proposer.launch(np.concatenate(zs)), us, states))
-
-    rounds = 0
-    final_state = None
-    while cnt < eval_size:
-        rounds += 1
-        if rounds > max_rounds:
-            raise RuntimeError("collaborate_fused: no sample accepted in %d rounds" % max_rounds)
-        while len(pending) < proposer.depth:
-            launch_round()
-        slot, us, states = pending.pop(0)
+        C.start(acc.shape[0])
+    while not C.full:
+        slot, us, flags, states = F.next_round(lambda z, *drawn: (proposer.launch(z), *drawn))
         t0 = time.perf_counter()
         imgs, sigs = proposer.result(slot)
         t1 = time.perf_counter()
-        t_wait += t1 - t0
+        F.t_wait += t1 - t0
         if out is None:
             out = np.empty((eval_size,) + imgs.shape[1:], dtype=np.float32)
         taken = []                                     # rows of this round's slot copied into ``out`` (moments)
-        for j in range(G):
-            batch = imgs[j * b:(j + 1) * b]
-            if cnt_propose < max_propose:
+        for j in range(G):                             # the host chain, a round behind the device (one counter call per batch: it is timed)
+            batch, cnt = imgs[j * b:(j + 1) * b], C.cnt
+            if not flags[j]:
                 # (a private copy of the batch's scores: the chain keeps a VIEW of the score it moved to -- idpsampler.py:52 -- and the
                 # pinned buffer behind ``sigs`` is overwritten when its slot is launched again)
                 rows = mh_sampler.walk(sigs[j * b:(j + 1) * b].copy(), us[j])
@@ -294,28 +418,18 @@ def collaborate_fused(proposer, mh_sampler, eval_size, real_sigmoid_mean, base=N
                     out[cnt:cnt + k] = batch[rows[:k]]
                     if moments is not None:
                         taken.extend(j * b + r for r in rows[:k])
-                cnt += n
             else:                                                                   # too inefficient: take the batch as is
-                k = min(b, eval_size - cnt)
+                n, k = b, min(b, eval_size - cnt)
                 out[cnt:cnt + k] = batch[:k]
                 if moments is not None:
                     taken.extend(range(j * b, j * b + k))
-                cnt += b
-            cnt_propose += b
-            if cnt >= eval_size:
-                final_state = states[j]
+            if C.add(n, b):
+                F.final_state = states[j]
                 break
         if taken:                                      # (the slot is launched again at the top of the loop at the earliest)
             proposer.accumulate(slot, np.asarray(taken, dtype=np.int64), moments)
-        t_chain += time.perf_counter() - t1
-    for slot, _, _ in pending:                         # rounds drawn ahead that the reference's loop never reaches: drained, discarded
-        proposer.result(slot)
-    if final_state is not None:
-        np.random.set_state(final_state)               # the global stream where the one-batch-at-a-time loop leaves it
-    if stats is not None:
-        stats.update(rounds=rounds, proposed=cnt_propose - eval_size, host_chain_s=t_chain, device_wait_s=t_wait,
-                     discarded_batches=drawn - (cnt_propose - eval_size) // b)
-    return out, cnt / cnt_propose
+        F.t_chain += time.perf_counter() - t1
+    return out, F.finish(stats, host_chain_s=F.t_chain, device_wait_s=F.t_wait)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -328,47 +442,16 @@ def reject_fill(propose, score, rejector, eval_size, real_sigmoid_max, base=None
     score(batch)         -> discriminator sigmoids [B, 1]                        (fake_sigmoids)
     rejector             -> a ``sampling.Rejector``; its bound is seeded with ``real_sigmoid_max`` (np.amax(sigmoid_real), GAN.py:314)
     base                 -> optional (samples, sigmoids) for the first pass (the standard evaluation set, GAN.py:315, main.py:153)
-    min_efficiency       -> GAN.py:283,323: once proposals exceed eval_size / min_efficiency, stop rejecting and take whole batches
+    min_efficiency       -> GAN.py:283,323: once the proposals exceed eval_size over min_efficiency, stop rejecting and take whole batches
     count_only_productive-> main.py:163-169: the proposal counter only advances for batches that yielded samples
     shift_percent        -> 100.0 at every call site of the reference
     One deliberate difference: GAN.py:326 stores a batch's accepted rows only when something had been accepted before, which leaves
     rows of np.empty garbage in the evaluation set while the counter moves on.  The rows are stored always here: uninitialised memory
     defines no parity.
     Returns (samples [eval_size, ...], efficiency = accepted / proposed)."""
-    out, cnt, cnt_propose = None, 0, eval_size
-    rejector.set_score_max(real_sigmoid_max)
-    if base is not None:
-        acc = rejector.sampling(base[0], base[1], epsilon=epsilon, shift_percent=shift_percent)
-        if acc.shape[0] > 0:
-            out = np.empty((eval_size,) + acc.shape[1:], dtype=acc.dtype)
-            k = min(acc.shape[0], eval_size)
-            out[:k] = acc[:k]
-        cnt = acc.shape[0]
-    max_propose = eval_size / min_efficiency if min_efficiency else float("inf")
-    rounds = 0
-    while cnt < eval_size:
-        rounds += 1
-        if rounds > max_rounds:
-            raise RuntimeError("reject_fill: no sample accepted in %d rounds" % max_rounds)
-        batch = propose()
-        B = batch.shape[0]
-        if out is None:
-            out = np.empty((eval_size,) + batch.shape[1:], dtype=np.float32)
-        if cnt_propose < max_propose:
-            acc = rejector.sampling(batch, score(batch), epsilon=epsilon, shift_percent=shift_percent)
-            n = acc.shape[0]
-            if n > 0:
-                k = min(n, eval_size - cnt)
-                out[cnt:cnt + k] = acc[:k]
-            cnt += n
-            if n > 0 or not count_only_productive:
-                cnt_propose += B
-        else:                                                                       # too inefficient: take the batch as is
-            k = min(B, eval_size - cnt)
-            out[cnt:cnt + k] = batch[:k]
-            cnt += B
-            cnt_propose += B
-    return out, cnt / cnt_propose
+    return _host_fill("reject_fill", lambda: rejector.set_score_max(real_sigmoid_max),
+                      lambda batch, sigmoids: rejector.sampling(batch, sigmoids, epsilon=epsilon, shift_percent=shift_percent),
+                      propose, score, eval_size, base, min_efficiency, count_only_productive, max_rounds)
 
 
 def reject_fill_fused(proposer, rejector, eval_size, real_sigmoid_max, base=None, min_efficiency=None, shift_percent=100.0, epsilon=1e-8,
@@ -386,115 +469,45 @@ def reject_fill_fused(proposer, rejector, eval_size, real_sigmoid_max, base=None
     Returns (pool: device fp32 tensor [eval_size, ...], efficiency) -- the rows, their order, the efficiency, ``rejector.D_tilde_M``
     and the global numpy stream afterwards are those of ``reject_fill`` with a host ``Rejector`` fed the same scores one batch at a time."""
     import time
-    import torch
-    if moments is not None:
-        if proposer.feat_dev is None:
-            raise ValueError("reject_fill_fused(moments=...) needs FusedProposer(features=True)")
-        if base is not None and len(base) != 3:
-            raise ValueError("reject_fill_fused(moments=...): base must carry features too, as (samples, sigmoids, features)")
-    b, G, dev = proposer.b, proposer.G, proposer.dev
-    n = b * G
-
-    def on_device(x):
-        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-        return t.to(dev, torch.float32).contiguous()
-
-    pool = feat_pool = sig_pool = None
-
-    def pools_for(rows_like):
-        nonlocal pool, feat_pool, sig_pool
-        if pool is None:
-            pool = torch.empty((eval_size,) + tuple(rows_like.shape[1:]), dtype=torch.float32, device=dev)
-            if moments is not None:
-                feat_pool = torch.empty((eval_size, proposer.feat_width), dtype=torch.float32, device=dev)
-            if calibration is not None:
-                sig_pool = torch.empty((eval_size, 1), dtype=torch.float32, device=dev)
+    F = _FusedFill("reject_fill_fused", proposer, eval_size, base, min_efficiency, max_rounds, moments, _RAND, pools=True, calibration=calibration)
+    torch, b, G, dev, C = F.torch, proposer.b, proposer.G, proposer.dev, F.counter
 
     def compact_all(imgs, sigs, feats, offset, take_all=None):
-        rejector.compact(imgs, pool, offset, take_all)
-        if feat_pool is not None:
-            rejector.compact(feats, feat_pool, offset, take_all)
-        if sig_pool is not None:
-            rejector.compact(sigs, sig_pool, offset, take_all)
+        for src, pool in F.into_pools(imgs, sigs, feats):
+            rejector.compact(src, pool, offset, take_all)
 
-    cnt, cnt_propose = 0, eval_size
     rejector.set_score_max(real_sigmoid_max)                                           # nsgan/GAN.py:314
     if base is not None:
-        imgs, sigs = on_device(base[0]), on_device(base[1])
-        pools_for(imgs)
+        imgs, sigs, feats = F.base_sources(base)
         _, counts, _ = rejector.decide_device(sigs, None, shift_percent, epsilon, groups=1)     # :315, the whole set as one batch
-        compact_all(imgs, sigs, on_device(base[2]) if moments is not None else None, 0)
-        cnt = int(counts.cpu()[0])
-    chain = torch.cuda.Event()                                                         # (the rounds run on the slots' streams)
-    chain.record(torch.cuda.current_stream(dev))
-    max_propose = eval_size / min_efficiency if min_efficiency else float("inf")
-    t_wait = 0.0
-    drawn = 0                                          # logical batches drawn so far: batch i meets cnt_propose = eval_size + i*b
-    pending = []                                       # rounds in flight: (slot, uniforms per logical batch, RNG state after each)
-
-    def launch_round():
-        nonlocal drawn
-        zs, us, states = [], [], []
-        for _ in range(G):
-            zs.append(np.random.uniform(-1, 1, [b, proposer.zdim]).astype(np.float32))          # nsgan/GAN.py:321
-            through = eval_size + drawn * b < max_propose                                       # :323, known ahead: +b per iteration (:339)
-            us.append(np.random.rand(b) if through else None)                                   # rejector.py:33, one per proposal
-            states.append(np.random.get_state())
-            drawn += 1
-        pending.append((proposer.launch(np.concatenate(zs), refine=False, to_host=False), us, states))
-
-    rounds = 0
-    final_state = None
-    while cnt < eval_size:
-        rounds += 1
-        if rounds > max_rounds:
-            raise RuntimeError("reject_fill_fused: no sample accepted in %d rounds" % max_rounds)
-        while len(pending) < proposer.depth:
-            launch_round()
-        slot, us, states = pending.pop(0)
-        G1 = sum(u is not None for u in us)            # the batches that go through the rejector come first: the counter only grows
-        imgs, sigs = proposer.img_dev[slot], proposer.sig_dev[slot]
-        pools_for(imgs)
+        compact_all(imgs, sigs, feats, 0)
+        C.start(int(counts.cpu()[0]))
+    F.chain_behind(torch.cuda.current_stream(dev))                                     # (the rounds run on the slots' streams)
+    while not C.full:
+        slot, us, flags, states = F.next_round(lambda z, *drawn: (proposer.launch(z, refine=False, to_host=False), *drawn))
+        G1 = G - sum(flags)                            # the batches that go through the rejector come first: the counter only grows
+        imgs, sigs, feats = F.slot_sources(slot)
         st = proposer.streams[slot]
         t0 = time.perf_counter()
         with torch.cuda.stream(st):                    # (behind the slot's ``done``: the same stream)
-            st.wait_event(chain)                       # the decide + compact before this one, whichever stream it ran on
-            mask = torch.zeros(n, dtype=torch.uint8, device=dev) if G1 < G else None
+            st.wait_event(F.chain)                     # the decide + compact before this one, whichever stream it ran on
+            mask = torch.zeros(b * G, dtype=torch.uint8, device=dev) if G1 < G else None
             if G1 > 0:
                 m, counts, _ = rejector.decide_device(sigs[:G1 * b], np.concatenate(us[:G1]), shift_percent, epsilon, groups=G1)
                 if mask is None:
                     mask = m
                 else:
                     mask[:G1 * b].copy_(m)
-            flags = None if G1 == G else [j >= G1 for j in range(G)]
             rejector.last_accept = mask
-            compact_all(imgs, sigs, proposer.feat_dev[slot] if moments is not None else None, min(cnt, eval_size), flags)
+            compact_all(imgs, sigs, feats, min(C.cnt, eval_size), flags if G1 < G else None)
             accepted = counts.cpu().numpy() if G1 > 0 else np.zeros(0, dtype=np.int32)          # the round's only read-back
-        t_wait += time.perf_counter() - t0
-        for j in range(G):
-            cnt += int(accepted[j]) if j < G1 else b
-            cnt_propose += b
-            if cnt >= eval_size:
-                final_state = states[j]
-                if j < G1 - 1:                         # the reference's loop stops here: later batches never reach its rejector
-                    with torch.cuda.stream(st):
-                        rejector.rewind_to(j)
-                break
-        chain = torch.cuda.Event()
-        chain.record(st)
-    for slot, _, _ in pending:                         # rounds drawn ahead that the reference's loop never reaches: drained, discarded
-        proposer.result(slot)
-    if final_state is not None:
-        np.random.set_state(final_state)               # the global stream where the one-batch-at-a-time loop leaves it
-    torch.cuda.current_stream(dev).wait_event(chain)
-    if moments is not None:
-        moments.update(feat_pool)
-    if calibration is not None:
-        calibration.update(sig_pool, 0)
-    if stats is not None:
-        stats.update(rounds=rounds, proposed=cnt_propose - eval_size, device_wait_s=t_wait,
-                     discarded_batches=drawn - (cnt_propose - eval_size) // b)
-    return pool, cnt / cnt_propose
+        F.t_wait += time.perf_counter() - t0
+        j = F.count_round(list(accepted) + [b] * (G - G1), states)
+        if j is not None and j < G1 - 1:               # the reference's loop stops here: later batches never reach its rejector
+            with torch.cuda.stream(st):
+                rejector.rewind_to(j)
+        F.chain_behind(st)
+    return F.pool, F.finish(stats, device_wait_s=F.t_wait)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -518,104 +531,47 @@ def hastings_fill_fused(proposer, sampler, eval_size, real_sigmoid_mean, base=No
     ``d_curr`` and ``cnt_chain`` and the global numpy stream afterwards are those of ``collaborate`` with a host ``IndependenceSampler``
     fed the same scores one batch at a time."""
     import time
-    import torch
-    if moments is not None:
-        if proposer.feat_dev is None:
-            raise ValueError("hastings_fill_fused(moments=...) needs FusedProposer(features=True)")
-        if base is not None and len(base) != 3:
-            raise ValueError("hastings_fill_fused(moments=...): base must carry features too, as (samples, sigmoids, features)")
-    b, G, dev = proposer.b, proposer.G, proposer.dev
-
-    def on_device(x):
-        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-        return t.to(dev, torch.float32).contiguous()
-
-    pool = torch.empty((eval_size,) + tuple(proposer.engines[0].A["img"]), dtype=torch.float32, device=dev)
-    feat_pool = torch.empty((eval_size, proposer.feat_width), dtype=torch.float32, device=dev) if moments is not None else None
-    sig_pool = torch.empty((eval_size, 1), dtype=torch.float32, device=dev) if calibration is not None else None
+    F = _FusedFill("hastings_fill_fused", proposer, eval_size, base, min_efficiency, max_rounds, moments, _UNIFORM, blank=np.zeros(proposer.b),
+                   pools=True, calibration=calibration)
+    torch, G, dev, C = F.torch, proposer.G, proposer.dev, F.counter
     fill = torch.zeros(1, dtype=torch.int64, device=dev)               # rows the pool has received, unclipped; the walks advance it
 
     def walk_and_gather(imgs, sigs, feats, uniforms, groups, take_all):
         rows, counts, span = sampler.walk_device(sigs, uniforms, groups, take_all, fill, eval_size)
-        sampler.gather(imgs, pool, span, rows)
-        if feat_pool is not None:
-            sampler.gather(feats, feat_pool, span, rows)
-        if sig_pool is not None:
-            sampler.gather(sigs, sig_pool, span, rows)
+        for src, pool in F.into_pools(imgs, sigs, feats):
+            sampler.gather(src, pool, span, rows)
         return counts
 
-    cnt, cnt_propose = 0, eval_size
     sampler.set_score_curr(real_sigmoid_mean)                                          # nsgan/GAN.py:350,401
     if base is not None:
-        imgs, sigs = on_device(base[0]), on_device(base[1])
-        if tuple(imgs.shape[1:]) != tuple(pool.shape[1:]):
-            raise ValueError(f"hastings_fill_fused: base samples {tuple(imgs.shape)} are not rows of the proposer's {tuple(pool.shape[1:])}")
-        counts = walk_and_gather(imgs, sigs, on_device(base[2]) if moments is not None else None, None, 1, None)      # :351,402
-        cnt = int(counts.cpu()[0])
-    chain = torch.cuda.Event()                                                         # (the rounds run on the slots' streams)
-    chain.record(torch.cuda.current_stream(dev))
-    max_propose = eval_size / min_efficiency if min_efficiency else float("inf")
-    t_wait = t_chain = 0.0
-    drawn = 0                                          # logical batches drawn so far: batch i meets cnt_propose = eval_size + i*b
-    pending = []                                       # rounds in flight: (slot, device counts, RNG state after each logical batch)
+        imgs, sigs, feats = F.base_sources(base)
+        if tuple(imgs.shape[1:]) != tuple(F.pool.shape[1:]):
+            raise ValueError(f"hastings_fill_fused: base samples {tuple(imgs.shape)} are not rows of the proposer's {tuple(F.pool.shape[1:])}")
+        C.start(int(walk_and_gather(imgs, sigs, feats, None, 1, None).cpu()[0]))       # :351,402
+    F.chain_behind(torch.cuda.current_stream(dev))                                     # (the rounds run on the slots' streams)
 
-    def launch_round():
-        nonlocal drawn, chain
-        zs, us, flags, states = [], [], [], []
-        for _ in range(G):
-            zs.append(np.random.uniform(-1, 1, [b, proposer.zdim]).astype(np.float32))          # nsgan/GAN.py:355,408
-            through_chain = eval_size + drawn * b < max_propose                                 # :357,410, known ahead: +b per iteration
-            us.append(np.random.uniform(0, 1, size=b) if through_chain else np.zeros(b))        # idpsampler.py:50, one per proposal
-            flags.append(not through_chain)
-            states.append(np.random.get_state())
-            drawn += 1
-        st = proposer.streams[proposer.launched % proposer.depth]
+    def launch_round(z, us, flags, states):            # the walk is queued with the round: ``pending`` holds its device counts
+        st =proposer.streams[proposer.launched % proposer.depth]
         with torch.cuda.stream(st):                    # (uploaded while the slot's stream is idle: a copy from pageable memory waits for the stream)
             u_dev = torch.from_numpy(np.concatenate(us)).to(dev)
             flags_dev = torch.from_numpy(np.asarray(flags, dtype=np.uint8)).to(dev) if any(flags) else None
-        slot = proposer.launch(np.concatenate(zs), refine=refine, to_host=False)
+        slot = proposer.launch(z, refine=refine, to_host=False)
         with torch.cuda.stream(st):                    # (behind the slot's ``done``: the same stream)
-            st.wait_event(chain)                       # the walk before this one, whichever stream it ran on: the chain state is shared
-            counts = walk_and_gather(proposer.img_dev[slot], proposer.sig_dev[slot], proposer.feat_dev[slot] if moments is not None else None,
-                                     u_dev, G, flags_dev)
-            chain = torch.cuda.Event()
-            chain.record(st)
-        pending.append((slot, counts, states))
+            st.wait_event(F.chain)                     # the walk before this one, whichever stream it ran on: the chain state is shared
+            counts = walk_and_gather(*F.slot_sources(slot), u_dev, G, flags_dev)
+            F.chain_behind(st)
+        return slot, counts, states
 
-    rounds = 0
-    final_state = None
-    while cnt < eval_size:
-        rounds += 1
-        if rounds > max_rounds:
-            raise RuntimeError("hastings_fill_fused: no sample accepted in %d rounds" % max_rounds)
-        while len(pending) < proposer.depth:
-            launch_round()
-        slot, counts, states = pending.pop(0)
+    while not C.full:
+        slot, counts, states = F.next_round(launch_round)
         t0 = time.perf_counter()
         with torch.cuda.stream(proposer.streams[slot]):
             emitted = counts.cpu().numpy()                                             # the round's only read-back
         t1 = time.perf_counter()
-        t_wait += t1 - t0
-        for j in range(G):
-            cnt += int(emitted[j])                     # (never -1 here: the pool was not full when this batch was reached)
-            cnt_propose += b
-            if cnt >= eval_size:
-                final_state = states[j]
-                break
-        t_chain += time.perf_counter() - t1
-    for slot, _, _ in pending:                         # rounds drawn ahead that the reference's loop never reaches: walked by nobody, drained
-        proposer.result(slot)
-    if final_state is not None:
-        np.random.set_state(final_state)               # the global stream where the one-batch-at-a-time loop leaves it
-    torch.cuda.current_stream(dev).wait_event(chain)
-    if moments is not None:
-        moments.update(feat_pool)
-    if calibration is not None:
-        calibration.update(sig_pool, 0)
-    if stats is not None:
-        stats.update(rounds=rounds, proposed=cnt_propose - eval_size, host_chain_s=t_chain, device_wait_s=t_wait,
-                     discarded_batches=drawn - (cnt_propose - eval_size) // b)
-    return pool, cnt / cnt_propose
+        F.t_wait += t1 - t0
+        F.count_round(emitted, states)                 # (never -1 here: the pool was not full when this batch was reached)
+        F.t_chain += time.perf_counter() - t1
+    return F.pool, F.finish(stats, host_chain_s=F.t_chain, device_wait_s=F.t_wait)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

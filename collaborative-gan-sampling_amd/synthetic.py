@@ -295,9 +295,11 @@ def landscape_grid(scale, ngrids=21):
 def _device_chain_fill(mh, discriminator, propose, eval_size, real_sigmoid_mean, base, base_sig):
     """The fill loop of synthetic/main.py:182-202 / 229-253 with the chain on the device (``mh``: a sampling.DeviceIndependenceSampler):
     scores stay where D left them, every round is ONE segment of ``eval_size`` proposals, the pool is a device tensor; per round the host
-    reads one count and applies the productive-only counter rule (:196-202, :245-251) to it.  ``propose()`` -> the round's proposals
-    (host array or device tensor); the round's uniforms are drawn after it, where the reference's ``sampling`` call stands.
+    reads one count and hands it to the productive-only counter rule (:196-202, :245-251: ``cnt_propose += eval_size`` for a round that
+    yielded rows, and for no other).  ``propose()`` -> the round's proposals (host array or device tensor); the round's uniforms are drawn
+    after it, where the reference's ``sampling`` call stands.
     -> (pool: device fp32 [eval_size, 2], efficiency)"""
+    from .evaluate import _FillCounter
     dev = discriminator.dev
     pool = torch.empty((eval_size, 2), dtype=torch.float32, device=dev)
     fill = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -307,14 +309,54 @@ def _device_chain_fill(mh, discriminator, propose, eval_size, real_sigmoid_mean,
         rows, counts, span = mh.walk_device(sig, None, 1, None, fill, eval_size)
         mh.gather(x, pool, span, rows)
         return int(counts.cpu()[0])                                                    # the round's only read-back
-    cnt, cnt_propose = one_round(_upload(base, dev), base_sig), eval_size
-    while cnt < eval_size:
+    C = _FillCounter(eval_size, productive_only=True)
+    C.start(one_round(_upload(base, dev), base_sig))
+    while not C.full:
         x = _upload(propose(), dev)
-        n = one_round(x, discriminator.sigmoid_and_saliency(x, want_saliency=False)[0])
-        if n > 0:
-            cnt += n
-            cnt_propose += eval_size                                                   # :202,251: only productive rounds count
-    return pool, cnt / cnt_propose
+        C.add(one_round(x, discriminator.sigmoid_and_saliency(x, want_saliency=False)[0]), eval_size)
+    return pool, C.efficiency
+
+
+def _check_maps(maps):
+    if maps is not None and ("scale" not in maps or set(maps) - {"scale", "nbins", "grid_scale", "ngrids"}):
+        raise ValueError(f"maps: needs 'scale', takes 'nbins', 'grid_scale', 'ngrids'; got {sorted(maps)}")
+
+
+def _quality_of(diagnostics, target_batch, centeroids, thres, dev):
+    """-> quality(samples): the reference's four 2-D metrics of a pool against ``target_batch`` (utils_sampling.py:132-184) -- on the host
+    as the reference computes them, or, with ``diagnostics``, from ``metrics.ModeStats`` on the device."""
+    from . import metrics as Mx
+    if diagnostics:
+        real_modes = Mx.ModeStats(centeroids, thres, dev).update(_upload(target_batch, dev)).state()
+
+    def quality(samples):
+        if diagnostics:
+            return Mx.mode_metrics(Mx.ModeStats(centeroids, thres, dev).update(_upload(samples, dev)).state(), real_modes)
+        if isinstance(samples, torch.Tensor):
+            samples = samples.cpu().numpy()
+        mean_dist, good = Mx.metrics_distance(samples, centeroids, thres)
+        return {"mean_dist": float(mean_dist), "good": float(good),
+                "kl": float(Mx.metrics_diversity(target_batch, samples, centeroids, thres)),
+                "js": float(Mx.metrics_distribution(target_batch, samples, centeroids, thres))}
+    return quality
+
+
+def _batch_generator(generate, n):
+    """``generate`` as a callable: an ``MLPGenerator`` becomes training-mode G on fresh noise, n per batch (main.py:158-159,239-240)."""
+    if not isinstance(generate, MLPGenerator):
+        return generate
+    noise = NoiseDataset()
+    return lambda: generate.generate(noise.next_batch(n)).cpu().numpy()
+
+
+def _maps_of(maps, pools, discriminator):
+    """The density maps of ``pools`` ((name, pool) pairs) and D's landscape, as ``maps`` asks for them (``evaluate_collaborative``)."""
+    from . import metrics as Mx
+    scale, nbins = maps["scale"], maps.get("nbins", 100)
+    out = {name: Mx.kde_grid(pool, scale, nbins, device=discriminator.dev)[0] for name, pool in pools}
+    grid = landscape_grid(maps.get("grid_scale", scale), maps.get("ngrids", 21))
+    out["landscape"] = (grid, discriminator.sigmoid_and_saliency(grid, want_saliency=False)[0].cpu().numpy())
+    return out
 
 
 def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_batch, centeroids, std, mh_sampler=None, diagnostics=False,
@@ -342,30 +384,14 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
     from . import metrics as Mx
     from .evaluate import collaborate
     from .sampling import DeviceIndependenceSampler, IndependenceSampler
-    thres = std * 4
-    if maps is not None and ("scale" not in maps or set(maps) - {"scale", "nbins", "grid_scale", "ngrids"}):      # before any draw
-        raise ValueError(f"maps: needs 'scale', takes 'nbins', 'grid_scale', 'ngrids'; got {sorted(maps)}")
-    if diagnostics:
-        dev = discriminator.dev
-        real_modes = Mx.ModeStats(centeroids, thres, dev).update(_upload(target_batch, dev)).state()
-
-    def quality(samples):
-        if diagnostics:
-            return Mx.mode_metrics(Mx.ModeStats(centeroids, thres, dev).update(_upload(samples, dev)).state(), real_modes)
-        if isinstance(samples, torch.Tensor):
-            samples = samples.cpu().numpy()
-        mean_dist, good = Mx.metrics_distance(samples, centeroids, thres)
-        return {"mean_dist": float(mean_dist), "good": float(good),
-                "kl": float(Mx.metrics_diversity(target_batch, samples, centeroids, thres)),
-                "js": float(Mx.metrics_distribution(target_batch, samples, centeroids, thres))}
-    if isinstance(generate, MLPGenerator):                                             # training-mode G on fresh noise, main.py:239-240
-        G, noise, n = generate, NoiseDataset(), len(eval_batch)
-        generate = lambda: G.generate(noise.next_batch(n)).cpu().numpy()
+    _check_maps(maps)                                                                  # before any draw
+    quality = _quality_of(diagnostics, target_batch, centeroids, std * 4, discriminator.dev)
+    generate = _batch_generator(generate, len(eval_batch))
     _, score = proposer(refiner, generate, discriminator)
     real_sigmoid = score(target_batch)                                                 # main.py:116
     out = {"standard": quality(eval_batch)}
     if diagnostics:                                                                    # :116-117,123: straight from D's device output
-        cal = Mx.CalibrationStats(dev)
+        cal = Mx.CalibrationStats(discriminator.dev)
         cal.update(discriminator.sigmoid_and_saliency(eval_batch, want_saliency=False)[0], 0)
         cal.update(discriminator.sigmoid_and_saliency(target_batch, want_saliency=False)[0], 1)
         out["calibration"] = cal.diagnostics()
@@ -384,11 +410,8 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
     if keep_pools:
         out["pools"] = {"refinement": refined, "collaborate": samples}
     if maps is not None:
-        scale, nbins = maps["scale"], maps.get("nbins", 100)
-        pools = (("standard", eval_batch), ("refinement", refined), ("collaborate", samples), ("target", target_batch))
-        out["maps"] = {name: Mx.kde_grid(pool, scale, nbins, device=discriminator.dev)[0] for name, pool in pools}
-        grid = landscape_grid(maps.get("grid_scale", scale), maps.get("ngrids", 21))
-        out["maps"]["landscape"] = (grid, discriminator.sigmoid_and_saliency(grid, want_saliency=False)[0].cpu().numpy())
+        out["maps"] = _maps_of(maps, (("standard", eval_batch), ("refinement", refined), ("collaborate", samples), ("target", target_batch)),
+                               discriminator)
     return out
 
 
@@ -408,29 +431,14 @@ def evaluate_calibrated(discriminator, generate, eval_batch, target_batch, cente
     left there; the hastings pool is then a device tensor too, handed to ``ModeStats`` and ``kde_grid`` as it is; samples, ``eff`` and the
     numpy stream are those of the host sampler."""
     from . import metrics as Mx
-    from .evaluate import collaborate
+    from .evaluate import _FillCounter, collaborate
     from .sampling import DeviceIndependenceSampler, DeviceRejector, IndependenceSampler
-    thres = std * 4
     dev = discriminator.dev
-    if maps is not None and ("scale" not in maps or set(maps) - {"scale", "nbins", "grid_scale", "ngrids"}):      # before any draw
-        raise ValueError(f"maps: needs 'scale', takes 'nbins', 'grid_scale', 'ngrids'; got {sorted(maps)}")
-    if diagnostics:
-        real_modes = Mx.ModeStats(centeroids, thres, dev).update(_upload(target_batch, dev)).state()
-
-    def quality(samples):
-        if diagnostics:
-            return Mx.mode_metrics(Mx.ModeStats(centeroids, thres, dev).update(_upload(samples, dev)).state(), real_modes)
-        if isinstance(samples, torch.Tensor):
-            samples = samples.cpu().numpy()
-        mean_dist, good = Mx.metrics_distance(samples, centeroids, thres)
-        return {"mean_dist": float(mean_dist), "good": float(good),
-                "kl": float(Mx.metrics_diversity(target_batch, samples, centeroids, thres)),
-                "js": float(Mx.metrics_distribution(target_batch, samples, centeroids, thres))}
-    if isinstance(generate, MLPGenerator):                                             # training-mode G on fresh noise, main.py:158-159
-        G, noise, n_gen = generate, NoiseDataset(), len(eval_batch)
-        generate = lambda: G.generate(noise.next_batch(n_gen)).cpu().numpy()
-    sigmoid = lambda x: discriminator.sigmoid_and_saliency(x, want_saliency=False)[0]
     eval_size = len(eval_batch)
+    _check_maps(maps)                                                                  # before any draw
+    quality = _quality_of(diagnostics, target_batch, centeroids, std * 4, dev)
+    generate = _batch_generator(generate, eval_size)
+    sigmoid = lambda x: discriminator.sigmoid_and_saliency(x, want_saliency=False)[0]
     eval_dev = _upload(eval_batch, dev)
     real_sig, eval_sig = sigmoid(target_batch), sigmoid(eval_dev)                      # main.py:116-117
     out = {"standard": quality(eval_batch)}
@@ -445,15 +453,14 @@ def evaluate_calibrated(discriminator, generate, eval_batch, target_batch, cente
     rej.set_score_max(real_sig)                                                        # :152
     _, counts = rej.decide(eval_sig, shift_percent=100.0)                              # :153
     rej.compact(eval_dev, pool, 0)
-    cnt, cnt_propose = int(counts[0]), eval_size
-    while cnt < eval_size:
+    C = _FillCounter(eval_size, productive_only=True)                                  # :163-169
+    C.start(int(counts[0]))
+    while not C.full:
         extra = _upload(generate(), dev)                                               # :158-159
         _, counts = rej.decide(sigmoid(extra), shift_percent=100.0)                    # :160-161
-        rej.compact(extra, pool, cnt)
-        if counts[0] > 0:
-            cnt += int(counts[0])
-            cnt_propose += eval_size                                                   # :169 (its own constant, whatever the batch holds)
-    out["rejection"] = dict(quality(pool), eff=float(cnt / cnt_propose))
+        rej.compact(extra, pool, C.cnt)
+        C.add(int(counts[0]), eval_size)                                               # :169 (its own constant, whatever the batch holds)
+    out["rejection"] = dict(quality(pool), eff=float(C.efficiency))
     # hastings, :182-202
     mh = mh_sampler if mh_sampler is not None else IndependenceSampler(T=20)           # main.py:80
     score = lambda batch: sigmoid(batch).cpu().numpy()
@@ -467,11 +474,8 @@ def evaluate_calibrated(discriminator, generate, eval_batch, target_batch, cente
     if keep_pools:
         out["pools"] = {"rejection": pool, "hastings": samples}
     if maps is not None:
-        scale, nbins = maps["scale"], maps.get("nbins", 100)
-        pools = (("standard", eval_batch), ("rejection", pool.cpu().numpy()), ("hastings", samples), ("target", target_batch))
-        out["maps"] = {name: Mx.kde_grid(p, scale, nbins, device=dev)[0] for name, p in pools}
-        grid = landscape_grid(maps.get("grid_scale", scale), maps.get("ngrids", 21))
-        out["maps"]["landscape"] = (grid, sigmoid(grid).cpu().numpy())
+        out["maps"] = _maps_of(maps, (("standard", eval_batch), ("rejection", pool.cpu().numpy()), ("hastings", samples), ("target", target_batch)),
+                               discriminator)
     return out
 
 

@@ -129,7 +129,7 @@ def test_set_score_max(n):
 
 
 # ---------------------------------------------------------------------------------------------------------------- compact
-ROWS = [1, 2, 3, 784, 12288]
+ROWS = [1, 2, 3, 784, 1024, 1028, 12288]                             # 1024: 256 float4 pieces, a block; 1028: 257, the first row that spans two
 NS = [1, 64, 65, 2048]
 MASKS = ["none", "all", "alternating", "random", "take_all"]
 

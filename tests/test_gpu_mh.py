@@ -89,7 +89,7 @@ def test_read_back_walk_and_drawn_uniforms_follow_the_host_class():
 
 
 # ---------------------------------------------------------------------------------------------------------------- gather
-@pytest.mark.parametrize("row", [1, 2, 3, 63, 75, 784])
+@pytest.mark.parametrize("row", [1, 2, 3, 63, 75, 784, 1024, 1028])     # 1024: 256 float4 pieces, a block; 1028: 257, the first row that spans two
 @pytest.mark.parametrize("off", [0, 1], ids=["aligned", "off-by-one-float"])
 def test_gather_rows(row, off):
     from cgs_amd import kernels as K
