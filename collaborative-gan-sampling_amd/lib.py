@@ -31,6 +31,8 @@ class IgemmPlanInfo(C.Structure):
                 ("prio_t", C.c_int * 3), ("row_order", C.c_int), ("perm_len", C.c_int * 4), ("executed_flops", C.c_double)]
 
 
+KNN_NN_MIN, KNN_RADII, KNN_BALL_COUNT = 0, 1, 2
+
 FORM_PLAIN, FORM_STATS, FORM_NSTATS, FORM_SIGNS, FORM_UPDATE = 0, 1, 2, 3, 4
 REDUCE_KERNELS = ("none", "tail_reduce_kernel<false>", "tail_reduce_kernel<true>", "splitk_reduce_kernel<false>", "splitk_reduce_kernel<true>",
                   "splitk_reduce_stats_kernel")          # by CGS_REDUCE_*
@@ -159,6 +161,11 @@ SIGNATURES = {
     "cgs_mh_ws_bytes": (_z, [_i, _i]),
     "cgs_mh_walk": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _ll, _p, _p, _p, _p, _z, _p]),
     "cgs_gather_rows": (_i, [_p, _i, _i, _p, _i, _p, _p, _ll, _p]),
+    "cgs_knn_plan": (_i, [_i, _i, _i, C.POINTER(C.c_int)]),
+    "cgs_knn_ws_bytes": (_z, [_i] * 5),
+    "cgs_nn_min": (_i, [_p, _i, _p, _i, _i, _i, _p, _p, _p, _z, _p]),
+    "cgs_knn_radii": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p, _z, _p]),
+    "cgs_ball_count": (_i, [_p, _i, _p, _i, _i, _p, _p, _p, _z, _p]),
 }
 
 _lib = None

@@ -587,3 +587,122 @@ def kde_grid(samples, scale, nbins=100, bw_scale=0.5, device=None):
     zi = DensityMap(axis, axis, whiten, dev).update(x).values(norm)
     lo, hi = float(zi.min()), float(zi.max())
     return zi, (lo, max(hi * 0.2, lo))
+
+
+# ----------------------------------------------------------------------------- nearest-neighbour metrics (csrc/knn.hip; DESIGN.md section 33)
+def _sq_distances(a, b):
+    """[len(a), len(b)] float64 squared distances in the difference form, the coordinates added in ascending order: the sum scipy's
+    ``cdist`` takes the root of."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError(f"pools {a.shape} and {b.shape} are not [n, d] and [m, d]")
+    out = np.zeros((a.shape[0], b.shape[0]))
+    for k in range(a.shape[1]):
+        diff = a[:, k, None] - b[None, :, k]
+        out += diff * diff
+    return out
+
+
+def pairwise_distance(real_batch, model_batch):
+    """The reference's ``pairwise_distance`` (sampling/utils_sampling.py:126-130) on host arrays, without scipy: per model sample the
+    distance to the nearest real sample, the real sample of the SAME index standing 10 farther away than it is (``cdist + 10 I``, minimum
+    over the real axis).  Like the reference it needs pools of one length."""
+    dist = np.sqrt(_sq_distances(real_batch, model_batch))
+    if dist.shape[0] != dist.shape[1]:
+        raise ValueError(f"pairwise_distance: the 10 I term needs pools of one length, got {dist.shape[0]} and {dist.shape[1]}")
+    return np.min(dist + 10.0 * np.identity(dist.shape[0]), axis=0)
+
+
+def _device_pool(x, who, device=None):
+    import torch
+    if isinstance(x, torch.Tensor):
+        if not x.is_cuda and device is None:
+            raise ValueError(f"{who}: a host tensor needs device=")
+        x = x.to(x.device if device is None else device, torch.float32).contiguous()
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        x = torch.from_numpy(np.array(x, dtype=np.float32, order="C")).to(dev)
+    if x.dim() != 2:
+        raise ValueError(f"{who}: a pool is [n, d], got {tuple(x.shape)}")
+    return x
+
+
+def nn_distance(real, model, exclude_self=None):
+    """``pairwise_distance`` on device pools (fp32 [n, d]; host arrays are uploaded) through ``cgs_nn_min``: per MODEL sample j the distance
+    to the nearest real sample and that sample's index, as device tensors (float64 [m], int32 [m]).  ``exclude_self``: True = the
+    reference's rule, the real sample of index j counts as 10 farther away than it is (needs pools of one length; the index is j where
+    that term still wins); False = the plain nearest neighbour; None = True for pools of one length, else False.  The root of the
+    minimum is the minimum of the roots (sqrt is monotone and correctly rounded), so with True the result equals
+    ``pairwise_distance`` wherever the kernel's D2 equals the host's."""
+    import torch
+    from . import knn
+    model = _device_pool(model, "nn_distance")
+    real = _device_pool(real, "nn_distance", model.device)
+    if exclude_self is None:
+        exclude_self = real.shape[0] == model.shape[0]
+    d2, idx, self_d2 = knn.nn_min(model, real, exclude_self=exclude_self)
+    dist = torch.sqrt(d2)
+    if not exclude_self:
+        return dist, idx
+    own = torch.sqrt(self_d2) + 10.0
+    j = torch.arange(model.shape[0], dtype=torch.int32, device=model.device)
+    wins = (own < dist) | ((own == dist) & (j < idx))
+    return torch.where(wins, own, dist), torch.where(wins, j, idx)
+
+
+def knn_radii(x, k):
+    """The distance from every row of the device pool ``x`` (fp32 [n, d]) to its k-th nearest OTHER row (1 <= k <= 8, k < n): float64 [n]
+    on the device.  (``cgs_amd.knn.knn_radii`` returns the squares and takes a second pool.)"""
+    import torch
+    from . import knn
+    return torch.sqrt(knn.knn_radii(_device_pool(x, "knn_radii"), k))
+
+
+def _manifold_result(hits_fake, balls_fake, hits_real, covered, k, n_real, n_fake):
+    return {"precision": hits_fake / n_fake, "recall": hits_real / n_real, "density": balls_fake / (k * n_fake), "coverage": covered / n_real,
+            "k": int(k), "n_real": int(n_real), "n_fake": int(n_fake)}
+
+
+def manifold_metrics(real_feat, fake_feat, k=5):
+    """The k-nearest-neighbour manifold metrics of two device pools of features (fp32 [n_real, d] and [n_fake, d]; host arrays are
+    uploaded): precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020), every comparison ``<=``, with
+    rho_k(x) the distance from x to its k-th nearest other row of its own pool:
+        count_j   = #{i : |f_j - r_i| <= rho_k(r_i)}            precision = mean_j [count_j > 0]       density = sum_j count_j / (k n_fake)
+        recall    = the precision formula with the pools exchanged (radii within the fakes)
+        coverage  = mean_i [min_j |r_i - f_j| <= rho_k(r_i)]
+    Two ``knn_radii``, two ``ball_count`` and one ``nn_min`` launch (csrc/knn.hip; the comparisons are made on the squares), four integer
+    sums in torch on the device, ONE readback of four integers.  Returns {"precision", "recall", "density", "coverage", "k", "n_real",
+    "n_fake"}.  NOT additive across ranks: a k-th neighbour needs the whole pool, so ranks first assemble it (``dist.gather_pool``) and
+    one of them calls this; there is no collective of its own."""
+    import torch
+    from . import knn
+    real = _device_pool(real_feat, "manifold_metrics")
+    fake = _device_pool(fake_feat, "manifold_metrics", real.device)
+    if real.shape[1] != fake.shape[1]:
+        raise ValueError(f"manifold_metrics: features of width {real.shape[1]} and {fake.shape[1]}")
+    r2_real, r2_fake = knn.knn_radii(real, k), knn.knn_radii(fake, k)
+    count_fake = knn.ball_count(fake, real, r2_real)
+    count_real = knn.ball_count(real, fake, r2_fake)
+    near_d2, _, _ = knn.nn_min(real, fake)
+    sums = torch.stack([(count_fake > 0).sum(), count_fake.sum(dtype=torch.int64), (count_real > 0).sum(), (near_d2 <= r2_real).sum()]).cpu()
+    hits_fake, balls_fake, hits_real, covered = (int(v) for v in sums)
+    return _manifold_result(hits_fake, balls_fake, hits_real, covered, k, real.shape[0], fake.shape[0])
+
+
+def manifold_metrics_host(real_feat, fake_feat, k=5):
+    """``manifold_metrics`` in float64 numpy on host arrays: the same definitions on the full distance matrices."""
+    real, fake = np.asarray(real_feat, dtype=np.float64), np.asarray(fake_feat, dtype=np.float64)
+
+    def radii2(x):
+        if not 1 <= k < len(x):
+            raise ValueError(f"manifold_metrics_host: k = {k} needs 1 <= k < {len(x)} rows")
+        d2 = _sq_distances(x, x)
+        np.fill_diagonal(d2, np.inf)
+        return np.partition(d2, k - 1, axis=1)[:, k - 1]
+    r2_real, r2_fake = radii2(real), radii2(fake)
+    cross = _sq_distances(fake, real)                                       # [n_fake, n_real]
+    count_fake = (cross <= r2_real[None, :]).sum(axis=1)
+    count_real = (cross.T <= r2_fake[None, :]).sum(axis=1)
+    covered = cross.min(axis=0) <= r2_real
+    return _manifold_result(int((count_fake > 0).sum()), int(count_fake.sum()), int((count_real > 0).sum()), int(covered.sum()), k,
+                            len(real), len(fake))

@@ -322,6 +322,21 @@ def _check_maps(maps):
         raise ValueError(f"maps: needs 'scale', takes 'nbins', 'grid_scale', 'ngrids'; got {sorted(maps)}")
 
 
+def _check_manifold(manifold):
+    if manifold is not None and (set(manifold) != {"k"} or not 1 <= int(manifold["k"]) <= 8):
+        raise ValueError(f"manifold: takes 'k' in 1..8 alone; got {manifold}")
+
+
+def _add_manifold(out, manifold, pools, target_batch, dev):
+    """Each row of ``out`` named in ``pools`` ((name, pool) pairs) gains precision / recall / density / coverage of its pool against
+    ``target_batch``, the 2-D points as features (``metrics.manifold_metrics``: csrc/knn.hip)."""
+    from . import metrics as Mx
+    target = _upload(target_batch, dev)
+    for name, pool in pools:
+        got = Mx.manifold_metrics(target, _upload(pool, dev), k=int(manifold["k"]))
+        out[name].update({key: got[key] for key in ("precision", "recall", "density", "coverage")})
+
+
 def _quality_of(diagnostics, target_batch, centeroids, thres, dev):
     """-> quality(samples): the reference's four 2-D metrics of a pool against ``target_batch`` (utils_sampling.py:132-184) -- on the host
     as the reference computes them, or, with ``diagnostics``, from ``metrics.ModeStats`` on the device."""
@@ -360,7 +375,7 @@ def _maps_of(maps, pools, discriminator):
 
 
 def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_batch, centeroids, std, mh_sampler=None, diagnostics=False,
-                           maps=None, keep_pools=False):
+                           maps=None, keep_pools=False, manifold=None):
     """The "shape"-mode evaluation of synthetic/main.py:215-263 on the device refiner: refine the evaluation batch, report its
     quality, then D-score -> MH fill (thinning T = 20, chain seeded with mean(real_sigmoid)) until ``len(eval_batch)`` samples
     are accepted (proposal counter advancing only for productive batches, :251) and report the collaborative sample's
@@ -380,11 +395,15 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
     proposals' scores stay where D left them, the pool is a device tensor handed to ``ModeStats`` and ``kde_grid`` as it is, one count
     per round comes back; samples, ``eff`` and the numpy stream are those of the host sampler.  ``keep_pools=True`` adds "pools": the
     refinement pool and the collaborate pool (a device tensor on the device route).
+    ``manifold=dict(k=...)``: the rows "standard", "refinement" and "collaborate" each gain "precision", "recall", "density" and
+    "coverage" of their pool against ``target_batch`` (``metrics.manifold_metrics``, the 2-D points as features, 1 <= k <= 8).  Like the
+    maps they draw nothing and are computed after everything else: the draws and every other entry are those of ``manifold=None``.
     """
     from . import metrics as Mx
     from .evaluate import collaborate
     from .sampling import DeviceIndependenceSampler, IndependenceSampler
     _check_maps(maps)                                                                  # before any draw
+    _check_manifold(manifold)
     quality = _quality_of(diagnostics, target_batch, centeroids, std * 4, discriminator.dev)
     generate = _batch_generator(generate, len(eval_batch))
     _, score = proposer(refiner, generate, discriminator)
@@ -412,11 +431,13 @@ def evaluate_collaborative(refiner, discriminator, generate, eval_batch, target_
     if maps is not None:
         out["maps"] = _maps_of(maps, (("standard", eval_batch), ("refinement", refined), ("collaborate", samples), ("target", target_batch)),
                                discriminator)
+    if manifold is not None:
+        _add_manifold(out, manifold, (("standard", eval_batch), ("refinement", refined), ("collaborate", samples)), target_batch, discriminator.dev)
     return out
 
 
 def evaluate_calibrated(discriminator, generate, eval_batch, target_batch, centeroids, std, rejector=None, mh_sampler=None, diagnostics=False,
-                        maps=None, keep_pools=False):
+                        maps=None, keep_pools=False, manifold=None):
     """The "calibrate"-mode evaluation of synthetic/main.py:137-214: the standard pool's quality, then the two samplers a calibrated D
     is for.  Rejection (:149-181): a ``sampling.DeviceRejector`` with its bound seeded by max(real_sigmoid) and shift_percent = 100
     decides the evaluation batch and then fresh generator batches of ``len(eval_batch)`` until that many samples are accepted (the
@@ -429,13 +450,15 @@ def evaluate_calibrated(discriminator, generate, eval_batch, target_batch, cente
     The numpy stream is consumed as the reference consumes it: per rejection batch one uniform per proposal, then the chain's.
     ``mh_sampler``: a ``sampling.DeviceIndependenceSampler`` runs the hastings leg's chain on the device (csrc/mh.hip) on the scores D
     left there; the hastings pool is then a device tensor too, handed to ``ModeStats`` and ``kde_grid`` as it is; samples, ``eff`` and the
-    numpy stream are those of the host sampler."""
+    numpy stream are those of the host sampler.  ``manifold=dict(k=...)`` as in ``evaluate_collaborative``: the rows "standard", "rejection"
+    and "hastings" gain the four numbers of their pool against ``target_batch``, after everything else."""
     from . import metrics as Mx
     from .evaluate import _FillCounter, collaborate
     from .sampling import DeviceIndependenceSampler, DeviceRejector, IndependenceSampler
     dev = discriminator.dev
     eval_size = len(eval_batch)
     _check_maps(maps)                                                                  # before any draw
+    _check_manifold(manifold)
     quality = _quality_of(diagnostics, target_batch, centeroids, std * 4, dev)
     generate = _batch_generator(generate, eval_size)
     sigmoid = lambda x: discriminator.sigmoid_and_saliency(x, want_saliency=False)[0]
@@ -476,6 +499,8 @@ def evaluate_calibrated(discriminator, generate, eval_batch, target_batch, cente
     if maps is not None:
         out["maps"] = _maps_of(maps, (("standard", eval_batch), ("rejection", pool.cpu().numpy()), ("hastings", samples), ("target", target_batch)),
                                discriminator)
+    if manifold is not None:
+        _add_manifold(out, manifold, (("standard", eval_dev), ("rejection", pool), ("hastings", samples)), target_batch, dev)
     return out
 
 

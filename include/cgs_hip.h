@@ -788,6 +788,41 @@ int cgs_mh_walk(const float* sig, int b, int groups, const double* uniforms, int
 int cgs_gather_rows(const float* src, int n, int row, const int* rows, int listed_max, const long long* span, float* dst, long long capacity,
                     void* stream);
 
+/* ---- nearest-neighbour queries between two pools of feature vectors, in double on the device (csrc/knn.hip) ----
+ * qry: [m][d] fp32, ref: [n][d] fp32, 1 <= d <= 2048, 1 <= m, n <= 2^30.  Every entry point evaluates the squared distance in the
+ * DIFFERENCE form, in double, k ascending, one fused multiply-add per coordinate:
+ *     D2(j, i) = sum_k (double(q_jk) - double(r_ik))^2
+ * so that equal rows give exactly 0, D2(j, i) and D2(i, j) are the same bits, and the error is relative: |D2^ - D2| <= (d + 3) 2^-53 D2.
+ * The n x m matrix is never stored: a block owns 64 queries, walks its share of the 64-reference tiles and keeps the answer per query.
+ * Where there are too few query tiles to fill the device the references are cut into `splits` runs of `tiles_per_split` tiles
+ * (cgs_knn_plan; a function of (m, n) alone), each run leaves a partial answer in ws and a second launch merges them in ascending order.
+ * The merges are order-free by construction (below), so the result does not depend on the split.  No atomics: a rerun is bit-equal.
+ * cgs_nn_min: out_d2[j] = min_i D2(j, i), out_idx[j] = the LOWEST i that attains it.  exclude_self = 1 (needs n == m; ref is then the
+ *     query pool itself or a pool of the same length) leaves i == j out of the minimum and stores D2(j, j) in out_d2[m + j]: out_d2 is
+ *     then 2 m doubles.  No candidate (exclude_self with n == 1): out_d2[j] = +inf, out_idx[j] = -1.  The reference's pairwise_distance
+ *     (sampling/utils_sampling.py:126-130: min over i of cdist + 10 I) is min(sqrt(out_d2[j]), sqrt(out_d2[m + j]) + 10) exactly,
+ *     because sqrt is monotone and correctly rounded: the minimum of the roots is the root of the minimum.
+ * cgs_knn_radii: out_r2[j] = the k-th smallest D2 from row j of x to the rows of `other` ([n_other][d]), or, other == NULL, to the rows
+ *     of x itself -- without row j where exclude_self = 1 (exclude_self needs other == NULL).  1 <= k <= 8; the k-th smallest VALUE of
+ *     a multiset does not depend on how ties are ordered.  Fewer than k candidates is CGS_EINVAL with a text, not an infinity.
+ * cgs_ball_count: out_count[j] = #{ i : D2(j, i) <= ref_r2[i] }, ref_r2: n doubles on the device.
+ * cgs_knn_ws_bytes(op, m, n, d, k): bytes of ws for op = CGS_KNN_NN_MIN / CGS_KNN_RADII / CGS_KNN_BALL_COUNT (k: of the radii only; m = rows
+ *     of the query side, n = rows of the reference side), at least 8; 0 = the call would be refused.  ws 8-byte aligned, CGS_EWORKSPACE
+ *     if smaller.  cgs_knn_plan: plan[4] = {query tiles, reference tiles, tiles_per_split, splits}; returns 0 where the shape is refused.
+ * Errors (CGS_EINVAL before any launch and before any pointer is looked at): d, m, n out of range, exclude_self not 0 / 1 or with
+ * n != m, k outside 1..8, fewer than k candidates.  Non-finite inputs give unspecified values, no fault. */
+#define CGS_KNN_NN_MIN 0
+#define CGS_KNN_RADII 1
+#define CGS_KNN_BALL_COUNT 2
+int cgs_knn_plan(int m, int n, int d, int* plan);
+size_t cgs_knn_ws_bytes(int op, int m, int n, int d, int k);
+int cgs_nn_min(const float* qry, int m, const float* ref, int n, int d, int exclude_self, double* out_d2, int* out_idx, void* ws,
+               size_t ws_bytes, void* stream);
+int cgs_knn_radii(const float* x, int n, int d, int k, int exclude_self, const float* other, int n_other, double* out_r2, void* ws,
+                  size_t ws_bytes, void* stream);
+int cgs_ball_count(const float* qry, int m, const float* ref, int n, int d, const double* ref_r2, int* out_count, void* ws, size_t ws_bytes,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
